@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: NormalizingFlow.log_prob throughput, BASELINE.json cfg 2 (configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `ms_per_step`, and the
+`roofline` of the fused kernel over the timed region).  `--full` adds everything that takes runs of its own: the grouped-launch
+median of the fused kernel, `roofline_elementwise`, `configs`, `training` and the CPU baselines (the `--no-*` options below
+trim a full run).  `--dump-outputs DIR` writes what the last timed step returned to its caller, the fp64 batch sum, as
+DIR/log_prob_sum.npy (rank 0); the inputs are seeded, so two builds can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (fresh child
 processes of `torch.distributed.run`, before this process has touched a GPU) and relays rank 0's JSON line.
@@ -63,6 +69,10 @@ def spawn_ranks(args) -> int:
            '--gpus', str(args.gpus), '--steps', str(args.steps), '--warmup', str(args.warmup)]
     if args.no_cpu_baseline:
         cmd.append('--no-cpu-baseline')
+    if getattr(args, 'full', False):
+        cmd.append('--full')
+    if getattr(args, 'dump_outputs', None):
+        cmd += ['--dump-outputs', os.path.abspath(args.dump_outputs)]
     if getattr(args, 'backend', 'nccl') != 'nccl':
         cmd += ['--backend', args.backend]
     return subprocess.run(cmd, env=env).returncode
@@ -526,20 +536,27 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra-configs', action='store_true', help='skip the cfg 3 / cfg 4 lines (N = 1)')
-    ap.add_argument('--no-training', action='store_true', help='skip the training-step entries (N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the kernel medians, the element-wise roofline, the other configurations, the '
+                         'training steps and the CPU baselines (each a run of its own)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s result as DIR/log_prob_sum.npy (fp64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baselines')
+    ap.add_argument('--no-extra-configs', action='store_true', help='(--full) skip the cfg 3 / cfg 4 lines (N = 1)')
+    ap.add_argument('--no-training', action='store_true', help='(--full) skip the training-step entries (N = 1)')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl',
                     help='collective backend of the N > 1 run.  nccl (= RCCL over xGMI) is the product path: one rank per GPU.  gloo '
                          'exists so that the WHOLE multi-rank control path (rank spawn, rendezvous, the async all-reduce ring, the '
                          'MAX over ranks of the elapsed time, rank 0\'s line) can run on a box with fewer GPUs than ranks: ranks share '
                          'GPUs round-robin and the numbers are a plumbing check, not a measurement')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args))
     # the CPU baseline's worker pool starts HERE, before anything below touches the GPU (see cpu_pool)
-    pool = start_cpu_pool() if args.gpus == 1 and 'WORLD_SIZE' not in os.environ and not args.no_cpu_baseline else None
+    pool = (start_cpu_pool() if args.full and args.gpus == 1 and 'WORLD_SIZE' not in os.environ and not args.no_cpu_baseline
+            else None)
 
     import torch
     import torch.distributed as dist
@@ -626,27 +643,24 @@ def main():
     elapsed = t.item()
     assert torch.isfinite(total).all()
     total_value = total.item()
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives: the (all-reduced) fp64 batch sum of the last timed step
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'log_prob_sum.npy'), total.detach().cpu().numpy().astype(np.float64))
 
     result = None
     if rank == 0:
         rows_total = ROWS_PER_GPU * world * args.steps
         # dominant kernel: the fused flow kernel, one launch per step; average launch period over the timed region itself
         # (HIP events ev0 / ev1; each step also launches a 4.6 us zero-fill of the 8-byte result and, since round 6, the exact
-        # redo pass of sx_flow_run2 -- on this data an empty list: its workgroups read one word and leave); the median of grouped
-        # launches afterwards is kept beside it
+        # redo pass of sx_flow_run2 -- on this data an empty list: its workgroups read one word and leave); --full: the median of
+        # grouped launches afterwards is kept beside it
         k_avg_ms = ev0.elapsed_time(ev1) / args.steps
-        with torch.no_grad():
-            _, k_med_ms = event_ms(lambda: flow.log_prob_sum(x, outs[0]), 10)
         achieved_tflops = FLOPS_PER_ROW * ROWS_PER_GPU / (k_avg_ms * 1e-3) / 1e12
         peak = PEAK_F16_MFMA_TFLOPS
         pmc = load_profile('pmc_cfg2.json')
         sq = load_profile('sq_cfg2.json')
-        # standalone element-wise affine coupling kernel (params precomputed in HBM), HBM roofline
-        from stribor_amd.flows.affine import run_affine_kernel
-        params = torch.randn(ROWS_PER_GPU, DIM, device=dev) * 0.1
-        e_avg_ms, _ = event_ms(lambda: run_affine_kernel(x, params, DIM, None, 0, DIM // 2, True, True, True, -1.0), 10)
-        del params
-        e_gbs = ELEMWISE_BYTES_PER_ROW * ROWS_PER_GPU / (e_avg_ms * 1e-3) / 1e9
         result = {
             'metric': 'log_prob samples/sec, D=64 8-layer affine-coupling',
             'value': rows_total / elapsed,
@@ -672,7 +686,7 @@ def main():
                          'traffic': pmc.get('flow_fused_kernel', {}).get('hbm_bytes_per_launch'),
                          'traffic_pmc_build_id': pmc.get('build_id'), 'traffic_stale_profile': pmc.get('stale_profile'),
                          'library_build_id': _hip.build_id(),
-                         'avg_kernel_ms': k_avg_ms, 'median_kernel_ms': k_med_ms,
+                         'avg_kernel_ms': k_avg_ms,
                          'gemm_arithmetic': 'fp16 x 3 split on v_mfma_f32_32x32x16_f16, fp32 accumulate '
                                             '(3 MFMA products per algorithmic product)',
                          'mfma_executed_tflops': achieved_tflops * 3,
@@ -687,15 +701,25 @@ def main():
                          'algorithmic_flops_per_launch': FLOPS_PER_ROW * ROWS_PER_GPU,
                          'algorithmic_bytes_per_launch': BYTES_PER_ROW * ROWS_PER_GPU,
                          'hbm_frac_of_same_kernel': BYTES_PER_ROW * ROWS_PER_GPU / (k_avg_ms * 1e-3) / 1e9 / PEAK_HBM_GBS},
-            'roofline_elementwise': {'kernel': 'affine_coupling_vec_kernel<bf16,reverse> (16 B per lane)', 'bound': 'hbm',
-                                     'achieved': e_gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': e_gbs / PEAK_HBM_GBS,
-                                     'traffic': (pmc.get('affine_coupling_vec_kernel') or pmc.get('affine_coupling_vec4_kernel') or {}).get('hbm_bytes_per_launch'),
-                                     'traffic_pmc_build_id': pmc.get('build_id'),
-                                     'avg_kernel_ms': e_avg_ms,
-                                     'algorithmic_bytes_per_launch': ELEMWISE_BYTES_PER_ROW * ROWS_PER_GPU},
             'log_prob_sum': total_value,
         }
-        if world == 1 and not args.no_extra_configs:
+        if args.full:
+            with torch.no_grad():
+                _, result['roofline']['median_kernel_ms'] = event_ms(lambda: flow.log_prob_sum(x, outs[0]), 10)
+            # standalone element-wise affine coupling kernel (params precomputed in HBM), HBM roofline
+            from stribor_amd.flows.affine import run_affine_kernel
+            params = torch.randn(ROWS_PER_GPU, DIM, device=dev) * 0.1
+            e_avg_ms, _ = event_ms(lambda: run_affine_kernel(x, params, DIM, None, 0, DIM // 2, True, True, True, -1.0), 10)
+            del params
+            e_gbs = ELEMWISE_BYTES_PER_ROW * ROWS_PER_GPU / (e_avg_ms * 1e-3) / 1e9
+            result['roofline_elementwise'] = {
+                'kernel': 'affine_coupling_vec_kernel<bf16,reverse> (16 B per lane)', 'bound': 'hbm',
+                'achieved': e_gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': e_gbs / PEAK_HBM_GBS,
+                'traffic': (pmc.get('affine_coupling_vec_kernel') or pmc.get('affine_coupling_vec4_kernel') or {}).get('hbm_bytes_per_launch'),
+                'traffic_pmc_build_id': pmc.get('build_id'),
+                'avg_kernel_ms': e_avg_ms,
+                'algorithmic_bytes_per_launch': ELEMWISE_BYTES_PER_ROW * ROWS_PER_GPU}
+        if args.full and world == 1 and not args.no_extra_configs:
             # BASELINE cfg 3 / cfg 4 at their full 2^20 rows, fp32 storage, same process, after the headline; beside each its own
             # CPU baseline (the oracle on this box's cores, bounded sample), and cfg 2 once more in the exact-fp32 arithmetic
             extra_steps = max(5, min(args.steps, 20))
@@ -788,7 +812,7 @@ def main():
                 for t_ in tr:
                     if t_.get('ms_per_step') is not None:
                         result['train_ms_' + t_['name']] = t_['ms_per_step']
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(desc, state, pool=pool)
         # LAST keys of the line (the driver's record keeps the tail of stdout): first-level scalars of the other single-GPU BASELINE
         # configurations of this run -- rows/s, ms per step and fraction of the dense fp16 MFMA peak (cfg2_exact: of the fp32 MFMA peak)

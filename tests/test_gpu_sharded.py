@@ -76,3 +76,26 @@ def test_bench_starts_its_own_ranks(backend, world, run_child):
     assert 'configs' not in r and 'training' not in r            # the single-GPU extras stay out of an N > 1 line
     # the all-reduced sum is that of `world` independent shards (seeds 1234 + rank): of the magnitude of world x 2^20 rows
     assert r['log_prob_sum'] < 0 and abs(r['log_prob_sum']) > 5e6 * world
+
+
+@pytest.mark.parametrize('world', [1, 2])
+def test_bench_dumps_the_last_steps_result(world, run_child, tmp_path):
+    """`bench.py --dump-outputs DIR`: the fp64 sum the last timed step handed its caller lands in DIR/log_prob_sum.npy (rank 0), and
+    a plain run (no --full) carries the headline only."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', '3', '--warmup', '1',
+           '--dump-outputs', str(tmp_path)]
+    if world > 1:
+        cmd += ['--backend', 'gloo']
+    out = run_child(cmd, env={'HSA_ENABLE_IPC_MODE_LEGACY': '0'},
+                    unset=('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'), timeout=900)
+    assert out['rc'] == 0, out['stderr'][-3000:]
+    lines = [l for l in out['stdout'].splitlines() if l.startswith('{')]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[-1])
+    assert r['steps'] == 3 and r['ms_per_step'] > 0 and r['value'] > 0
+    for key in ('configs', 'training', 'cpu_baseline', 'roofline_elementwise'):
+        assert key not in r, key
+    got = np.load(tmp_path / 'log_prob_sum.npy')
+    assert got.dtype == np.float64 and got.shape == (1,)
+    assert got[0] == r['log_prob_sum']

@@ -348,6 +348,10 @@ def test_bench_spawns_its_own_ranks(monkeypatch):
     assert '--backend' not in cmd                      # nccl (RCCL) is the default and the product path
     bench.spawn_ranks(argparse.Namespace(gpus=2, steps=3, warmup=1, no_cpu_baseline=True, backend='gloo'))
     assert seen['cmd'][seen['cmd'].index('--backend') + 1] == 'gloo'
+    assert '--full' not in seen['cmd'] and '--dump-outputs' not in seen['cmd']
+    bench.spawn_ranks(argparse.Namespace(gpus=2, steps=3, warmup=1, no_cpu_baseline=False, full=True, dump_outputs='out'))
+    assert '--full' in seen['cmd']
+    assert seen['cmd'][seen['cmd'].index('--dump-outputs') + 1] == os.path.abspath('out')
 
 
 @pytest.mark.parametrize('cubic', [False, True])
