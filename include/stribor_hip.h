@@ -621,6 +621,68 @@ int sx_colsum(const float *A, int64_t lda, int64_t n_rows, int32_t M, float *out
  * the triangular solves of stribor/flows/affine.py:159-163, 254-266 against the identity. */
 int sx_tri_inverse_f64(const double *T, double *X, int32_t batch, int32_t D, int32_t lower, int32_t unit, void *stream);
 
+/* ---- invertible ResNet flows (IResNet / ContinuousIResNet, stribor/flows/iresnet.py:9-99) ------------------------------
+ * The residual network g is stribor's MLP (net/mlp.py:6-65) with every Linear after the first wrapped in
+ * torch.nn.utils.spectral_norm (iresnet.py:31-32, 76-77).  A wrapped layer is passed with its UNNORMALISED weight_orig;
+ * its normalisation 1 / sigma comes from a device table filled by sx_spectral_sigma. */
+#define SX_RESNET_MAX_LAYERS 4          /* the first Linear + up to three more (hidden_dims of length <= 3)          */
+#define SX_RESNET_LDS_BYTES (160 * 1024)
+typedef struct {
+    const float *W;        /* [out_dim, in_dim] row-major (weight, or weight_orig of a wrapped layer)                   */
+    const float *b;        /* [out_dim] or NULL                                                                        */
+    int32_t out_dim, in_dim;
+    int32_t sigma_col;     /* column of this layer in the sigma table, -1 = not wrapped                                */
+    int32_t pad_;
+} sx_resnet_layer;
+typedef struct {
+    sx_resnet_layer layer[SX_RESNET_MAX_LAYERS];
+    int32_t n_layers;      /* Linear layers, 1..4; layer 0 reads dim features, the last writes dim                      */
+    int32_t dim;           /* 1..128                                                                                    */
+    int32_t act;           /* SX_ACT_* between layers (mlp.py:38, 50)                                                   */
+    int32_t final_act;     /* SX_ACT_* after the last layer, SX_ACT_IDENTITY for none (mlp.py:55-56)                    */
+    int32_t n_wrapped;     /* columns of the sigma table                                                                */
+    int32_t pad_;
+} sx_resnet_net;
+/* the scale s of y = x + s * g(x) (iresnet.py:39, 81): time embeddings of net/time_net.py, evaluated per row from t[n] */
+#define SX_RESNET_TIME_NONE     -1      /* IResNet: s = 1                                                            */
+#define SX_RESNET_TIME_IDENTITY  0      /* s_d = t                                                                   */
+#define SX_RESNET_TIME_LINEAR    1      /* s_d = a_d t                          (time_a = scale [dim])               */
+#define SX_RESNET_TIME_TANH      2      /* s_d = tanh(a_d t)                                                         */
+#define SX_RESNET_TIME_LOG       3      /* s_d = log(exp(a_d) t + 1)                                                 */
+#define SX_RESNET_TIME_FOURIER   4      /* s_d = sum_q a_dq sin(b_dq t)  (time_a = get_scale(), time_b = shift, [dim, time_hidden]) */
+#define SX_RESNET_TIME_ROWS      5      /* s given as rows: s_rows [n_rows, dim] (any other time net, evaluated by the caller) */
+
+/* Bytes of LDS sx_resnet_flow stages for this network (tiles of 32 padded to 1, 2 or 4); 0 for a malformed one.
+ * Networks above SX_RESNET_LDS_BYTES are refused by sx_resnet_flow. */
+size_t sx_resnet_lds_bytes(const sx_resnet_net *net_host);
+
+/* inverse == 0: out = in + s * g(in)                                  (IResNet.forward, iresnet.py:38-39, 80-81)
+ * inverse != 0: x = in; `iterations` times x = in - s * g(x); out = x   (IResNet.inverse, iresnet.py:41-46, 83-90)
+ * in / out: fp32 [n_rows, dim] (may not alias); t: fp32 [n_rows].  Iteration k uses row k of sigma
+ * [sigma_rows][n_wrapped] (sigma_rows == 1: row 0 for every iteration).  Exact fp32 arithmetic (v_mfma_f32_32x32x2_f32)
+ * in every set_gemm_precision mode.  One launch. */
+int sx_resnet_flow(const sx_resnet_net *net_host, const float *in, float *out, int64_t n_rows, const float *t,
+                   const float *s_rows, int32_t time_kind, const float *time_a, const float *time_b, int32_t time_hidden,
+                   const float *sigma, int32_t sigma_rows, int32_t iterations, int32_t inverse, void *stream);
+
+/* torch.nn.utils.spectral_norm's compute_weight (torch/nn/utils/spectral_norm.py) for the wrapped layers of one network,
+ * over `n_calls` consecutive hook calls: per call n_power rounds of v = normalize(W^T u), u = normalize(W v)
+ * (normalize(a) = a / max(|a|_2, eps)), then sigma[call][l] = u . (W v).  u / v are updated in place (when n_power > 0);
+ * n_power = 0 is eval mode (no update).  One launch, one workgroup per layer; layers up to 128 x 128. */
+typedef struct {
+    const float *W;        /* weight_orig [out_dim, in_dim]                                                            */
+    float *u;              /* weight_u [out_dim]                                                                       */
+    float *v;              /* weight_v [in_dim]                                                                        */
+    int32_t out_dim, in_dim, n_power;
+    float eps;
+} sx_sn_layer;
+typedef struct {
+    sx_sn_layer layer[SX_RESNET_MAX_LAYERS];
+    int32_t n_layers;
+    int32_t pad_;
+} sx_sn_job;
+int sx_spectral_sigma(const sx_sn_job *job_host, int32_t n_calls, float *sigma, void *stream);
+
 /* LDS bytes and grid the launcher will use for a program (introspection for tests/bench). */
 int sx_flow_launch_info(const sx_program *prog_host, int64_t n_rows, int32_t *grid, int32_t *block,
                         int32_t *lds_bytes);

@@ -58,7 +58,13 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_flow_launch_info', 'sx_wgrad', 'sx_wgrad_layer', 'sx_colsum', 'sx_tri_inverse_f64',
            'sx_wgrad_scratch_floats', 'sx_wgrad_layer_scratch_floats', 'sx_flow_bwd_max_steps', 'sx_flow_bwd_partials',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
-           'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden']
+           'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
+           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma']
+
+# invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
+RESNET_MAX_LAYERS = 4
+RESNET_LDS_BYTES = 160 * 1024
+RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
 
 
 class HipLibraryMissing(RuntimeError):
@@ -87,6 +93,25 @@ class sx_program(C.Structure):
     _fields_ = [('n_steps', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('x_tiles', C.c_int32),
                 ('tiles', C.c_int32), ('h_tiles', C.c_int32), ('identity_cols', C.c_int32), ('pad_', C.c_int32),
                 ('steps', sx_step * SX_MAX_STEPS)]
+
+
+class sx_resnet_layer(C.Structure):
+    _fields_ = [('W', C.c_void_p), ('b', C.c_void_p), ('out_dim', C.c_int32), ('in_dim', C.c_int32), ('sigma_col', C.c_int32),
+                ('pad_', C.c_int32)]
+
+
+class sx_resnet_net(C.Structure):
+    _fields_ = [('layer', sx_resnet_layer * 4), ('n_layers', C.c_int32), ('dim', C.c_int32), ('act', C.c_int32),
+                ('final_act', C.c_int32), ('n_wrapped', C.c_int32), ('pad_', C.c_int32)]
+
+
+class sx_sn_layer(C.Structure):
+    _fields_ = [('W', C.c_void_p), ('u', C.c_void_p), ('v', C.c_void_p), ('out_dim', C.c_int32), ('in_dim', C.c_int32),
+                ('n_power', C.c_int32), ('eps', C.c_float)]
+
+
+class sx_sn_job(C.Structure):
+    _fields_ = [('layer', sx_sn_layer * 4), ('n_layers', C.c_int32), ('pad_', C.c_int32)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -188,6 +213,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_flow_bwd_run.argtypes = [C.POINTER(sx_program), vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
     lib.sx_wgrad_reduce.restype = i32
     lib.sx_wgrad_reduce.argtypes = [vp, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]
+    lib.sx_resnet_lds_bytes.restype = C.c_size_t
+    lib.sx_resnet_lds_bytes.argtypes = [C.POINTER(sx_resnet_net)]
+    lib.sx_resnet_flow.restype = i32
+    lib.sx_resnet_flow.argtypes = [C.POINTER(sx_resnet_net), vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp]
+    lib.sx_spectral_sigma.restype = i32
+    lib.sx_spectral_sigma.argtypes = [C.POINTER(sx_sn_job), i32, vp, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

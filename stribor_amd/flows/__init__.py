@@ -4,3 +4,4 @@ from .permute import Flip, Permute
 from .spline import Spline
 from .linear import AffineLU, MatrixExponential
 from .pointwise import ELU, Cumsum, Diff, Identity, LeakyReLU, Logit, Sigmoid
+from .iresnet import ContinuousIResNet, IResNet

@@ -14,6 +14,8 @@ A description is a list of dicts, e.g.
     {"kind": "matrix_exp", "dim": 128, "bias": false, "log_time": false}
     {"kind": "permute", "dim": 64}
     {"kind": "flip"}
+    {"kind": "iresnet", "dim": 2, "hidden": [32, 64], "n_power_iterations": 5}     activation / final_activation optional
+    {"kind": "continuous_iresnet", "dim": 2, "hidden": [32, 32], "time_kind": "tanh"}   (+ "time_hidden" for Fourier)
 """
 from __future__ import annotations
 
@@ -94,11 +96,27 @@ def build_transform(st, d: Dict):
             tn = {'identity': st.net.TimeIdentity, 'linear': st.net.TimeLinear, 'tanh': st.net.TimeTanh,
                   'log': st.net.TimeLog}[d['time_kind']](d.get('time_out', 2 * dim))
         return st.ContinuousAffineCoupling(latent_net=net, time_net=tn, mask=d['mask'], concatenate_time=cat)
+    if k in ('iresnet', 'continuous_iresnet'):
+        dim = d['dim']
+        kw = dict(activation=d.get('activation', 'ReLU'), final_activation=d.get('final_activation'),
+                  n_power_iterations=d.get('n_power_iterations', 5))
+        if k == 'iresnet':
+            return st.IResNet(dim, list(d['hidden']), **kw)
+        tn = _make_time_net(st, d, dim)                   # built first: the reference's test passes it as an argument
+        return st.ContinuousIResNet(dim, list(d['hidden']), time_net=tn, **kw)
     if k in POINTWISE:
         return {'sigmoid': st.Sigmoid, 'logit': st.Logit, 'elu': st.ELU, 'identity': st.Identity,
                 'leaky_relu': lambda: st.LeakyReLU(d.get('negative_slope', 0.01)),
                 'cumsum': lambda: st.Cumsum(-1), 'diff': lambda: st.Diff(-1)}[k]()
     raise ValueError(k)
+
+
+def _make_time_net(st, d: Dict, out: int):
+    if d['time_kind'] in ('fourier', 'fourier_bounded'):
+        cls = st.net.TimeFourier if d['time_kind'] == 'fourier' else st.net.TimeFourierBounded
+        return cls(out, d.get('time_hidden', 8))
+    return {'identity': st.net.TimeIdentity, 'linear': st.net.TimeLinear, 'tanh': st.net.TimeTanh,
+            'log': st.net.TimeLog}[d['time_kind']](out)
 
 
 def build_flow(st, desc: List[Dict], dim: int):
