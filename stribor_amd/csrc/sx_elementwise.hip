@@ -209,34 +209,16 @@ extern "C" int sx_affine_coupling(const void *x, void *y, float *ldj, const floa
                       (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 15) == 0;
     if (fast) {
         const int tl = ilog2(dim / cpt);
-        // Streaming (non-temporal) accesses and, for bf16 storage, two rows in flight per thread: measured on 2^20 x 64
-        // (tools/sweep_affine.py; fraction of 8 TB/s): plain loads 0.64-0.69, nt 0.72-0.73, nt + 2 rows + 32 workgroups
-        // per CU 0.75 (bf16) / 0.70 (fp32).  SX_AFFINE_VARIANT = 10 * rows-in-flight + nt, SX_AFFINE_GRID = workgroups per
-        // CU override the choice (experiments; read once).
-        static const int variant_env = sx_debug_knob("SX_AFFINE_VARIANT", 0);
-        static const int grid_env = sx_debug_knob("SX_AFFINE_GRID", 0);
-        const int variant = variant_env ? variant_env : (dtype == SX_BF16 ? 21 : 11);
-        const int grid_mul = grid_env ? grid_env : (dtype == SX_BF16 ? 32 : 16);
-        const int unr = variant / 10 < 1 ? 1 : variant / 10;
-        const int grid = grid_for((n_rows << tl) / unr + 1, 256, 256 * grid_mul);
-#define SX_AC3(BF, RV, U, N)                                                                  \
-    hipLaunchKernelGGL((affine_coupling_vec_kernel<BF, RV, U, N>), dim3(grid), dim3(256), 0, st, x, y, ldj, \
+        // Streaming (non-temporal) accesses and, for bf16 storage, two rows in flight per thread: measured on 2^20 x 64 (fraction
+        // of 8 TB/s): plain loads 0.64-0.69, nt 0.72-0.73, nt + 2 rows + 32 workgroups per CU 0.75 (bf16) / 0.70 (fp32).
+        const int unr = dtype == SX_BF16 ? 2 : 1;
+        const int grid = grid_for((n_rows << tl) / unr + 1, 256, 256 * (dtype == SX_BF16 ? 32 : 16));
+#define SX_AC(BF, RV, U)                                                                      \
+    hipLaunchKernelGGL((affine_coupling_vec_kernel<BF, RV, U, true>), dim3(grid), dim3(256), 0, st, x, y, ldj, \
                        params, params_stride, live_start, n_live, n_rows, dim, tl, ldj_accumulate, ldj_scale)
-#define SX_AC(BF, RV)                                                                         \
-    do {                                                                                      \
-        switch (variant) {                                                                    \
-            case 11: SX_AC3(BF, RV, 1, true); break;                                          \
-            case 20: SX_AC3(BF, RV, 2, false); break;                                         \
-            case 21: SX_AC3(BF, RV, 2, true); break;                                          \
-            case 40: SX_AC3(BF, RV, 4, false); break;                                         \
-            case 41: SX_AC3(BF, RV, 4, true); break;                                          \
-            default: SX_AC3(BF, RV, 1, false); break;                                         \
-        }                                                                                     \
-    } while (0)
-        if (dtype == SX_BF16) { if (reverse) SX_AC(true, true); else SX_AC(true, false); }
-        else { if (reverse) SX_AC(false, true); else SX_AC(false, false); }
+        if (dtype == SX_BF16) { if (reverse) SX_AC(true, true, 2); else SX_AC(true, false, 2); }
+        else { if (reverse) SX_AC(false, true, 1); else SX_AC(false, false, 1); }
 #undef SX_AC
-#undef SX_AC3
     } else {
         const int grid = grid_for(n_rows * 64, 256);
         const size_t lds = (size_t)dim * sizeof(int);

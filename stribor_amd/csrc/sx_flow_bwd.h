@@ -22,7 +22,6 @@ __device__ __forceinline__ void store_ctile(float *row_base, int off, const f32x
 template <int XT, int HT, int C0, int CT, int T0, int TT>
 __device__ __forceinline__ void coupling_affine_bwd(tile<1> (&xs)[2 * XT], const wptr w, float g, float *side_row,
                                                     int lane, rng_t &rg) {
-    SX_DEP_MARK_BWD;
     constexpr int F1 = 0;                                            // forward pack(W1', HT x CT)
     constexpr int F2 = HT * CT * 1024 + HT * 32;                     // forward pack(W2', 2TT x HT)
     constexpr int F2B = F2 + 2 * TT * HT * 1024;                     //   its bias
@@ -127,7 +126,6 @@ __device__ __forceinline__ void coupling_affine_bwd(tile<1> (&xs)[2 * XT], const
 template <int XT, int HT, int C0, int CT, int T0, int TT>
 __device__ __forceinline__ void coupling_affine_bwd_a(tile<1> (&xs)[2 * XT], const wptr w, float g, float *side_row, int lane,
                                                       rng_t &rg, tile<1> (&keep)[HT + 2 * TT]) {
-    SX_DEP_MARK_BWD;
     constexpr int F1 = 0;                                            // pack(W1', HT x CT)
     constexpr int F2 = HT * CT * 1024 + HT * 32;                     // pack(W2', 2TT x HT)
     constexpr int F2B = F2 + 2 * TT * HT * 1024;                     //   its bias
@@ -137,7 +135,7 @@ __device__ __forceinline__ void coupling_affine_bwd_a(tile<1> (&xs)[2 * XT], con
         for (int c = 0; c < CT; ++c) store_ctile(side_row, 32 * c, xs[C0 + c].v[0], h);
     }
     tile<1> hid[HT];
-#if defined(SX_F16X3) && !defined(SX_BWD_MMAJOR)
+#ifdef SX_F16X3
     // (one wave per SIMD: the A fragments of gemm tile q + 1 are requested before the MFMAs of tile q -- gemm_tile_pf -- through the
     //  hidden layer and the output layer; the sigmoid of hidden tile m - 1 rides between the MFMAs of tile m's first k-chunk)
     constexpr int NHT = HT * CT, NOT_ = 2 * TT * HT;
@@ -187,7 +185,7 @@ __device__ __forceinline__ void coupling_affine_bwd_a(tile<1> (&xs)[2 * XT], con
         tile<1> ls = load_cfrag<1>(w.cb, F2B + (2 * t) * 32), sh = load_cfrag<1>(w.cb, F2B + (2 * t + 1) * 32);
 #pragma unroll
         for (int m = 0; m < HT; ++m) {
-#if defined(SX_F16X3) && !defined(SX_BWD_MMAJOR)
+#ifdef SX_F16X3
             gemm_tile_pf<1, false>(w.wb, cura, off_of(q + 1), bh[m], ls, none); ++q;       // kk*log_scale, kk = -log2 e
             gemm_tile_pf<1, false>(w.wb, cura, off_of(q + 1), bh[m], sh, none); ++q;       // shift
 #else
@@ -214,7 +212,6 @@ __device__ __forceinline__ void coupling_affine_bwd_a(tile<1> (&xs)[2 * XT], con
 template <int XT, int HT, int C0, int CT, int T0, int TT>
 __device__ __forceinline__ void coupling_affine_bwd_b(tile<1> (&xs)[2 * XT], const wptr w, float *side_row, int lane, rng_t &rg,
                                                       tile<1> (&keep)[HT + 2 * TT]) {
-    SX_DEP_MARK_BWD;
     constexpr int B2 = 0;                                            // pack(W2^T, HT x 2TT)
     constexpr int B1 = HT * 2 * TT * 1024 + HT * 32;                 // pack(W1^T, CT x HT)
     const int h = lane >> 5;
@@ -223,7 +220,7 @@ __device__ __forceinline__ void coupling_affine_bwd_b(tile<1> (&xs)[2 * XT], con
     for (int m = 0; m < HT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dh[m].v[0][r] = 0.f;
-#if defined(SX_F16X3) && !defined(SX_BWD_MMAJOR)
+#ifdef SX_F16X3
     constexpr int NDH = 2 * TT * HT, NDZ = CT * HT;
     auto off_of = [](int q) {            // q-th gemm tile: dh per (t, m): the log_scale and the shift adjoint's; then dz per (c, m)
         if (q < NDH) { const int t = q / (2 * HT), m = (q / 2) % HT, which = q & 1; return B2 + (m * 2 * TT + 2 * t + which) * 1024; }
@@ -239,7 +236,7 @@ __device__ __forceinline__ void coupling_affine_bwd_b(tile<1> (&xs)[2 * XT], con
         const btile<1> b0 = make_btile<1>(keep[HT + 2 * t], rg), b1 = make_btile<1>(keep[HT + 2 * t + 1], rg);
 #pragma unroll
         for (int m = 0; m < HT; ++m) {
-#if defined(SX_F16X3) && !defined(SX_BWD_MMAJOR)
+#ifdef SX_F16X3
             gemm_tile_pf<1, false>(w.wb, cura, off_of(q + 1), b0, dh[m], none); ++q;
             gemm_tile_pf<1, false>(w.wb, cura, off_of(q + 1), b1, dh[m], none); ++q;
 #else
@@ -273,7 +270,7 @@ __device__ __forceinline__ void coupling_affine_bwd_b(tile<1> (&xs)[2 * XT], con
         for (int r = 0; r < 16; ++r) dz.v[0][r] = 0.f;
 #pragma unroll
         for (int m = 0; m < HT; ++m) {
-#if defined(SX_F16X3) && !defined(SX_BWD_MMAJOR)
+#ifdef SX_F16X3
             gemm_tile_pf<1, false>(w.wb, cura, off_of(q + 1), bd[m], dz, none); ++q;
 #else
             gemm_tile<1>(w.wb, B1 + (c * HT + m) * 1024, bd[m], dz);
@@ -291,13 +288,12 @@ __device__ __forceinline__ void coupling_affine_bwd_b(tile<1> (&xs)[2 * XT], con
 template <int XT, int T0>
 __device__ __forceinline__ void linear_bwd_half(tile<1> (&xs)[2 * XT], const wptr w, float *side_row, int soff, bool store_before,
                                                 int lane, rng_t &rg) {
-    SX_DEP_MARK_BWD;
     const int h = lane >> 5;
     if (side_row != nullptr && store_before) {
 #pragma unroll
         for (int c = 0; c < XT; ++c) store_ctile(side_row, soff + 32 * c, xs[T0 + c].v[0], h);
     }
-#if defined(SX_F16X3) && !defined(SX_BWD_MMAJOR)
+#ifdef SX_F16X3
     {
         // k-major over XT live accumulators, as the forward layer (sx_flow_kernel.h, SX_STEP_LINEAR_TILE): the fp16 split of source
         // tile c + 1 rides between the MFMAs of k-tile c, the A fragments of the next gemm tile are requested before the MFMAs of the
@@ -424,7 +420,6 @@ struct wacc {                  // one layer's weight-gradient accumulators (prun
 };
 template <int HT>
 __device__ __forceinline__ void wacc_zero(wacc<HT> &a) {
-    SX_DEP_MARK_BWD;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         a.b2[p] = 0.f;
@@ -446,7 +441,6 @@ __device__ __forceinline__ void wacc_zero(wacc<HT> &a) {
 template <int HT, int C0, int T0>
 __device__ __forceinline__ void coupling_affine_bwd_acc(tile<1> (&xs)[4], const wptr w, float g, bool live, wacc<HT> &A,
                                                         const sel_t &sel, rng_t &rg) {
-    SX_DEP_MARK_BWD;
     constexpr int XT = 2, CT = 1, TT = 1;
     constexpr int F1 = 0;
     constexpr int F2 = HT * CT * 1024 + HT * 32;
@@ -490,7 +484,7 @@ __device__ __forceinline__ void coupling_affine_bwd_acc(tile<1> (&xs)[4], const 
     }
     __builtin_amdgcn_sched_barrier(0);
     // 3. dW2 partial: sum_n dp_n r_n^T (turned tiles; the tanh fix-up happens once per workgroup), one hidden tile at a time
-    if (!(SX_X & 512)) {        // (SX_X & 512: timing experiment without the weight-gradient contraction)
+    {
         float dummy = 0.f;
         const tfrag t0 = turn_tile(b0, sel, A.b2[0]), t1 = turn_tile(b1, sel, A.b2[1]);
 #pragma unroll
@@ -531,7 +525,6 @@ __device__ __forceinline__ void coupling_affine_bwd_acc(tile<1> (&xs)[4], const 
 #pragma unroll
         for (int r = 0; r < 16; ++r) xs[XT + C0].v[0][r] += dz.v[0][r];
         float dummy = 0.f;
-        if (SX_X & 512) return;
         const tfrag tz = turn_tile(make_btile<1>(xs[C0]), sel, dummy);      // z again (the tile itself is unchanged)
 #pragma unroll
         for (int m = 0; m < HT; ++m) {

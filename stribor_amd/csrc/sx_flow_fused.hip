@@ -1,12 +1,5 @@
 // Host dispatcher of the fused flow kernel (device code: sx_flow_kernel.h, one object per tile pair).
 #include "sx_flow_types.h"
-#include <stdlib.h>
-
-// experiment knobs, read once per process
-static const bool g_no_pure_mode = sx_debug_knob("SX_NO_PURE_MODE", 0) != 0;
-static const bool g_static_chunks = sx_debug_knob("SX_STATIC_CHUNKS", 0) != 0;
-static const int g_blocks_per_cu = sx_debug_knob("SX_BLOCKS_PER_CU", 0);
-
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -247,7 +240,7 @@ static int validate_and_convert(const sx_program *p, dprog *d, int *buf_floats, 
                    (s.reverse != 0) == (dir != 0);
             any = true;
         }
-        if (pure && any && !g_no_pure_mode) *mlp_mode = (*mlp_mode == 2 ? 7 : 5) + (dir ? 0 : 1);
+        if (pure && any) *mlp_mode = (*mlp_mode == 2 ? 7 : 5) + (dir ? 0 : 1);
     }
     SX_REQUIRE((size_t)mx * 8 <= 160 * 1024, "sx_flow_run: a step needs %d B of LDS per buffer (> 80 KiB)", mx * 4);
     return SX_OK;
@@ -256,7 +249,6 @@ static int validate_and_convert(const sx_program *p, dprog *d, int *buf_floats, 
 static int pick_grid(int64_t n_rows, int lds_bytes, int tiles, int mode) {
     int per_cu = (160 * 1024) / (lds_bytes > 0 ? lds_bytes : 1);
     int max_per_cu = SX_BLOCKS_FOR(tiles, mode);
-    if (g_blocks_per_cu > 0) max_per_cu = g_blocks_per_cu;      // experiment knob
     if (per_cu > max_per_cu) per_cu = max_per_cu;
     if (per_cu < 1) per_cu = 1;
     const int rows_per_block = 32 * SX_BLOCK_WAVES(tiles, mode) * SX_NS_FOR(tiles);
@@ -335,7 +327,7 @@ extern "C" int sx_flow_run2(const sx_program *prog_host, const float *blobs, con
     // dynamic chunk hand-out pays once a workgroup has several chunks; it needs a barrier per chunk (>= 1 step)
     const int rpb = 32 * SX_BLOCK_WAVES(prog_host->tiles, mlp_mode) * SX_NS_FOR(prog_host->tiles);
     const int64_t n_chunks = (n_rows + rpb - 1) / rpb;
-    a.work = (prog_host->n_steps > 0 && n_chunks > 2 * (int64_t)a.grid && !g_static_chunks) ? work : nullptr;
+    a.work = (prog_host->n_steps > 0 && n_chunks > 2 * (int64_t)a.grid) ? work : nullptr;
     a.flags = err_flag;
     a.frag_in = nullptr; a.frag_out = nullptr; a.acc_out = nullptr;
     a.redo = redo; a.redo_pass = 0;
@@ -420,7 +412,7 @@ extern "C" int sx_flow_bwd_run(const sx_program *prog_host, const float *blobs, 
     const int64_t n_chunks = (n_rows + rpb - 1) / rpb;
     // single-step programs hand their chunks out statically: one workgroup per CU, every chunk the same work -- and without
     // the ticket a wave needs no barrier per chunk (measured: the same kernel time either way before that change)
-    a.work = (prog_host->n_steps != 1 && n_chunks > 2 * (int64_t)a.grid && !g_static_chunks) ? work : nullptr;
+    a.work = (prog_host->n_steps != 1 && n_chunks > 2 * (int64_t)a.grid) ? work : nullptr;
     a.flags = err_flag;
     a.frag_in = frag_in; a.frag_out = frag_out; a.acc_out = acc_out;
     if (prog_host->h_tiles == 1) return sx_flow_launch_f16x3_t4h1_f2(a);

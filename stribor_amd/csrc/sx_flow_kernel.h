@@ -44,32 +44,12 @@
 #define SX_PREC_NS sx_f32x
 #endif
 namespace SX_PREC_NS {
-#ifndef SX_WAVES_PER_SIMD
-#define SX_WAVES_PER_SIMD 2
-#endif
 
 __host__ __device__ static inline int sx_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 extern __shared__ __attribute__((aligned(16))) float smem[];
 
 typedef __attribute__((address_space(3))) void lds_void;
-
-// Experiment hooks.  The product build knows none of the timing experiments: SX_X (compile-time ablations), SX_DBG (run-time
-// ablation bits), SX_STAMP (in-kernel phase stamps) and the SX_EXP_* hooks all fold to nothing below.  A build with -DSX_EXPERIMENTS
-// (tools/knob_sweep.sh, tools/experiments/*.sh -- results are then WRONG or stamped, never shipped) pulls their code in from
-// sx_flow_experiments.h.
-#ifdef SX_EXPERIMENTS
-#include "sx_flow_experiments.h"
-#else
-#define SX_X 0
-#define SX_DBG(bit) 0
-struct prof_t {};
-#define SX_STAMP(p, id) ((void)0)
-#define SX_EXP_KERNEL_BEGIN(pf) ((void)0)
-#define SX_EXP_KERNEL_END(pf) ((void)0)
-#define SX_EXP_BEFORE_LAUNCH() ((void)0)
-#define SX_EXP_AFTER_LAUNCH(a) ((void)0)
-#endif
 
 template <int NS>
 struct tile {            // one 32-feature tile of NS x 32 samples, C-fragment order
@@ -94,9 +74,7 @@ struct tile {            // one 32-feature tile of NS x 32 samples, C-fragment o
 // on ~ 7 % of the rows -- +0.23 ms of exact pass per 2^20 rows; at 2048 the BASELINE flows name nothing.)
 // Ordinary (normalised) data never reaches it; data that does is evaluated exactly, at the exact kernel's speed.
 // Without a list (graph-building calls, plain sx_flow_run) the limit stays fp16's own: beyond it NaN + SX_FLAG_F16_RANGE.
-#ifndef SX_REDO_ABOVE
 #define SX_REDO_ABOVE 2048.0f
-#endif
 struct rng_t {
     uint64_t bad;          // lanes that formed an out-of-range operand: wave-uniform, lives in SGPRs (the pure coupling kernel
                            // sits exactly on its 128-VGPR budget: a per-lane running max spilled)
@@ -110,7 +88,7 @@ __device__ __forceinline__ float rng_max(float m, float a, float b) {
     return r;
 }
 __device__ __forceinline__ void rng_note(rng_t &rg, float m) {
-#if defined(SX_F16X3) && !defined(SX_NO_RANGE_TRACK)
+#ifdef SX_F16X3
     rg.bad |= __builtin_amdgcn_ballot_w64(m > rg.thr);              // v_cmp + s_or_b64
 #endif
 }
@@ -177,11 +155,6 @@ __device__ __forceinline__ bool rng_over(float) { return false; }
 
 template <int NS, class F>
 __device__ __forceinline__ void gemm_tile_f(const char *wb, int a_off, const btile<NS> &b, tile<NS> &acc, F &&f) {
-    if (SX_DBG(16)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) f(i);
-        return;
-    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const f32x4 a = *reinterpret_cast<const f32x4 *>(wb + (a_off + g * 256) * 4);   // ds_read_b128, imm offset
@@ -214,15 +187,11 @@ struct btile {            // one 32-deep B operand: 2 k16-steps x (hi, lo) fragm
 // over a sum; nearest leaves 2^-22 |v| without a sign preference.  Same instruction count, same time on cfg 2 / 3 / 4
 // (tools/experiments/cfg4_ab.sh, three interleaved rounds); against the fp64 oracle on 8,192 rows
 // (tools/experiments/split_accuracy.py): cfg 2 log_prob rms 1.9e-7 -> 1.2e-7, mean signed error +1.1e-7 -> +1.7e-8 (the reference's own
-// fp32 sequence: 8.6e-8, +6.8e-9); cfg 4 rms 1.8e-6 -> 8.3e-7, mean +1.6e-6 -> +6e-8 (fp32 sequence: 1.2e-6).  -DSX_SPLIT_RTZ: the old split.)
+// fp32 sequence: 8.6e-8, +6.8e-9); cfg 4 rms 1.8e-6 -> 8.3e-7, mean +1.6e-6 -> +6e-8 (fp32 sequence: 1.2e-6).)
 __device__ __forceinline__ uint32_t pk_f16(float a, float b) {
-#ifndef SX_SPLIT_RTZ
     typedef float f32x2v __attribute__((ext_vector_type(2)));
     typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2v){a, b}, f16x2v));
-#else
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
-#endif
 }
 // lo halfs of a pair: f16(v - hi) straight from the packed hi register: v_fma_mix_f32 reads the fp16 source in
 // place (no v_cvt_f32_f16) and subtracts in fp32 (exact): 4 full-rate VALU instructions per pair for the whole
@@ -248,7 +217,6 @@ __device__ __forceinline__ btile<NS> make_btile_impl(const tile<NS> &c, rng_t *r
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float v0 = c.v[n][8 * s + 2 * q], v1 = c.v[n][8 * s + 2 * q + 1];
-                if (SX_X & 64) { hi[q] = __float_as_uint(v0); lo[q] = __float_as_uint(v1); continue; }
                 if constexpr (TRACK) mx = rng_max(mx, v0, v1);
                 const uint32_t ph = pk_f16(v0, v1);
                 hi[q] = ph;
@@ -290,11 +258,7 @@ __device__ __forceinline__ btile<NS> make_btile_mx(const tile<NS> &c, float &mx)
     return b;
 }
 __device__ __forceinline__ bool rng_over(float mx) {
-#ifndef SX_NO_RANGE_TRACK
     return __builtin_amdgcn_ballot_w64(mx > SX_F16_MAX) != 0ull;
-#else
-    return false;
-#endif
 }
 struct rng_pow2 { float sc, inv; };
 // 2^-e / 2^e with |v| 2^-e < 2^15 for every operand of the sample (its max over BOTH lane halves); e = 0 inside the range
@@ -321,16 +285,10 @@ template <int NS>
 __device__ __forceinline__ btile<NS> make_btile(const tile<NS> &c, rng_t &rg) { return make_btile_impl<NS, true>(c, &rg); }
 template <int NS, class F>
 __device__ __forceinline__ void gemm_tile_f(const char *wb, int a_off, const btile<NS> &b, tile<NS> &acc, F &&f) {
-    if (SX_DBG(16)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) f(i);
-        return;
-    }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        if (SX_X & 16) { f(8 * s + 0); f(8 * s + 1); f(8 * s + 2); f(8 * s + 3); f(8 * s + 4); f(8 * s + 5); f(8 * s + 6); f(8 * s + 7); continue; }
-        const u32x4 ahu = (SX_X & 32) ? u32x4{(uint32_t)a_off, 1u, 2u, 3u} : *reinterpret_cast<const u32x4 *>(wb + (a_off + (2 * s) * 256) * 4);       // ds_read_b128, imm offset
-        const u32x4 alu = (SX_X & 32) ? u32x4{5u, (uint32_t)a_off, 2u, 3u} : *reinterpret_cast<const u32x4 *>(wb + (a_off + (2 * s + 1) * 256) * 4);
+        const u32x4 ahu = *reinterpret_cast<const u32x4 *>(wb + (a_off + (2 * s) * 256) * 4);       // ds_read_b128, imm offset
+        const u32x4 alu = *reinterpret_cast<const u32x4 *>(wb + (a_off + (2 * s + 1) * 256) * 4);
         const h8 ah = __builtin_bit_cast(h8, ahu), al = __builtin_bit_cast(h8, alu);
         // smallest terms first
 #pragma unroll
@@ -393,63 +351,18 @@ __device__ __forceinline__ tile<NS> load_cfrag(const char *cb, int off) {
 
 // r = 1/(exp2(z) + 1): the folded form of tanh (the weights carry its constants, see sx_pack_linear)
 __device__ __forceinline__ float fast_sig2(float v) { return __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(v) + 1.0f); }
-// the same on registers i, i+1 of a C tile (i even; odd i is a no-op so callers can pass gemm_tile_f's unit index):
-// the +1 is one v_pk_add_f32 for the pair
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// fp32 arithmetic on register pairs.  SX_PK: 0 scalar (default: beside MFMAs a v_pk_*_f32 costs more than the two
-// scalar instructions it replaces -- MI355X_MICROARCH.md 'price of one filler beside MFMAs'; measured here
-// 0.423 vs 0.443 ms on cfg 2), 1 vector types (the compiler packs, and its pre-emit peephole un-packs again
-// whatever sits in an MFMA's shadow), 2 v_pk_*_f32 pinned by inline asm (experiments only).
-#ifndef SX_PK
-#define SX_PK 0
-#endif
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-#if SX_PK == 2
-    f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-#elif SX_PK == 1
-    return a + b;
-#else
-    return f32x2{a.x + b.x, a.y + b.y};
-#endif
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-#if SX_PK == 2
-    f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r;
-#elif SX_PK == 1
-    return a - b;
-#else
-    return f32x2{a.x - b.x, a.y - b.y};
-#endif
-}
-__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
-#if SX_PK == 2
-    f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-#elif SX_PK == 1
-    return a * b;
-#else
-    return f32x2{a.x * b.x, a.y * b.y};
-#endif
-}
-__device__ __forceinline__ f32x2 pk_add_one(f32x2 a) {
-#if SX_PK == 2
-    f32x2 r; asm("v_pk_add_f32 %0, %1, 1.0 op_sel_hi:[1,0]" : "=v"(r) : "v"(a)); return r;
-#else
-    return a + 1.0f;
-#endif
-}
+// the same on registers i, i+1 of a C tile (i even; odd i is a no-op so callers can pass gemm_tile_f's unit index)
 __device__ __forceinline__ void fast_sig2_pair(f32x16 &t, int i) {
     if (i & 1) return;
-    if (SX_X & 4) { t[i] *= 0.5f; t[i + 1] *= 0.5f; return; }
-#if SX_PK == 0
     t[i] = fast_sig2(t[i]);
     t[i + 1] = fast_sig2(t[i + 1]);
-#else
-    f32x2 e = {__builtin_amdgcn_exp2f(t[i]), __builtin_amdgcn_exp2f(t[i + 1])};
-    e = pk_add_one(e);
-    t[i] = __builtin_amdgcn_rcpf(e.x);
-    t[i + 1] = __builtin_amdgcn_rcpf(e.y);
-#endif
 }
+// fp32 arithmetic on register pairs, written as scalar operations: beside MFMAs a v_pk_*_f32 costs more than the two scalar
+// instructions it replaces (MI355X_MICROARCH.md 'price of one filler beside MFMAs'; measured here 0.423 vs 0.443 ms on cfg 2)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) { return f32x2{a.x + b.x, a.y + b.y}; }
+__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) { return f32x2{a.x - b.x, a.y - b.y}; }
+__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) { return f32x2{a.x * b.x, a.y * b.y}; }
 
 __device__ __forceinline__ float act_one(float v, int act) {
     switch (act) {
@@ -567,10 +480,9 @@ __device__ __forceinline__ void hidden_layer_keep(const tile<NS> (&src)[NSRC], t
 // FOLDED (the Tanh hot path): no runtime conditionals inside; REV selects (x - sh)*scale vs x*scale + sh.
 template <int NS, int TX, int HT, int C0, int CT, int T0, int TT, bool FOLDED, bool REV>
 __device__ __forceinline__ void coupling_affine(tile<NS> (&xs)[TX], const wptr w, const dstep &st, float (&ldj)[NS],
-                                                prof_t &pf, rng_t &rg) {
+                                                rng_t &rg) {
     tile<NS> hid[HT];
     hidden_layer<NS, TX, HT, C0, CT, FOLDED>(xs, hid, w, 0, st.act, rg);
-    SX_STAMP(pf, 3);     // GEMM-1 (+ pipelined activation)
     constexpr int a2 = HT * CT * 1024 + HT * 32;   // pack_linear(W2: 2*TT m-tiles, HT k-tiles)
     constexpr int b2 = a2 + 2 * TT * HT * 1024;
     f32x2 s[NS];         // log-det partial sums, two lanes of v_pk_add_f32
@@ -619,12 +531,10 @@ __device__ __forceinline__ void coupling_affine(tile<NS> (&xs)[TX], const wptr w
 #pragma unroll
             for (int n = 0; n < NS; ++n) {
                 s[n] = pk_add(s[n], f32x2{ls.v[n][i], ls.v[n][i + 1]});
-                if (SX_X & 8) continue;
                 ls.v[n][i] = __builtin_amdgcn_exp2f(FOLDED ? ls.v[n][i] : ls.v[n][i] * sgn);
                 ls.v[n][i + 1] = __builtin_amdgcn_exp2f(FOLDED ? ls.v[n][i + 1] : ls.v[n][i + 1] * sgn);
             }
         });
-        SX_STAMP(pf, 4);     // GEMM-2 (+ pipelined activation / exp)
         tile<NS> &x = xs[T0 + t];
 #pragma unroll
         for (int n = 0; n < NS; ++n)
@@ -639,7 +549,6 @@ __device__ __forceinline__ void coupling_affine(tile<NS> (&xs)[TX], const wptr w
     }
 #pragma unroll
     for (int n = 0; n < NS; ++n) ldj[n] += st.ldj_scale * (s[n].x + s[n].y);
-    SX_STAMP(pf, 5);         // affine + log-det
 }
 #ifdef SX_F16X3
 // ---- the same step with the A fragments one tile ahead ------------------------------------------------------------------------
@@ -651,10 +560,7 @@ struct afr { u32x4 q[4]; };
 __device__ __forceinline__ afr afr_load(const char *wb, int a_off) {
     afr a;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (SX_X & 32) a.q[i] = u32x4{(uint32_t)a_off, 0x3c003c00u, (uint32_t)i, 0x38003800u};      // timing experiment: no fragment reads
-        else a.q[i] = *reinterpret_cast<const u32x4 *>(wb + (a_off + i * 256) * 4);
-    }
+    for (int i = 0; i < 4; ++i) a.q[i] = *reinterpret_cast<const u32x4 *>(wb + (a_off + i * 256) * 4);
     return a;
 }
 // one tile: request tile `next_off` (< 0: none), then the MFMAs on `cur` with the riders f(0..15) between them, then cur = next
@@ -727,7 +633,7 @@ __device__ __forceinline__ btile<NS> btile_of(const u32x4 (&hi)[NS][2], const u3
 // ([..] = not covered by MFMAs of this wave.)  The output layer runs k-major over four live accumulators.
 template <int NS, int TX, int HT, int C0, int CT, int T0, int TT, bool REV>
 __device__ __forceinline__ void coupling_affine_pf(tile<NS> (&xs)[TX], const wptr w, const dstep &st, float (&ldj)[NS],
-                                                   prof_t &pf, rng_t &rg) {
+                                                   rng_t &rg) {
     static_assert(CT == 2 && HT <= 2, "coupling_affine_pf: two conditioner tiles, hidden <= 64");
     constexpr int a2 = HT * CT * 1024 + HT * 32;   // pack_linear(W2: 2*TT m-tiles, HT k-tiles)
     constexpr int b2 = a2 + 2 * TT * HT * 1024;
@@ -764,7 +670,6 @@ __device__ __forceinline__ void coupling_affine_pf(tile<NS> (&xs)[TX], const wpt
         }
         rng_note(rg, mx);      // a sample's conditioner input beyond fp16's range: named for the exact pass (rng_note)
     }
-    SX_STAMP(pf, 3);     // hidden layer
     btile<NS> bh[HT];
     if constexpr (HT == 1) {
 #pragma unroll
@@ -833,12 +738,10 @@ __device__ __forceinline__ void coupling_affine_pf(tile<NS> (&xs)[TX], const wpt
             if (HT == 2 && k == 0 && r == 2) bh[1] = btile_of<NS>(shi, slo);
         }
     }
-    SX_STAMP(pf, 4);     // output layer (+ exp2, affine map of all tiles but the last)
 #pragma unroll
     for (int i = 0; i < 16; i += 2) affine_rider(xs[T0 + TT - 1], out[2 * TT - 2], out[2 * TT - 1], i);
 #pragma unroll
     for (int n = 0; n < NS; ++n) ldj[n] += st.ldj_scale * (s[n].x + s[n].y);
-    SX_STAMP(pf, 5);         // last tile's affine map + log-det
 }
 #endif
 // Deep conditioners (>= 2 hidden layers, kernel MODE 9): the earlier hidden layers ran as their own steps and left their
@@ -1153,17 +1056,13 @@ __device__ __forceinline__ void coupling_time_dispatch(tile<NS> (&xs)[TX], const
 // one runtime dispatch per step on (activation kind, direction) -> straight-line specialisations
 template <int NS, int TX, int HT, int C0, int CT, int T0, int TT>
 __device__ __forceinline__ void coupling_affine_dispatch(tile<NS> (&xs)[TX], const wptr w, const dstep &st,
-                                                         float (&ldj)[NS], prof_t &pf, rng_t &rg) {
-#ifdef SX_ONLY_HOT     // ISA-inspection build: only the specialisation cfg 2's log_prob executes
-    coupling_affine<NS, TX, HT, C0, CT, T0, TT, true, true>(xs, w, st, ldj, pf, rg);
-    return;
-#endif
+                                                         float (&ldj)[NS], rng_t &rg) {
     if (st.act == SX_ACT_TANH_FOLDED) {
-        if (st.reverse) coupling_affine<NS, TX, HT, C0, CT, T0, TT, true, true>(xs, w, st, ldj, pf, rg);
-        else coupling_affine<NS, TX, HT, C0, CT, T0, TT, true, false>(xs, w, st, ldj, pf, rg);
+        if (st.reverse) coupling_affine<NS, TX, HT, C0, CT, T0, TT, true, true>(xs, w, st, ldj, rg);
+        else coupling_affine<NS, TX, HT, C0, CT, T0, TT, true, false>(xs, w, st, ldj, rg);
     } else {
-        if (st.reverse) coupling_affine<NS, TX, HT, C0, CT, T0, TT, false, true>(xs, w, st, ldj, pf, rg);
-        else coupling_affine<NS, TX, HT, C0, CT, T0, TT, false, false>(xs, w, st, ldj, pf, rg);
+        if (st.reverse) coupling_affine<NS, TX, HT, C0, CT, T0, TT, false, true>(xs, w, st, ldj, rg);
+        else coupling_affine<NS, TX, HT, C0, CT, T0, TT, false, false>(xs, w, st, ldj, rg);
     }
 }
 
@@ -1319,8 +1218,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
     constexpr bool LDS_SUM = MODE == 5 || MODE == 6;
     [[maybe_unused]] double *lds_sum = reinterpret_cast<double *>(smem + 2 * k.buf_floats + 4) + threadIdx.x;
     if constexpr (LDS_SUM) *lds_sum = 0.0;
-    prof_t pf;
-    SX_EXP_KERNEL_BEGIN(pf);
 
     // word 0 of the blob buffer's header: SX_FLAG_* bits raised while the weights were packed (a weight beyond the
     // fp16 x 3 range packs as inf); every launch that uses such weights reports it
@@ -1341,11 +1238,10 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
     // running one workgroup.  Thread 0 takes a ticket for the NEXT chunk in the prologue; it travels to the other
     // waves through LDS across the first step's barrier (two slots, alternating, behind the weight ring).
 #ifdef SX_F16X3
-    [[maybe_unused]] wacc<HT> WA[MODE == 11 ? SX_BWD_SLOTS : 1];
+    [[maybe_unused]] wacc<HT> WA;
     [[maybe_unused]] sel_t sel;
     if constexpr (MODE == 11) {
-        wacc_zero<HT>(WA[0]);
-        wacc_zero<HT>(WA[SX_BWD_SLOTS - 1]);
+        wacc_zero<HT>(WA);
         sel = make_sel(lane);
     }
 #endif
@@ -1520,7 +1416,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
         // (built with the atomic optimizer off: its readfirstlane epilogue would wait right here)
         uint32_t ticket = 0;
         if (dyn && threadIdx.x == 0) ticket = atomicAdd(k.work, 1u);
-        SX_STAMP(pf, 0);     // chunk prologue: x loads issued (not yet waited for)
         float ldj[NS];
 #pragma unroll
         for (int n = 0; n < NS; ++n) ldj[n] = 0.f;
@@ -1562,7 +1457,7 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             // MODE 11 with resident weights and static chunks: after the first chunk a wave needs nothing from the others (weights
             // are read-only, landing zones private): no wait, no barrier -- the waves of a workgroup drift freely
             const bool free_run = MODE == 11 && resident && !dyn && iter > 0;
-            if (!SX_DBG(2) && !free_run && !((SX_X & 128) && s > 0)) {      // (SX_X & 128: timing experiment without the per-step wait + barrier)
+            if (!free_run) {
                 if constexpr (MODE == 4 && TX == 8) {
                     // the weights (LDS-DMA issued one half-step ago) are OLDER than the >= 64 factor stores of that half-step:
                     // a counted wait leaves the stores in flight (vector-memory operations retire in order).  vmcnt cannot count
@@ -1577,7 +1472,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                 if (dyn && s == 0) next_chunk = (int64_t)gridDim.x + __builtin_amdgcn_readfirstlane(slot[iter & 1]);
             }
             const bool has_next_chunk = next_chunk < n_chunks;
-            SX_STAMP(pf, 1);     // wait for weights + barrier
             // (2) refill buffer cur^1 with the next step's weights (the DMA flies under this step's MFMAs)
             //     and fetch the next step's descriptor one step early.
             const dstep st = st_next;
@@ -1586,21 +1480,20 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             // waits for the DMA itself -- the refill then no longer flies under the step's arithmetic
             int wb_off = cur * buf_floats * 4 + lane * 16, cb_off = cur * buf_floats * 4 + (lane >> 5) * 64;
             asm volatile("" : "+v"(wb_off), "+v"(cb_off));
-            // MODE 7 / 8 on four tiles (8-wave workgroups): the refill is the OLDER half's job (SX_M7_DMA_WHO, sx_flow_types.h)
-            constexpr int DMA_WHO = ((MODE == 7 || MODE == 8) && WB == 8) ? SX_M7_DMA_WHO : 0;
-            [[maybe_unused]] const uint32_t dma_off_now = dma_off, dma_floats_now = ((s + 1 < n_steps || has_next_chunk) && !SX_DBG(1)) ? dma_floats : 0u;
-            if constexpr (DMA_WHO == 1) {
-                if (dma_floats_now && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) < WB / 2)
-                    stage_blob<WB / 2>(k.blobs + dma_off_now, (cur ^ 1) * buf_floats, dma_floats_now);
-            } else if constexpr (DMA_WHO == 0)
-            if ((s + 1 < n_steps || has_next_chunk) && dma_floats && !SX_DBG(1) && !resident)
-                stage_blob<WB>(k.blobs + dma_off, (cur ^ 1) * buf_floats, dma_floats);
+            // MODE 7 / 8 on four tiles (8-wave workgroups): the refill is the OLDER half's job, at the END of its step (below) -- the
+            // older half wins the SIMD's issue arbitration, finishes a step at ~65 % of its duration and waits at the next barrier: the
+            // refill then costs the younger half (the critical path) nothing
+            constexpr bool DMA_LATE = (MODE == 7 || MODE == 8) && WB == 8;
+            [[maybe_unused]] const uint32_t dma_off_now = dma_off, dma_floats_now = (s + 1 < n_steps || has_next_chunk) ? dma_floats : 0u;
+            if constexpr (!DMA_LATE)
+                if ((s + 1 < n_steps || has_next_chunk) && dma_floats && !resident)
+                    stage_blob<WB>(k.blobs + dma_off, (cur ^ 1) * buf_floats, dma_floats);
             if constexpr (MODE == 11) {
                 if (resident && s == 0 && k.frag_in != nullptr && has_next_chunk) {
                     const int64_t ngrp = next_chunk * WB + wave;
                     if (ngrp < ((n_rows + 31) >> 5)) {       // wave-uniform
                         // (MUBUF LDS-DMA: see stage_blob -- this prefetch is in flight for the whole chunk)
-                        const int64_t ngrp_s = (SX_X & 256) ? (__builtin_amdgcn_readfirstlane((int)ngrp) & 255) : __builtin_amdgcn_readfirstlane((int)ngrp);      // (SX_X & 256: state traffic folded onto 4 MB -- the launch's time without HBM)
+                        const int64_t ngrp_s = __builtin_amdgcn_readfirstlane((int)ngrp);
                         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(k.frag_in + ngrp_s * (TX * 4 * 64 * 4)), 0, TX * 4 * 1024, 0x00020000);
                         char *ldst = reinterpret_cast<char *>(smem + pf_base + __builtin_amdgcn_readfirstlane(wave) * 4096);
 #pragma unroll
@@ -1635,26 +1528,20 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
 
             const wptr w = wptr{reinterpret_cast<const char *>(smem) + wb_off, reinterpret_cast<const char *>(smem) + cb_off};
             [[maybe_unused]] float st_cur_const = st.ldj_const;      // (a spline triple moves on to its next steps inside the iteration)
-            SX_STAMP(pf, 2);     // descriptor + DMA issue
             if constexpr (MODE == 5 || MODE == 6) {
                 // pure split-coupling programs (host: validate_and_convert): two straight-line arms, state in place
                 if constexpr (TX >= 2) {
-                    if (st.c0 == 0) coupling_affine<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, true, MODE == 5>(xs, w, st, ldj, pf, rg);
-                    else coupling_affine<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, true, MODE == 5>(xs, w, st, ldj, pf, rg);
+                    if (st.c0 == 0) coupling_affine<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, true, MODE == 5>(xs, w, st, ldj, rg);
+                    else coupling_affine<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, true, MODE == 5>(xs, w, st, ldj, rg);
                 }
             } else if constexpr (MODE == 11) {
 #ifdef SX_F16X3
                 if constexpr (TX == 4 && NS == 1 && HT <= 2) {
                     const float gg = gg11;
                     const bool live = row[0] < n_rows;
-                    // static accumulator slots (the host keeps a MODE 11 program to SX_BWD_SLOTS steps)
-                    if (SX_BWD_SLOTS == 1 || s == 0) {
-                        if (st.c0 == 0) coupling_affine_bwd_acc<HT, 0, 1>(xs, w, gg, live, WA[0], sel, rg);
-                        else coupling_affine_bwd_acc<HT, 1, 0>(xs, w, gg, live, WA[0], sel, rg);
-                    } else {
-                        if (st.c0 == 0) coupling_affine_bwd_acc<HT, 0, 1>(xs, w, gg, live, WA[SX_BWD_SLOTS - 1], sel, rg);
-                        else coupling_affine_bwd_acc<HT, 1, 0>(xs, w, gg, live, WA[SX_BWD_SLOTS - 1], sel, rg);
-                    }
+                    // one accumulator set: the host keeps a MODE 11 program to one step
+                    if (st.c0 == 0) coupling_affine_bwd_acc<HT, 0, 1>(xs, w, gg, live, WA, sel, rg);
+                    else coupling_affine_bwd_acc<HT, 1, 0>(xs, w, gg, live, WA, sel, rg);
                 }
 #endif
             } else if ((MODE == 7 || MODE == 8) && st.kind == SX_STEP_COUPLING_AFFINE) {
@@ -1662,12 +1549,12 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                 if constexpr (TX >= 2 && (MODE == 7 || MODE == 8)) {
 #ifdef SX_F16X3
                     if constexpr (TX == 4 && HT <= 2) {        // two waves per SIMD: A fragments one tile ahead, vector work between the MFMAs
-                        if (st.c0 == 0) coupling_affine_pf<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, MODE == 7>(xs, w, st, ldj, pf, rg);
-                        else coupling_affine_pf<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, MODE == 7>(xs, w, st, ldj, pf, rg);
+                        if (st.c0 == 0) coupling_affine_pf<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, MODE == 7>(xs, w, st, ldj, rg);
+                        else coupling_affine_pf<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, MODE == 7>(xs, w, st, ldj, rg);
                     } else
 #endif
-                    if (st.c0 == 0) coupling_affine<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, true, MODE == 7>(xs, w, st, ldj, pf, rg);
-                    else coupling_affine<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, true, MODE == 7>(xs, w, st, ldj, pf, rg);
+                    if (st.c0 == 0) coupling_affine<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, true, MODE == 7>(xs, w, st, ldj, rg);
+                    else coupling_affine<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, true, MODE == 7>(xs, w, st, ldj, rg);
                 }
             } else if constexpr (MODE == 15) {
                 // programs of time-conditioned affine couplings (ContinuousAffineCoupling / NeuralFlow)
@@ -1748,15 +1635,15 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                     if constexpr (RQ || MODE == 7 || MODE == 8 || TX == 8) break;   // pure spline programs carry no affine couplings (register budget; mixed: MODE 14); 7 / 8: handled above; 8 tiles: chunk steps only
                     if constexpr (TX >= 2) {
                         if (st.ct == TX / 2 && st.c0 == 0 && st.t0 == TX / 2) {          // cond = low tiles
-                            coupling_affine_dispatch<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2>(xs, w, st, ldj, pf, rg);
+                            coupling_affine_dispatch<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2>(xs, w, st, ldj, rg);
                             break;
                         }
                         if (st.ct == TX / 2 && st.c0 == TX / 2 && st.t0 == 0) {          // cond = high tiles
-                            coupling_affine_dispatch<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2>(xs, w, st, ldj, pf, rg);
+                            coupling_affine_dispatch<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2>(xs, w, st, ldj, rg);
                             break;
                         }
                     }
-                    coupling_affine_dispatch<NS, TX, HT, 0, TX, 0, TX>(xs, w, st, ldj, pf, rg);       // dense
+                    coupling_affine_dispatch<NS, TX, HT, 0, TX, 0, TX>(xs, w, st, ldj, rg);       // dense
                     break;
                 case SX_STEP_AFFINE_CONST:
                     if constexpr (MODE != 7 && MODE != 8) affine_const<NS, TX>(xs, w, st, x_tiles, ldj);
@@ -1859,11 +1746,10 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                     if constexpr (MODE == 20 && TX == 8 && NS == 1) {
                         if (st.c0 == 0) wide_hidden<TX, HT, 0>(xs, bhp, w, rg);
                         else wide_hidden<TX, HT, TX / 2>(xs, bhp, w, rg);
-                        SX_STAMP(pf, 3);
                     }
                     break;
                 case SX_STEP_WIDE_AFFINE_TILE:
-                    if constexpr (MODE == 20 && TX == 8 && NS == 1) { wide_affine_tile<TX, HT>(xs, bhp, w, st, ldj[0]); SX_STAMP(pf, 4); }
+                    if constexpr (MODE == 20 && TX == 8 && NS == 1) wide_affine_tile<TX, HT>(xs, bhp, w, st, ldj[0]);
                     break;
                 case SX_STEP_COUPLING_AFFINE_HC:
                     if constexpr (MODE == 20 && TX >= 2 && TX <= 4) {
@@ -1951,7 +1837,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                             float mx = 0.f;
                             btile<NS> bcur = make_btile_mx<NS>(xs[0], mx);
                             __builtin_amdgcn_sched_barrier(0);
-                            SX_STAMP(pf, 5);
                             u32x4 nhi[NS][2], nlo[NS][2];
                             constexpr int PPM = 8 / TX;            // split pairs of the next source tile per gemm tile (TX = 4: two)
 #pragma unroll
@@ -1981,7 +1866,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
 #pragma unroll
                         for (int c = 0; c < TX; ++c) bx[c] = make_btile_mx<NS>(xs[c], mx);
                         __builtin_amdgcn_sched_barrier(0);
-                        SX_STAMP(pf, 5);
                         rng_note(rg, mx);      // a sample's state beyond fp16's range: rng_note
 #pragma unroll
                         for (int m = 0; m < TX; ++m) {
@@ -2089,14 +1973,12 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                     else if constexpr (RQ && NS == 1) {
                         // the group's three blocks in this one iteration (the host plans them back to back, the launcher checks it)
                         auto advance = [&](dstep &stn, wptr &wn) {
-                            SX_STAMP(pf, 6);
                             ldj_c += st_cur_const;
                             cur ^= 1;
                             ++s;
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                             __builtin_amdgcn_s_barrier();
-                            SX_STAMP(pf, 1);     // wait for weights + barrier
                             stn = st_next;
                             st_cur_const = stn.ldj_const;
                             int wb2 = cur * buf_floats * 4 + lane * 16, cb2 = cur * buf_floats * 4 + (lane >> 5) * 64;
@@ -2107,10 +1989,9 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                             dma_off = prog.steps[nb2].blob_off;
                             dma_floats = prog.steps[nb2].blob_floats;
                             wn = wptr{reinterpret_cast<const char *>(smem) + wb2, reinterpret_cast<const char *>(smem) + cb2};
-                            SX_STAMP(pf, 2);     // descriptor + DMA issue
                         };
                         if constexpr (CUB) cubic_triple<TX, HT>(xs, rq_bh, w, st, ldj[0], lane, advance);
-                        else rqs_triple<TX, HT>(xs, rq_bh, w, st, ldj[0], lane, advance, pf);
+                        else rqs_triple<TX, HT>(xs, rq_bh, w, st, ldj[0], lane, advance);
                     }
                     break;
                 case SX_STEP_ROW_SCALE_EXP:
@@ -2140,13 +2021,12 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                 default: break;
             }
             if (st.kind != SX_STEP_ROW_SCALE_EXP && st.kind != SX_STEP_POINTWISE) ldj_c += st_cur_const;      // (those two keep a parameter there)
-            if constexpr (DMA_WHO == 2) {
+            if constexpr (DMA_LATE) {
                 // (buffer cur ^ 1 has been free since this step's barrier; the pieces land while the younger half finishes the step)
                 if (dma_floats_now && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) < WB / 2)
                     stage_blob<WB / 2>(k.blobs + dma_off_now, (cur ^ 1) * buf_floats, dma_floats_now);
             }
             if (!resident) cur ^= 1;
-            SX_STAMP(pf, 6);     // step tail
         }
         if constexpr (MODE == 11) {
             // E: the next chunk's state (LDS-DMA) and dL/dlog_prob were requested a whole step ago: waiting for them HERE, in
@@ -2156,7 +2036,7 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
         }
 
         // ---- epilogue: outputs -----------------------------------------------------------------------------
-#if defined(SX_F16X3) && !defined(SX_NO_POISON)
+#ifdef SX_F16X3
         if constexpr (MODE != 1) {
             // a sample whose GEMM operands left the fp16 x 3 range (|v| > 65504) comes back as NaN, never as a
             // plausible number, and SX_FLAG_F16_RANGE is raised (the two lane halves hold one sample)
@@ -2173,12 +2053,10 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
 #pragma unroll
                     for (int n = 0; n < NS; ++n) {
                         ldj[n] = __builtin_nanf("");
-#ifndef SX_NO_POISON_Y
 #pragma unroll
                         for (int t = 0; t < TX; ++t)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) xs[t].v[n][r] = __builtin_nanf("");
-#endif
                     }
                     if (k.flags != nullptr) __hip_atomic_fetch_or(k.flags, SX_FLAG_F16_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
@@ -2190,7 +2068,7 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
 #endif
         if constexpr (MODE == 11) {
             if (k.frag_out != nullptr && chunk * WB + wave < ((n_rows + 31) >> 5)) {
-                f32x4 *fo = reinterpret_cast<f32x4 *>(k.frag_out) + ((SX_X & 256) ? ((chunk * WB + wave) & 255) : (chunk * WB + wave)) * (TX * 4 * 64) + lane;
+                f32x4 *fo = reinterpret_cast<f32x4 *>(k.frag_out) + (chunk * WB + wave) * (TX * 4 * 64) + lane;
 #pragma unroll
                 for (int t = 0; t < TX; ++t)
 #pragma unroll
@@ -2254,7 +2132,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                 }
             }
         }
-        SX_STAMP(pf, 7);         // chunk epilogue
         chunk = next_chunk;
     }
     if (dyn && threadIdx.x == 0) {     // the last workgroup out re-arms the counters for the next launch on this stream
@@ -2274,52 +2151,48 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                    // nobody reads the weight ring any more
         float *red = smem;
+        if (n_steps > 0) {
+            const wacc<HT> &A = WA;
+            for (int wv = 0; wv < WB; ++wv) {
+                if (wave == wv) {
 #pragma unroll
-        for (int slot = 0; slot < SX_BWD_SLOTS; ++slot) {
-            if (slot < n_steps) {
-                const wacc<HT> &A = WA[slot];
-                for (int wv = 0; wv < WB; ++wv) {
-                    if (wave == wv) {
+                    for (int p = 0; p < 2; ++p) {
 #pragma unroll
-                        for (int p = 0; p < 2; ++p) {
-#pragma unroll
-                            for (int m = 0; m < HT; ++m)
-#pragma unroll
-                                for (int r = 0; r < 16; ++r) {
-                                    const int e = (32 * p + (r & 3) + 8 * (r >> 2) + 4 * kk) * N2 + 32 * m + i;
-                                    red[e] = (wv == 0 ? 0.f : red[e]) + A.c2[p][m][r];
-                                }
-                            const float tb = A.b2[p] + __shfl_xor(A.b2[p], 32, 64);
-                            if (kk == 0) { const int e = 64 * N2 + 32 * p + i; red[e] = (wv == 0 ? 0.f : red[e]) + tb; }
-                        }
-#pragma unroll
-                        for (int m = 0; m < HT; ++m) {
+                        for (int m = 0; m < HT; ++m)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
-                                const int e = E2 + (32 * m + (r & 3) + 8 * (r >> 2) + 4 * kk) * 32 + i;
-                                red[e] = (wv == 0 ? 0.f : red[e]) + A.c1[m][r];
+                                const int e = (32 * p + (r & 3) + 8 * (r >> 2) + 4 * kk) * N2 + 32 * m + i;
+                                red[e] = (wv == 0 ? 0.f : red[e]) + A.c2[p][m][r];
                             }
-                            const float tb = A.b1[m] + __shfl_xor(A.b1[m], 32, 64);
-                            if (kk == 0) { const int e = E2 + 32 * HT * 32 + 32 * m + i; red[e] = (wv == 0 ? 0.f : red[e]) + tb; }
-                        }
+                        const float tb = A.b2[p] + __shfl_xor(A.b2[p], 32, 64);
+                        if (kk == 0) { const int e = 64 * N2 + 32 * p + i; red[e] = (wv == 0 ? 0.f : red[e]) + tb; }
                     }
-                    __syncthreads();
-                }
-                // per step: [gridDim.x][E2] then [gridDim.x][E1] (two inputs of wgrad_reduce_kernel)
-                float *dst2 = k.acc_out + (int64_t)slot * gridDim.x * (E2 + E1) + (int64_t)blockIdx.x * E2;
-                float *dst1 = k.acc_out + (int64_t)slot * gridDim.x * (E2 + E1) + (int64_t)gridDim.x * E2 + (int64_t)blockIdx.x * E1;
-                for (int e = threadIdx.x; e < E2 + E1; e += 64 * WB) {
-                    float v = red[e];
-                    if (e < 64 * N2) v = red[64 * N2 + e / N2] - 2.f * v;          // tanh = 1 - 2 r
-                    if (e < E2) dst2[e] = v; else dst1[e - E2] = v;
+#pragma unroll
+                    for (int m = 0; m < HT; ++m) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int e = E2 + (32 * m + (r & 3) + 8 * (r >> 2) + 4 * kk) * 32 + i;
+                            red[e] = (wv == 0 ? 0.f : red[e]) + A.c1[m][r];
+                        }
+                        const float tb = A.b1[m] + __shfl_xor(A.b1[m], 32, 64);
+                        if (kk == 0) { const int e = E2 + 32 * HT * 32 + 32 * m + i; red[e] = (wv == 0 ? 0.f : red[e]) + tb; }
+                    }
                 }
                 __syncthreads();
             }
+            // [gridDim.x][E2] then [gridDim.x][E1] (two inputs of wgrad_reduce_kernel)
+            float *dst2 = k.acc_out + (int64_t)blockIdx.x * E2;
+            float *dst1 = k.acc_out + (int64_t)gridDim.x * E2 + (int64_t)blockIdx.x * E1;
+            for (int e = threadIdx.x; e < E2 + E1; e += 64 * WB) {
+                float v = red[e];
+                if (e < 64 * N2) v = red[64 * N2 + e / N2] - 2.f * v;          // tanh = 1 - 2 r
+                if (e < E2) dst2[e] = v; else dst1[e - E2] = v;
+            }
+            __syncthreads();
         }
     }
 #endif
 
-    SX_EXP_KERNEL_END(pf);
     if (k.sum_out != nullptr) {
         double *part = reinterpret_cast<double *>(smem);   // no second __shared__ object beside the DMA ring
         if constexpr (LDS_SUM) block_sum = *lds_sum;
@@ -2346,7 +2219,6 @@ constexpr bool in_family(int f) { return SX_FAMILY < 0 || SX_FAMILY == f; }
 
 template <int TX, int HT>
 static int sx_flow_launch_impl(const sx_flow_args &a) {
-    SX_EXP_BEFORE_LAUNCH();
     constexpr int NS = SX_NS_FOR(TX);
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -2410,7 +2282,6 @@ static int sx_flow_launch_impl(const sx_flow_args &a) {
 #endif
 #undef SX_FL
     SX_LAUNCH_CHECK();
-    SX_EXP_AFTER_LAUNCH(a);
     return SX_OK;
 }
 

@@ -20,16 +20,8 @@
 // The bin index of an element is the same value in its select and its evaluate block, and both compare it with every bin number: the
 // optimizer shares those compares -- up to 2 x 31 lane masks kept alive across the step advance between the blocks, i.e. spilled to
 // lanes and read back two v_readlane per select.  Each block takes the index through an empty asm instead and compares again.
-#ifndef SX_NO_SWEEP_FENCE
 #define SX_OPAQUE(v) asm volatile("" : "+v"(v))
-#else
-#define SX_OPAQUE(v) ((void)0)
-#endif
-#ifndef SX_NO_SWEEP_FENCE
 #define SX_SWEEP_FENCE(a, b, c) do { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define SX_SWEEP_FENCE(a, b, c) ((void)0)
-#endif
 struct rqs_elems {          // the 4 elements of the current group a lane owns
     float x[4];             // input values
     float a_b[4], a_w[4];   // searched sequence: knot at the bin, bin size
@@ -77,73 +69,8 @@ __device__ __forceinline__ float rqs_softmax(tile<1> (&acc)[4], int K) {
     return (1.f - RQS_MIN * Kf) * fast_rcp(sum);         // :101-105
 }
 
-// phase 0: knots of the searched block (:180-192) and the bin search (search_sorted.py:4-5) in one sweep.
-// The knots increase and `x >= knot_j` is true for a prefix of j, so
-//   knot at the bin  = last knot with x >= knot  (running select),
-//   next knot        = min over the knots with x < knot (min with `hi` where x >= knot).
-// K = 16: the sixteen-step sweep as a two-level search -- which group of four bins (three compares against the knots at
-// bins 4, 8, 12, formed from the groups' sums), then the bin inside the group (its four sizes picked by the group index): ~70
-// VALU instructions per element instead of ~130 for the same knot values up to the order of the additions.
-#ifndef SX_RQS_FLAT
-template <int Q>
-__device__ __forceinline__ void rqs_search16(tile<1> (&acc)[4], rqs_elems &e, float lo, float hi) {
-    const float xv = e.x[Q];
-    const bool in = (xv >= lo) && (xv <= hi);                       // :71 closed interval
-    const float xin = in ? xv : lo;
-    const float inv = rqs_softmax<Q, 16>(acc, 16);
-    const float span = hi - lo;
-    // cumulative sizes at the group boundaries: cs_4, cs_8, cs_12 (:180-192)
-    const float S0 = 4.f * RQS_MIN + inv * ((RQS_P(acc, Q, 0) + RQS_P(acc, Q, 1)) + (RQS_P(acc, Q, 2) + RQS_P(acc, Q, 3)));
-    const float S1 = 4.f * RQS_MIN + inv * ((RQS_P(acc, Q, 4) + RQS_P(acc, Q, 5)) + (RQS_P(acc, Q, 6) + RQS_P(acc, Q, 7)));
-    const float S2 = 4.f * RQS_MIN + inv * ((RQS_P(acc, Q, 8) + RQS_P(acc, Q, 9)) + (RQS_P(acc, Q, 10) + RQS_P(acc, Q, 11)));
-    const float C1 = S0, C2 = S0 + S1, C3 = (S0 + S1) + S2;
-    const bool m1 = xin >= span * C1 + lo, m2 = xin >= span * C2 + lo, m3 = xin >= span * C3 + lo;       // a prefix: knots grow
-    const float base = m3 ? C3 : (m2 ? C2 : (m1 ? C1 : 0.f));
-    const int gb = m3 ? 12 : (m2 ? 8 : (m1 ? 4 : 0));
-    auto pick = [&](int i) {
-        return m3 ? RQS_P(acc, Q, 12 + i) : (m2 ? RQS_P(acc, Q, 8 + i) : (m1 ? RQS_P(acc, Q, 4 + i) : RQS_P(acc, Q, i)));
-    };
-    const float cs1 = base + (RQS_MIN + pick(0) * inv), cs2 = cs1 + (RQS_MIN + pick(1) * inv);
-    const float cs3 = cs2 + (RQS_MIN + pick(2) * inv), cs4 = cs3 + (RQS_MIN + pick(3) * inv);
-    const float k0 = m1 ? span * base + lo : lo;                    // ends pinned
-    const float k1 = span * cs1 + lo, k2 = span * cs2 + lo, k3 = span * cs3 + lo;
-    const float k4 = m3 ? hi : span * cs4 + lo;
-    const bool g1 = xin >= k1, g2 = xin >= k2, g3 = xin >= k3;
-    e.b[Q] = gb + (g3 ? 3 : (g2 ? 2 : (g1 ? 1 : 0))) + (in ? 0 : RQS_OUT);
-    const float k_b = g3 ? k3 : (g2 ? k2 : (g1 ? k1 : k0));
-    const float k_n = g3 ? k4 : (g2 ? k3 : (g1 ? k2 : k1));
-    e.a_b[Q] = k_b;
-    e.a_w[Q] = k_n - k_b;
-}
-// the other block at the found bin: the two knots around bin b from the group sums + the group's own sizes
-template <int Q>
-__device__ __forceinline__ void rqs_select16(tile<1> (&acc)[4], rqs_elems &e, float lo, float hi) {
-    const float inv = rqs_softmax<Q, 16>(acc, 16);
-    const float span = hi - lo;
-    const int b = e.b[Q] & (RQS_OUT - 1);
-    const float S0 = 4.f * RQS_MIN + inv * ((RQS_P(acc, Q, 0) + RQS_P(acc, Q, 1)) + (RQS_P(acc, Q, 2) + RQS_P(acc, Q, 3)));
-    const float S1 = 4.f * RQS_MIN + inv * ((RQS_P(acc, Q, 4) + RQS_P(acc, Q, 5)) + (RQS_P(acc, Q, 6) + RQS_P(acc, Q, 7)));
-    const float S2 = 4.f * RQS_MIN + inv * ((RQS_P(acc, Q, 8) + RQS_P(acc, Q, 9)) + (RQS_P(acc, Q, 10) + RQS_P(acc, Q, 11)));
-    const bool m1 = b >= 4, m2 = b >= 8, m3 = b >= 12;
-    const float base = m3 ? (S0 + S1) + S2 : (m2 ? S0 + S1 : (m1 ? S0 : 0.f));
-    auto pick = [&](int i) {
-        return m3 ? RQS_P(acc, Q, 12 + i) : (m2 ? RQS_P(acc, Q, 8 + i) : (m1 ? RQS_P(acc, Q, 4 + i) : RQS_P(acc, Q, i)));
-    };
-    const float cs1 = base + (RQS_MIN + pick(0) * inv), cs2 = cs1 + (RQS_MIN + pick(1) * inv);
-    const float cs3 = cs2 + (RQS_MIN + pick(2) * inv), cs4 = cs3 + (RQS_MIN + pick(3) * inv);
-    const int bl = b & 3;
-    const float k0 = m1 ? span * base + lo : lo;
-    const float k1 = span * cs1 + lo, k2 = span * cs2 + lo, k3 = span * cs3 + lo;
-    const float k4 = m3 ? hi : span * cs4 + lo;
-    const bool g1 = bl >= 1, g2 = bl >= 2, g3 = bl >= 3;
-    const float k_b = g3 ? k3 : (g2 ? k2 : (g1 ? k1 : k0));
-    const float k_n = g3 ? k4 : (g2 ? k3 : (g1 ? k2 : k1));
-    e.c_b[Q] = k_b;
-    e.c_w[Q] = k_n - k_b;
-}
-#endif
 // ------------------------------------------------------------------------------------------------
-// K = 16, BOUNDED logits (round 4): the lean form of the three phases above.  What changed and why (profiles/sq_cfg3.json: 256 of
+// K = 16, BOUNDED logits (round 4): the lean form of the K-generic phases below (rqs_search, rqs_select, rqs_eval).  What changed and why (profiles/sq_cfg3.json: 256 of
 // the 545 vector instructions per element were selects, compares and moves; 256 VGPRs + 68 B of scratch):
 //   * no running maximum.  The softmax is shift-invariant and the shift only guards exp against overflow; the packer leaves a bound
 //     on |logit| of the step's rows behind the spline bounds (sx_pack_linear_bound: |b' + the positive (negative) packed weights| --
@@ -157,7 +84,7 @@ __device__ __forceinline__ void rqs_select16(tile<1> (&acc)[4], rqs_elems &e, fl
 //     the front end -- the old code ran s_and_saveexec / s_cbranch_execz diamonds inside the element code --, and `c ? a : b` on
 //     two lvalues selects the ADDRESS, which pins the operands to scratch);
 //   * an element's 16 parameters are ONE output tile (RQS_P), so element q's arithmetic runs beside the MFMAs of tile q + 1
-//     (rqs16_block): the matrix pipe and the VALU overlap inside the wave instead of only across the two waves of a SIMD.
+//     (rqs16_group): the matrix pipe and the VALU overlap inside the wave instead of only across the two waves of a SIMD.
 // Arithmetic: the same knots up to the order of the additions (the reference: cumsum of MIN + (1 - K MIN) softmax, times the span,
 // plus the lower bound, ends pinned -- rational_quadratic_spline.py:180-192).
 // ------------------------------------------------------------------------------------------------
@@ -350,11 +277,12 @@ __device__ __forceinline__ void rqs16_select(const f32x16 &u, rqs_elems &e, cons
     e.c_w[Q] = k_n - k_b;
     hk.template pt<11>(e.c_b[Q], e.c_w[Q]);
 }
+// phase 0: knots of the searched block (:180-192) and the bin search (search_sorted.py:4-5) in one sweep.
+// The knots increase and `x >= knot_j` is true for a prefix of j, so
+//   knot at the bin  = last knot with x >= knot  (running select),
+//   next knot        = min over the knots with x < knot (min with `hi` where x >= knot).
 template <int Q, int KC, int W = 1>
 __device__ __forceinline__ void rqs_search(tile<1> (&acc)[4], rqs_elems &e, int K, float lo, float hi) {
-#ifndef SX_RQS_FLAT
-    if constexpr (KC == 16 && W == 1) { rqs_search16<Q>(acc, e, lo, hi); return; }
-#endif
     const float xv = e.x[Q];
     const bool in = (xv >= lo) && (xv <= hi);                       // :71 closed interval
     const float xin = in ? xv : lo;
@@ -384,9 +312,6 @@ __device__ __forceinline__ void rqs_search(tile<1> (&acc)[4], rqs_elems &e, int 
 // phase 1: knots of the other block at the found bin
 template <int Q, int KC, int W = 1>
 __device__ __forceinline__ void rqs_select(tile<1> (&acc)[4], rqs_elems &e, int K, float lo, float hi) {
-#ifndef SX_RQS_FLAT
-    if constexpr (KC == 16 && W == 1) { rqs_select16<Q>(acc, e, lo, hi); return; }
-#endif
     const float inv = rqs_softmax<Q, KC, W>(acc, K);
     const int Kn = KC ? KC : K;
     int b = e.b[Q] & (RQS_OUT - 1);
@@ -482,9 +407,8 @@ __device__ __forceinline__ void rqs_eval(const f32x16 &u, const rqs_elems &e, in
     float r_b = cst, r_n = cst;
     // derivative k sits between bins k and k+1: it is the RIGHT knot's of bin k and the LEFT knot's of bin k+1, so one
     // compare per bin index serves both selections
-#ifndef SX_RQS_FLAT
     if constexpr (KC == 16) {
-        // two-level pick (see rqs_search16): D[-1] = D[15] = cst, r_b = D[b - 1], r_n = D[b]; the five candidates D[4g-1 .. 4g+3]
+        // two-level pick (as in rqs16_search): D[-1] = D[15] = cst, r_b = D[b - 1], r_n = D[b]; the five candidates D[4g-1 .. 4g+3]
         // of the bin's group first, then the pair inside it.  (Scalars and macros on purpose: the same code with a float[5] and
         // a lambda became a stack object -- scratch in the phase loop, cfg 3 6.4 -> 27.6 ms.)
         const bool m1 = b >= 4, m2 = b >= 8, m3 = b >= 12;
@@ -504,7 +428,6 @@ __device__ __forceinline__ void rqs_eval(const f32x16 &u, const rqs_elems &e, in
         r_n = g3 ? v4 : (g2 ? v3 : (g1 ? v2 : v1));
         hk.template pt<3>(r_b, r_n);
     } else
-#endif
     {
     bool is_prev = (b == 0);             // "bin index == k" carried to the next iteration as "bin index - 1 == k - 1"
 #pragma unroll
@@ -563,7 +486,6 @@ __device__ __forceinline__ void rqs_phase_k(tile<1> (&acc)[4], tile<1> (&xs)[TX]
 #pragma unroll
                     for (int q = 0; q < 4; ++q) e.x[q] = xs[t].v[0][4 * gg + q];
                 }
-#if !defined(SX_RQS_FLAT) && !defined(SX_RQS_OLD16)
         if constexpr (KC == 16) {
             const rqs16_c c = rqs16_consts(lo, hi);
             rqs_nohook nh16;
@@ -572,7 +494,6 @@ __device__ __forceinline__ void rqs_phase_k(tile<1> (&acc)[4], tile<1> (&xs)[TX]
             rqs16_search<2, false>(acc[2].v[0], e, c, nh16); __builtin_amdgcn_sched_barrier(0);
             rqs16_search<3, false>(acc[3].v[0], e, c, nh16);
         } else
-#endif
         {
         rqs_search<0, KC>(acc, e, K, lo, hi);
         rqs_search<1, KC>(acc, e, K, lo, hi);
@@ -580,7 +501,6 @@ __device__ __forceinline__ void rqs_phase_k(tile<1> (&acc)[4], tile<1> (&xs)[TX]
         rqs_search<3, KC>(acc, e, K, lo, hi);
         }
     } else if (st.ct == 1) {
-#if !defined(SX_RQS_FLAT) && !defined(SX_RQS_OLD16)
         if constexpr (KC == 16) {
             const rqs16_c c = rqs16_consts(lo, hi);
             rqs_nohook nh16;
@@ -589,7 +509,6 @@ __device__ __forceinline__ void rqs_phase_k(tile<1> (&acc)[4], tile<1> (&xs)[TX]
             rqs16_select<2, false>(acc[2].v[0], e, c, nh16); __builtin_amdgcn_sched_barrier(0);
             rqs16_select<3, false>(acc[3].v[0], e, c, nh16);
         } else
-#endif
         {
         rqs_select<0, KC>(acc, e, K, lo, hi);
         rqs_select<1, KC>(acc, e, K, lo, hi);
@@ -631,7 +550,6 @@ __device__ __forceinline__ void rqs_phase_k(tile<1> (&acc)[4], tile<1> (&xs)[TX]
 template <int TX, int HT>
 __device__ __forceinline__ void rqs_phase(tile<1> (&xs)[TX], const btile<1> (&bh)[HT], rqs_elems &e, const wptr w,
                                           const dstep &st, float &ldj, int lane, bool &group_lean) {
-    SX_DEP_MARK_SPLINE;
     const int h = lane >> 5;
     tile<1> acc[4];
     rqs_gemm<HT>(w, bh, acc);
@@ -912,23 +830,6 @@ __device__ __forceinline__ void rqs32_group(const wptr w0, const btile<1> (&bh)[
     }
     live_mask = st.mask; ldj_scale = st.ldj_scale;
 }
-template <int HT, int PH, bool REV>
-__device__ __forceinline__ void rqs16_block(const wptr w, const btile<1> (&bh)[HT], rqs_elems &e, const rqs16_c &c, float (&out)[4],
-                                            float (&lj)[4], prof_t &pf) {
-    tile<1> A, B;
-    {   // tile 0: nothing to run beside it yet
-        A = load_cfrag<1>(w.cb, 4 * HT * 1024);
-#pragma unroll
-        for (int m = 0; m < HT; ++m) gemm_tile<1>(w.wb, m * 1024, bh[m], A);
-    }
-    SX_STAMP(pf, 3);     // a block's first tile (not overlapped)
-    { rqs_tile_pipe<HT, 1> p(w, bh, B); p.start(); rqs16_unit<PH, REV, 0>(A.v[0], e, c, out, lj, p); }
-    { rqs_tile_pipe<HT, 2> p(w, bh, A); p.start(); rqs16_unit<PH, REV, 1>(B.v[0], e, c, out, lj, p); }
-    { rqs_tile_pipe<HT, 3> p(w, bh, B); p.start(); rqs16_unit<PH, REV, 2>(A.v[0], e, c, out, lj, p); }
-    SX_STAMP(pf, 4);     // three (tile GEMM, element) pairs
-    { rqs_pinhook nh; rqs16_unit<PH, REV, 3>(B.v[0], e, c, out, lj, nh); }
-    SX_STAMP(pf, 5);     // the last element (no MFMAs beside it)
-}
 // elements 0 .. 2 of a block beside its tiles 1 .. 3 (tile 0 is in A on entry, tile 3 in B on exit)
 template <int HT, int PH, bool REV, bool GEN>
 __device__ __forceinline__ void rqs16_mid(const wptr w, const btile<1> (&bh)[HT], rqs_elems &e, const rqs16_c &c, float (&out)[4],
@@ -971,8 +872,7 @@ __device__ __forceinline__ void rqs16_group(const wptr w0, const btile<1> (&bh)[
 }
 template <int TX, int HT, class ADV>
 __device__ __forceinline__ void rqs_triple(tile<1> (&xs)[TX], const btile<1> (&bh)[HT], const wptr w0, const dstep &st0, float &ldj,
-                                           int lane, ADV &&advance, prof_t &pf) {
-    SX_DEP_MARK_SPLINE;
+                                           int lane, ADV &&advance) {
     const int h = lane >> 5;
     const int K = st0.tt, tg = 4 * st0.t0 + st0.c0;
     rqs_elems e;
@@ -983,22 +883,8 @@ __device__ __forceinline__ void rqs_triple(tile<1> (&xs)[TX], const btile<1> (&b
     RQS_GROUP_CASES(RQS_FETCH)
     rqs_block_scalars<HT>(w0, h, lo, hi, lean);     // (the bound in the first block's blob covers both softmax blocks of the group)
     if (K <= 16 && lean) {
-#ifndef SX_RQS_NO_CHAIN
         if (K == 16) rqs16_group<HT, false>(w0, bh, e, K, lo, hi, h, advance, out, lj, live_mask, ldj_scale);
         else rqs16_group<HT, true>(w0, bh, e, K, lo, hi, h, advance, out, lj, live_mask, ldj_scale);
-#else
-        wptr w;
-        dstep st;
-        rqs16_block<HT, 0, false>(w0, bh, e, rqs16_consts(lo, hi), out, lj, pf);
-        advance(st, w);
-        rqs_block_scalars<HT>(w, h, lo, hi, lean);
-        const rqs16_c c1 = rqs16_consts(lo, hi);
-        rqs16_block<HT, 1, false>(w, bh, e, c1, out, lj, pf);
-        advance(st, w);
-        if (st.reverse) rqs16_block<HT, 2, true>(w, bh, e, c1, out, lj, pf);
-        else rqs16_block<HT, 2, false>(w, bh, e, c1, out, lj, pf);
-        live_mask = st.mask; ldj_scale = st.ldj_scale;
-#endif
     } else if (K > 16) {
         // 17 .. 32 bins (round 4: the one-launch tier used to stop at 16 and such layers ran conditioner program + element-wise kernel
         // through HBM, 8x slower): an element's parameters are TWO output tiles, so a step carries two of the lane's four elements
@@ -1123,8 +1009,7 @@ __device__ __forceinline__ float cub_softmax(tile<1> (&acc)[4], int K) {
     return (1.f - CUBIC_MIN_BIN * Kf) * cubic_frcp(sum);         // :103-104, :110-111
 }
 __device__ __forceinline__ float cub_norm(float xv, bool in, float lo, float hi) { return ((in ? xv : lo) - lo) * cubic_frcp(hi - lo); }   // :98-101
-#ifndef SX_CUB_FLAT
-// K = 16: two-level forms of the two sweeps below (see rqs_search16): the group of four bins from the groups' sums, then the six
+// K = 16: two-level forms of the two sweeps below (as in rqs16_search): the group of four bins from the groups' sums, then the six
 // sizes around it (bins 4g-1 .. 4g+4) picked by the group index, the bin and its neighbours inside them
 #define CUB_CL(k) ((k) < 0 ? 0 : ((k) > 15 ? 15 : (k)))        /* (the out-of-range neighbours are never used) */
 #define CUB_Z(i) (CUBIC_MIN_BIN + inv * (m3 ? RQS_P(acc, Q, CUB_CL(11 + (i))) : (m2 ? RQS_P(acc, Q, CUB_CL(7 + (i))) : \
@@ -1166,13 +1051,10 @@ __device__ __forceinline__ void cub_select16(tile<1> (&acc)[4], cubic_elems &e) 
     e.o_b[Q] = g3 ? z4 : (g2 ? z3 : (g1 ? z2 : z1));
     e.o_p[Q] = g3 ? z5 : (g2 ? z4 : (g1 ? z3 : z2));
 }
-#endif
 // phase 0: sizes + running knots of the searched block and the bin search (search_sorted.py:4-5) in one sweep
 template <int Q, int KC>
 __device__ __forceinline__ void cub_search(tile<1> (&acc)[4], cubic_elems &e, int K, float lo, float hi) {
-#ifndef SX_CUB_FLAT
     if constexpr (KC == 16) { cub_search16<Q>(acc, e, lo, hi); return; }
-#endif
     const float xv = e.x[Q];
     const bool in = (xv >= lo) && (xv <= hi);                       // :40 closed interval
     const float xn = cub_norm(xv, in, lo, hi);
@@ -1199,9 +1081,7 @@ __device__ __forceinline__ void cub_search(tile<1> (&acc)[4], cubic_elems &e, in
 // phase 1: the other block at the found bin
 template <int Q, int KC>
 __device__ __forceinline__ void cub_select(tile<1> (&acc)[4], cubic_elems &e, int K) {
-#ifndef SX_CUB_FLAT
     if constexpr (KC == 16) { cub_select16<Q>(acc, e); return; }
-#endif
     const float inv = cub_softmax<Q, KC>(acc, K);
     const int b = e.b[Q] & (RQS_OUT - 1);
     float k_b = 0.f, o_b = 0.f, o_m = 1.f, o_p = 1.f, cum = 0.f;
@@ -1385,21 +1265,6 @@ __device__ __forceinline__ void cub16_unit(const f32x16 &u, cubic_elems &e, cons
     else if constexpr (PH == 1) cub16_select<Q>(u, e, cc, hk);
     else cub_eval<Q, REV>(u, e, GEN ? cc.K : 16, lo, hi, out[Q], lj[Q], hk);
 }
-template <int HT, int PH, bool REV>
-__device__ __forceinline__ void cub16_block(const wptr w, const btile<1> (&bh)[HT], cubic_elems &e, float lo, float hi, float (&out)[4],
-                                            float (&lj)[4]) {
-    const cub16_c cc = cub16_consts();
-    tile<1> A, B;
-    {
-        A = load_cfrag<1>(w.cb, 4 * HT * 1024);
-#pragma unroll
-        for (int m = 0; m < HT; ++m) gemm_tile<1>(w.wb, m * 1024, bh[m], A);
-    }
-    { rqs_tile_pipe<HT, 1> p(w, bh, B); p.start(); cub16_unit<PH, REV, 0, false>(A.v[0], e, cc, lo, hi, out, lj, p); }
-    { rqs_tile_pipe<HT, 2> p(w, bh, A); p.start(); cub16_unit<PH, REV, 1, false>(B.v[0], e, cc, lo, hi, out, lj, p); }
-    { rqs_tile_pipe<HT, 3> p(w, bh, B); p.start(); cub16_unit<PH, REV, 2, false>(A.v[0], e, cc, lo, hi, out, lj, p); }
-    { rqs_pinhook nh; cub16_unit<PH, REV, 3, false>(B.v[0], e, cc, lo, hi, out, lj, nh); }
-}
 template <int HT, int PH, bool REV, bool GEN>
 __device__ __forceinline__ void cub16_mid(const wptr w, const btile<1> (&bh)[HT], cubic_elems &e, const cub16_c &cc, float lo, float hi,
                                           float (&out)[4], float (&lj)[4], tile<1> &A, tile<1> &B) {
@@ -1441,7 +1306,6 @@ __device__ __forceinline__ void cub16_group(const wptr w0, const btile<1> (&bh)[
 template <int TX, int HT, class ADV>
 __device__ __forceinline__ void cubic_triple(tile<1> (&xs)[TX], const btile<1> (&bh)[HT], const wptr w0, const dstep &st0, float &ldj,
                                              int lane, ADV &&advance) {
-    SX_DEP_MARK_SPLINE;
     const int h = lane >> 5;
     const int K = st0.tt, tg = 4 * st0.t0 + st0.c0;
     cubic_elems e;
@@ -1452,21 +1316,8 @@ __device__ __forceinline__ void cubic_triple(tile<1> (&xs)[TX], const btile<1> (
     RQS_GROUP_CASES(CUB_FETCH)
     rqs_block_scalars<HT>(w0, h, lo, hi, lean);
     if (K <= 16 && lean) {
-#ifndef SX_RQS_NO_CHAIN
         if (K == 16) cub16_group<HT, false>(w0, bh, e, K, lo, hi, h, advance, out, lj, live_mask, ldj_scale);
         else cub16_group<HT, true>(w0, bh, e, K, lo, hi, h, advance, out, lj, live_mask, ldj_scale);
-#else
-        wptr w;
-        dstep st;
-        cub16_block<HT, 0, false>(w0, bh, e, lo, hi, out, lj);
-        advance(st, w);
-        cub16_block<HT, 1, false>(w, bh, e, lo, hi, out, lj);
-        advance(st, w);
-        rqs_block_scalars<HT>(w, h, lo, hi, lean);
-        if (st.reverse) cub16_block<HT, 2, true>(w, bh, e, lo, hi, out, lj);
-        else cub16_block<HT, 2, false>(w, bh, e, lo, hi, out, lj);
-        live_mask = st.mask; ldj_scale = st.ldj_scale;
-#endif
     } else {
 #define CUB_PIN4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); __builtin_amdgcn_sched_barrier(0)
         wptr w;
@@ -1565,7 +1416,6 @@ __device__ __forceinline__ void cubic_phase_k(tile<1> (&acc)[4], tile<1> (&xs)[T
 template <int TX, int HT>
 __device__ __forceinline__ void cubic_phase(tile<1> (&xs)[TX], const btile<1> (&bh)[HT], cubic_elems &e, const wptr w,
                                             const dstep &st, float &ldj, int lane) {
-    SX_DEP_MARK_SPLINE;
     const int h = lane >> 5;
     tile<1> acc[4];
     rqs_gemm<HT>(w, bh, acc);

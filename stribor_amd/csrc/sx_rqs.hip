@@ -26,9 +26,7 @@ extern __shared__ __attribute__((aligned(16))) float rqs_smem[];
 typedef __attribute__((address_space(3))) void rqs_lds_void;
 // cache policy of the parameter stream's LDS-DMA (aux bits of global_load_lds: 0 default, 2 = nt): the [N, n_live (3K-1)] tensor is read
 // exactly once (MI355X_MICROARCH.md, nt-weights: once-read streams land 18 % sooner under nt) -- measured in DESIGN 6
-#ifndef SX_RQS_DMA_AUX
 #define SX_RQS_DMA_AUX 2
-#endif
 template <int BYTES>
 __device__ __forceinline__ void rqs_dma_span(const float *__restrict__ g, float *lds_slice, int lane) {
     const char *gs = reinterpret_cast<const char *>(g) + lane * 16;

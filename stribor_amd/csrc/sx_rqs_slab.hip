@@ -30,21 +30,8 @@
 #include "sx_rqs_bwd.h"
 #include "sx_cubic_core.h"
 
-// Timing experiments only (results wrong): -DSX_SLAB_X=<bits>  1 no spline reverse mode  2 no dh  4 no dW2  8 no parameter GEMM
-#ifndef SX_SLAB_X
-#define SX_SLAB_X 0
-#endif
-
 namespace {
 using namespace sx_f16x3;
-
-// Phase timing (build with -DSX_SLAB_PROF; prints from sx_rqs_slab_bwd): s_memtime deltas of one wave, per phase
-#ifdef SX_SLAB_PROF
-__device__ unsigned long long g_slab_prof[16];
-#define SLAB_T(id) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pf[id] += t_ - pt; pt = t_; } while (0)
-#else
-#define SLAB_T(id) ((void)0)
-#endif
 
 struct slab_args {
     const float *x, *gout, *gldj, *h;   // x, gout [N, dim]; gldj [N]; h [N, ld_h] (H valid features)
@@ -169,9 +156,6 @@ __global__ __launch_bounds__(256 * SPW, (SPW == 1 && HT <= 2 && HTF == HT) ? 2 :
     const float sc_in = slab_scale_in(k.scale), sc_out = slab_scale_out(k.scale);
     const int c_begin = (int)((int64_t)k.n_chunks * range / k.n_ranges), c_end = (int)((int64_t)k.n_chunks * (range + 1) / k.n_ranges);
     const int iters = (c_end - c_begin + 3) >> 2;                      // passes: uniform over the workgroup
-#ifdef SX_SLAB_PROF
-    unsigned long long pf[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt = __builtin_amdgcn_s_memtime();
-#endif
     for (int it = 0; it < iters; ++it) {
         const int c = c_begin + q + 4 * it;
         const bool chunk_ok = c < c_end;
@@ -213,7 +197,6 @@ __global__ __launch_bounds__(256 * SPW, (SPW == 1 && HT <= 2 && HTF == HT) ? 2 :
                 }
                 bh[m] = make_btile<1>(hid, rg);
             }
-            SLAB_T(0);      // h load + split
             const float xl = xb_[xoff], gol = gb_[xoff], gll = lb_[jc];
             if constexpr (CUBIC) xo = (k.xout + row0 * k.dim)[xoff];
             xv = valid ? xl : k.bottom;
@@ -223,23 +206,21 @@ __global__ __launch_bounds__(256 * SPW, (SPW == 1 && HT <= 2 && HTF == HT) ? 2 :
             // round-robin -- an MFMA onto the previous one's result waits for it, and the A fragments come from LDS
     #pragma unroll
             for (int t = 0; t < 3; ++t) acc[t] = load_cfrag<1>(w.cb, bias_off + t * 32);
-            if (!(SX_SLAB_X & 8)) {
-    #pragma unroll
-                for (int m = 0; m < HT; ++m)
-    #pragma unroll
-                    for (int sx = 0; sx < 2; ++sx) {
-                        afrag a[3];
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) a[t] = load_afrag(w.wb, FWo + (t * HT + m) * 1024, sx);
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].lo, bh[m].hi[0][sx], acc[t].v[0]);      // smallest terms first
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bh[m].lo[0][sx], acc[t].v[0]);
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bh[m].hi[0][sx], acc[t].v[0]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-            }
+#pragma unroll
+            for (int m = 0; m < HT; ++m)
+#pragma unroll
+                for (int sx = 0; sx < 2; ++sx) {
+                    afrag a[3];
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) a[t] = load_afrag(w.wb, FWo + (t * HT + m) * 1024, sx);
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].lo, bh[m].hi[0][sx], acc[t].v[0]);      // smallest terms first
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bh[m].lo[0][sx], acc[t].v[0]);
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bh[m].hi[0][sx], acc[t].v[0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
         } else {
             const float xl = xb_[xoff], gol = gb_[xoff], gll = lb_[jc];
             if constexpr (CUBIC) xo = (k.xout + row0 * k.dim)[xoff];
@@ -270,135 +251,115 @@ __global__ __launch_bounds__(256 * SPW, (SPW == 1 && HT <= 2 && HTF == HT) ? 2 :
                 }
                 const btile<1> bcur = make_btile<1>(hid, rg);
                 if (mf >= M0 && mf < M0 + HT) bh[(mf >= M0 && mf < M0 + HT) ? mf - M0 : 0] = bcur;      // (mf is a constant once unrolled)
-                if (!(SX_SLAB_X & 8)) {
-    #pragma unroll
-                    for (int sx = 0; sx < 2; ++sx) {
-                        afrag a[3];
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) a[t] = load_afrag(w.wb, FWo + (t * HTF + mf) * 1024, sx);
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].lo, bcur.hi[0][sx], acc[t].v[0]);      // smallest terms first
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bcur.lo[0][sx], acc[t].v[0]);
-    #pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bcur.hi[0][sx], acc[t].v[0]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+#pragma unroll
+                for (int sx = 0; sx < 2; ++sx) {
+                    afrag a[3];
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) a[t] = load_afrag(w.wb, FWo + (t * HTF + mf) * 1024, sx);
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].lo, bcur.hi[0][sx], acc[t].v[0]);      // smallest terms first
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bcur.lo[0][sx], acc[t].v[0]);
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) acc[t].v[0] = mfma(a[t].hi, bcur.hi[0][sx], acc[t].v[0]);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            SLAB_T(0);      // h load + split + parameter GEMM
         }
-        SLAB_T(1);      // x / adjoint loads + parameter GEMM issue
         // ---- the spline's reverse mode on the lane's own element: parameters -> their gradients, in place ---------------
         float gxe;
         if constexpr (CUBIC)
             gxe = cubic_inverse_bwd_regs<KC>(acc[0].v[0], acc[1].v[0], acc[2].v[0], k.K, xv, xo, Ao, Al, k.left, k.right, valid);
         else
-            gxe = (SX_SLAB_X & 1) ? xv + Ao + Al
-                                  : rqs_inverse_bwd_regs<KC>(acc[0].v[0], acc[1].v[0], acc[2].v[0], k.K, xv, Ao, Al, k.left, k.right,
-                                                             k.bottom, k.top, valid);
-        SLAB_T(2);      // spline reverse mode (waits for the GEMM)
+            gxe = rqs_inverse_bwd_regs<KC>(acc[0].v[0], acc[1].v[0], acc[2].v[0], k.K, xv, Ao, Al, k.left, k.right, k.bottom, k.top, valid);
         btile<1> bd[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) bd[t] = make_btile<1>(acc[t], rg);
         if (valid) (k.gx + row0 * k.dim)[xoff] = rng_bad_sample(rg, lane) ? __builtin_nanf("") : gxe * sc_out;
         any_bad |= rg.bad;
         __builtin_amdgcn_sched_barrier(0);
-        SLAB_T(3);      // dp split + gx store
         // ---- dh partial = W2_slab^T dp ---------------------------------------------------------------------------
-        if (!(SX_SLAB_X & 2)) {
-            float *dst = k.dh_part + ((size_t)group * k.n_chunks + cc) * (HTF * 1024) + M0 * 1024;
-            tile<1> dh[HT];
+        float *dst = k.dh_part + ((size_t)group * k.n_chunks + cc) * (HTF * 1024) + M0 * 1024;
+        tile<1> dh[HT];
 #pragma unroll
-            for (int m = 0; m < HT; ++m)
+        for (int m = 0; m < HT; ++m)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dh[m].v[0][r] = 0.f;
+            for (int r = 0; r < 16; ++r) dh[m].v[0][r] = 0.f;
 #pragma unroll
-            for (int t = 0; t < 3; ++t)
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
-                for (int sx = 0; sx < 2; ++sx) {              // the HT chains round-robin, as in the parameter GEMM
-                    afrag a[HT];
+            for (int sx = 0; sx < 2; ++sx) {              // the HT chains round-robin, as in the parameter GEMM
+                afrag a[HT];
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) a[m] = load_afrag(w.wb, BWo + (m * 3 + t) * 1024, sx);
+                for (int m = 0; m < HT; ++m) a[m] = load_afrag(w.wb, BWo + (m * 3 + t) * 1024, sx);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) dh[m].v[0] = mfma(a[m].lo, bd[t].hi[0][sx], dh[m].v[0]);
+                for (int m = 0; m < HT; ++m) dh[m].v[0] = mfma(a[m].lo, bd[t].hi[0][sx], dh[m].v[0]);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) dh[m].v[0] = mfma(a[m].hi, bd[t].lo[0][sx], dh[m].v[0]);
+                for (int m = 0; m < HT; ++m) dh[m].v[0] = mfma(a[m].hi, bd[t].lo[0][sx], dh[m].v[0]);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) dh[m].v[0] = mfma(a[m].hi, bd[t].hi[0][sx], dh[m].v[0]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            if constexpr (SPW == 1) {
-                if (chunk_ok) {
+                for (int m = 0; m < HT; ++m) dh[m].v[0] = mfma(a[m].hi, bd[t].hi[0][sx], dh[m].v[0]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        if constexpr (SPW == 1) {
+            if (chunk_ok) {
 #pragma unroll
-                    for (int m = 0; m < HT; ++m)
+                for (int m = 0; m < HT; ++m)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 v = {dh[m].v[0][4 * g], dh[m].v[0][4 * g + 1], dh[m].v[0][4 * g + 2], dh[m].v[0][4 * g + 3]};
+                        reinterpret_cast<f32x4 *>(dst + m * 1024)[g * 64 + lane] = v;
+                    }
+            }
+        } else {
+            // the pair (slab 2g, slab 2g+1) of a chunk: wave `sl` hands the tile it does NOT own to its partner and owns
+            // hidden tile (sl % HT): with HT = 2 each wave adds and stores one tile, with HT = 1 the first slab's wave does
+            constexpr int OWN_SPLIT = HT == 2;
+            const int own = sl * 4 + q, oth = (1 - sl) * 4 + q;
+            f32x4 *xb = reinterpret_cast<f32x4 *>(smem + XB + own * 1024);
+            f32x4 *xp = reinterpret_cast<f32x4 *>(smem + XB + oth * 1024);
+            int *ready = reinterpret_cast<int *>(smem + FL), *ack = ready + 8;
+            const int give = OWN_SPLIT ? 1 - sl : 0;            // tile handed over (HT = 1: slab 1 gives its only tile)
+            if (OWN_SPLIT || sl == 1) {
+                flag_wait_ge(ack + own, it);                    // the partner has read the tile of the previous pass
+#pragma unroll
+                for (int m = 0; m < HT; ++m)
+                    if (m == give) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+                            xb[g * 64 + lane] = f32x4{dh[m].v[0][4 * g], dh[m].v[0][4 * g + 1], dh[m].v[0][4 * g + 2], dh[m].v[0][4 * g + 3]};
+                    }
+                flag_set(ready + own, it + 1);
+            }
+            if (OWN_SPLIT || sl == 0) {
+                flag_wait_ge(ready + oth, it + 1);
+#pragma unroll
+                for (int m = 0; m < HT; ++m)
+                    if (m == (OWN_SPLIT ? sl : 0)) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            const f32x4 v = {dh[m].v[0][4 * g], dh[m].v[0][4 * g + 1], dh[m].v[0][4 * g + 2], dh[m].v[0][4 * g + 3]};
-                            reinterpret_cast<f32x4 *>(dst + m * 1024)[g * 64 + lane] = v;
+                            const f32x4 o = xp[g * 64 + lane];
+                            const f32x4 v = {dh[m].v[0][4 * g] + o.x, dh[m].v[0][4 * g + 1] + o.y, dh[m].v[0][4 * g + 2] + o.z,
+                                             dh[m].v[0][4 * g + 3] + o.w};
+                            if (chunk_ok) reinterpret_cast<f32x4 *>(dst + m * 1024)[g * 64 + lane] = v;
                         }
-                }
-            } else {
-                // the pair (slab 2g, slab 2g+1) of a chunk: wave `sl` hands the tile it does NOT own to its partner and owns
-                // hidden tile (sl % HT): with HT = 2 each wave adds and stores one tile, with HT = 1 the first slab's wave does
-                constexpr int OWN_SPLIT = HT == 2;
-                const int own = sl * 4 + q, oth = (1 - sl) * 4 + q;
-                f32x4 *xb = reinterpret_cast<f32x4 *>(smem + XB + own * 1024);
-                f32x4 *xp = reinterpret_cast<f32x4 *>(smem + XB + oth * 1024);
-                int *ready = reinterpret_cast<int *>(smem + FL), *ack = ready + 8;
-                const int give = OWN_SPLIT ? 1 - sl : 0;            // tile handed over (HT = 1: slab 1 gives its only tile)
-                if (OWN_SPLIT || sl == 1) {
-                    flag_wait_ge(ack + own, it);                    // the partner has read the tile of the previous pass
-#pragma unroll
-                    for (int m = 0; m < HT; ++m)
-                        if (m == give) {
-#pragma unroll
-                            for (int g = 0; g < 4; ++g)
-                                xb[g * 64 + lane] = f32x4{dh[m].v[0][4 * g], dh[m].v[0][4 * g + 1], dh[m].v[0][4 * g + 2], dh[m].v[0][4 * g + 3]};
-                        }
-                    flag_set(ready + own, it + 1);
-                }
-                if (OWN_SPLIT || sl == 0) {
-                    flag_wait_ge(ready + oth, it + 1);
-#pragma unroll
-                    for (int m = 0; m < HT; ++m)
-                        if (m == (OWN_SPLIT ? sl : 0)) {
-#pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                const f32x4 o = xp[g * 64 + lane];
-                                const f32x4 v = {dh[m].v[0][4 * g] + o.x, dh[m].v[0][4 * g + 1] + o.y, dh[m].v[0][4 * g + 2] + o.z,
-                                                 dh[m].v[0][4 * g + 3] + o.w};
-                                if (chunk_ok) reinterpret_cast<f32x4 *>(dst + m * 1024)[g * 64 + lane] = v;
-                            }
-                        }
-                    flag_set(ack + oth, it + 1);
-                }
+                    }
+                flag_set(ack + oth, it + 1);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        SLAB_T(4);      // dh GEMM + exchange + store
         // ---- dW2_slab += dp^T h (contraction over this wave's 32 rows on the matrix pipe) --------------------------------
-        if (!(SX_SLAB_X & 4)) {
-            tfrag th[HT];
-            float dummy = 0.f;
+        tfrag th[HT];
+        float dummy = 0.f;
 #pragma unroll
-            for (int m = 0; m < HT; ++m) th[m] = turn_tile(bh[m], sel, dummy);
+        for (int m = 0; m < HT; ++m) th[m] = turn_tile(bh[m], sel, dummy);
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                const tfrag td = turn_tile(bd[t], sel, bsum[t]);
+        for (int t = 0; t < 3; ++t) {
+            const tfrag td = turn_tile(bd[t], sel, bsum[t]);
 #pragma unroll
-                for (int m = 0; m < HT; ++m) contract(td, th[m], A[t][m]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            for (int m = 0; m < HT; ++m) contract(td, th[m], A[t][m]);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        SLAB_T(5);      // turns + contraction
     }
-#ifdef SX_SLAB_PROF
-    if (blockIdx.x == 9 && wave == 1 && lane == 0) {
-        for (int i = 0; i < 6; ++i) g_slab_prof[i] = pf[i];
-        g_slab_prof[6] = (unsigned long long)iters;
-    }
-#endif
     if (any_bad != 0 && lane == 0 && k.flags != nullptr)
         __hip_atomic_fetch_or(k.flags, SX_FLAG_F16_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     // ---- one partial per slab and workgroup: its 4 waves add their tiles in LDS by turns (row-major [96][32 HT] | [96]) ----
@@ -1436,8 +1397,7 @@ __global__ __launch_bounds__(256) void rqs_slab_ldj_reduce_kernel(const float *_
 struct slab_shape { int spw, n_groups, n_ranges; };
 slab_shape slab_plan(int n_slabs, int n_chunks, int ht = 2) {
     slab_shape p;
-    static const int knob = sx_debug_knob("SX_SLAB_SPW", 0);      // experiments: 1 | 2, read once
-    p.spw = (knob == 1 || ht > 2) ? 1 : (n_slabs >= 2 ? 2 : 1);
+    p.spw = (ht > 2) ? 1 : (n_slabs >= 2 ? 2 : 1);
     p.n_groups = (n_slabs + p.spw - 1) / p.spw;
     int r = ((p.spw == 2 || ht > 2 ? 256 : 512) + p.n_groups - 1) / p.n_groups;      // workgroups per CU: 1 (8 waves, or HT > 2) | 2
     const int cap = (n_chunks + 3) / 4;              // at least one 32-row chunk per wave where the rows allow
@@ -1487,8 +1447,7 @@ extern "C" int sx_rqs_slab_bwd(const float *x, const float *gout, const float *g
     k.w_part = scratch + (size_t)n_groups * n_chunks * HT * 1024;
     k.live_idx = live_idx; k.scale = scale; k.flags = err_flag; k.n_rows = n_rows; k.ld_h = ld_h; k.l0 = live_start; k.n_live = n_live;
     k.K = n_bins; k.dim = dim; k.H = hidden; k.n_slabs = n_slabs; k.n_chunks = n_chunks; k.n_groups = n_groups; k.n_ranges = n_ranges;
-    static const int no_xcd = sx_debug_knob("SX_SLAB_NO_XCD", 0);                             // experiments, read once
-    k.xcd_map = (n_ranges % 8 == 0) && !no_xcd;
+    k.xcd_map = n_ranges % 8 == 0;
     k.left = left; k.right = right; k.bottom = bottom; k.top = top; k.ldj_scale = ldj_scale;
     const int HTa = HT <= 4 ? HT : (HT + 1) / 2;                // hidden tiles of the (first) launch; beyond four: two launches
     const size_t lds = (size_t)(pl.spw * (3 * (HT + HTa) * 1024 + 128) + (pl.spw == 2 ? 8 * 1024 + 32 : 0)) * sizeof(float);
@@ -1539,20 +1498,6 @@ extern "C" int sx_rqs_slab_bwd(const float *x, const float *gout, const float *g
 #undef SX_SLAB2
 #undef SX_SLAB
     SX_LAUNCH_CHECK();
-#ifdef SX_SLAB_PROF
-    {
-        (void)hipStreamSynchronize(st);
-        unsigned long long p[16];
-        (void)hipMemcpyFromSymbol(p, HIP_SYMBOL(g_slab_prof), sizeof(p));
-        static const char *names[6] = {"h load+split", "x/adjoint loads+param GEMM issue", "spline reverse", "dp split+gx", "dh GEMM+exchange",
-                                       "turn+contract"};
-        unsigned long long tot = 0;
-        for (int i = 0; i < 6; ++i) tot += p[i];
-        fprintf(stderr, "[slab prof] wave 1 of block 9, %llu passes, s_memtime ticks per pass:", p[6]);
-        for (int i = 0; i < 6; ++i) fprintf(stderr, " %s=%.0f (%.1f%%)", names[i], (double)p[i] / (p[6] ? p[6] : 1), 100.0 * p[i] / (tot ? tot : 1));
-        fprintf(stderr, " total=%.0f\n", (double)tot / (p[6] ? p[6] : 1));
-    }
-#endif
     const int N2 = 32 * HT, E = 96 * N2 + 96;
     hipLaunchKernelGGL(rqs_slab_w_reduce_kernel, dim3((E + 255) / 256, n_slabs), dim3(256), 0, st, k.w_part, n_ranges, N2,
                        (int)hidden, slot_rows, dW, ldw, db, scale);

@@ -1,9 +1,7 @@
 """Experiment / A-B switches of the host side, in ONE place (six ``STRIBOR_*`` switches were read ad hoc in
 product code paths).  Product code asks ``debug.on(NAME)``; every name is declared here with what it does.  None of them is needed to
 use the package; they exist for the measurements in ``tools/`` and the A/B tests in ``tests/``.  The environment is read at the time
-of the call (tests flip them with ``monkeypatch.setenv``).
-
-The library's own knobs (``SX_*``, read once per process through ``sx_debug_knob`` in csrc/sx_build_id.cpp) are listed there.
+of the call (tests flip them with ``monkeypatch.setenv``).  The HIP library itself reads no environment variables.
 """
 import os
 

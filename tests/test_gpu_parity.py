@@ -859,16 +859,27 @@ def test_dynamic_chunk_handout_equals_static_and_is_stream_safe():
     results to the static stride for ragged batch sizes, launch after launch, and on two streams at once."""
     torch.manual_seed(5)
     flow = fd.build_flow(st, fd.cfg2_desc(4, 64, 64), 64).to(DEV)
+    prog = flow._fused_program(True, 64, 0, torch.device(DEV))
+    _, block, _ = prog.launch_info(1)
+    rpb = block // 2                               # rows per workgroup chunk: one 32-row sample tile per wave
+    step = 2 * prog.launch_info(1 << 30)[0] * rpb  # the longest slice the dispatcher still hands out statically
+
+    def static_log_prob(x):
+        # slices of whole workgroup chunks (every row keeps its 32-row group), each with at most twice as many chunks as
+        # workgroups: the dispatcher runs those with the static stride
+        outs = []
+        for r0 in range(0, x.shape[0], step):
+            m = min(step, x.shape[0] - r0)
+            assert -(-m // rpb) <= 2 * prog.launch_info(m)[0]
+            outs.append(flow.log_prob(x[r0:r0 + m]))
+        return torch.cat(outs)
+
     sizes = [1, 127, 128 * 2048 + 1, 300_007, 1 << 19, (1 << 19) + 255, 777_777]
     for n in sizes:
         x = torch.randn(n, 64, device=DEV)
         a = flow.log_prob(x)
         b = flow.log_prob(x)                       # second launch on the same stream: counters were re-armed
-        os.environ['SX_STATIC_CHUNKS'] = '1'
-        try:
-            c = flow.log_prob(x)
-        finally:
-            del os.environ['SX_STATIC_CHUNKS']
+        c = static_log_prob(x)
         assert torch.equal(a, b) and torch.equal(a, c), n
         s = flow.log_prob_sum(x)
         assert abs(s.item() - a.double().sum().item()) <= 1e-9 * abs(s.item()) + 1e-6, n

@@ -2,8 +2,7 @@
 # Variant build of the library for A/B timing on ONE box (boxes differ by 3 - 8 %: never compare across gpurun calls).
 #   tools/build_variant.sh <name> <TX_HT pair, e.g. 4_2, or pair + MODE family, e.g. 4_2_f0> "<extra hipcc flags>"
 # copies csrc + include to /tmp/v_<name>, rebuilds only sx_flow_x_<pair>_f*.o (or the one family object) and the host dispatcher with the extra flags (e.g.
-# "-DSX_ONLY_MODE=7" for a seconds-long single-kernel build, "-DSX_EXPERIMENTS -DSX_DEBUG_KNOBS" for the in-kernel stamps,
-# "-DSX_EXPERIMENTS -DSX_X=32" for an ablation) and leaves build_variants/libstribor_hip_<name>.so (git-ignored; it travels with gpurun).
+# "-DSX_ONLY_MODE=7" for a seconds-long single-kernel build) and leaves build_variants/libstribor_hip_<name>.so (git-ignored).
 # STRIBOR_HIP_LIB=$PWD/build_variants/libstribor_hip_<name>.so selects it; tools/experiments/cfg4_ab.sh runs all of them interleaved.
 set -e
 NAME=$1; PAIR=$2; EXTRA=$3
