@@ -683,6 +683,35 @@ typedef struct {
 } sx_sn_job;
 int sx_spectral_sigma(const sx_sn_job *job_host, int32_t n_calls, float *sigma, void *stream);
 
+/* ---- multi-head attention core (stribor/net/attention.py:8-49 with util/safe_softmax.py:3-14) ---------------------------------
+ * q [R, Nq, E], k / v [R, Nk, E]: element (r, n, e) at base + r * bs + n * rs + e (unit column stride; bs = 0 broadcasts one
+ * [N, E] block over R).  n_heads heads of width dh = E / n_heads (1..SX_ATTENTION_MAX_HEAD_DIM), scale (1 / dh) ** 0.5
+ * (attention.py:29-33).  mask: [R, Nk] per key (row stride mask_bs, 0 = one row for all R) or NULL; key j is masked iff
+ * mask[j] != 1 (attention.py:38-41: (1 - mask).bool()).  mask_diagonal: key == query is masked (attention.py:35-36; needs
+ * Nq == Nk).  out_mask: output row n is multiplied by mask[n] (attention.py:47-48: the reference does so iff Nq == Nk).
+ * A query whose keys are all masked gets an output of exactly 0 (safe_softmax.py:12-13).  Exact fp32 (v_mfma_f32_32x32x2_f32) in
+ * every set_gemm_precision mode. */
+#define SX_ATTENTION_MAX_HEAD_DIM 128
+typedef struct {
+    const float *q, *k, *v;
+    int64_t q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;
+    const float *mask;
+    int64_t mask_bs;
+    int64_t R;
+    int32_t Nq, Nk, E, n_heads;
+    int32_t mask_diagonal, out_mask;
+} sx_attention_args;
+
+/* out [R, Nq, E] contiguous = attention(q, k, v) (attention.py:26-49); lse [R, n_heads, Nq] = log sum_j exp(score_j) per query
+ * (+inf for a fully masked query), for sx_attention_bwd.  Flash-style: no [Nq, Nk] tensor in HBM.  One launch. */
+int sx_attention_fwd(const sx_attention_args *args_host, float *out, float *lse, void *stream);
+
+/* dq [R, Nq, E], dk / dv [R, Nk, E] (contiguous) of the forward above, from its output y, its lse and dy = dL/dout (contiguous):
+ * P recomputed from lse, D = rowsum(dy o y), dS = P o (dP - D).  delta: caller scratch of R * n_heads * Nq floats.  Two launches
+ * (query-owner pass for dq, key-owner pass for dk / dv), no atomics: bit-identical across runs.  No mask gradient. */
+int sx_attention_bwd(const sx_attention_args *args_host, const float *y, const float *dy, const float *lse, float *dq, float *dk,
+                     float *dv, float *delta, void *stream);
+
 /* LDS bytes and grid the launcher will use for a program (introspection for tests/bench). */
 int sx_flow_launch_info(const sx_program *prog_host, int64_t n_rows, int32_t *grid, int32_t *block,
                         int32_t *lds_bytes);

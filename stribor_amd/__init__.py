@@ -3,7 +3,8 @@
 Same names and constructor signatures as ``stribor`` for the classes on the path
 (``NormalizingFlow``, ``Coupling``, ``Affine``, ``Spline``, ``AffineLU``, ``MatrixExponential``,
 ``Permute``/``Flip``, ``Sigmoid``/``Logit``, ``ELU``, ``LeakyReLU``, ``Cumsum``/``Diff``, ``Identity``,
-``IResNet``/``ContinuousIResNet``, ``UnitNormal``, ``net.MLP``, ``util.get_mask``); the arithmetic is hand-written
+``IResNet``/``ContinuousIResNet``, ``UnitNormal``, ``net.MLP``, ``net.attention``/``net.Attention``/``net.SelfAttention``/
+``net.InducedSelfAttention``, ``util.get_mask``, ``util.safe_softmax``); the arithmetic is hand-written
 HIP for gfx950 behind the C ABI in ``include/stribor_hip.h``.  There is no CPU fallback.
 """
 from . import net, util

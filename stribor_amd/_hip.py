@@ -59,12 +59,15 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_wgrad_scratch_floats', 'sx_wgrad_layer_scratch_floats', 'sx_flow_bwd_max_steps', 'sx_flow_bwd_partials',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
-           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma']
+           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
 RESNET_LDS_BYTES = 160 * 1024
 RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
+
+# multi-head attention core (include/stribor_hip.h: sx_attention_fwd / sx_attention_bwd)
+ATTENTION_MAX_HEAD_DIM = 128
 
 
 class HipLibraryMissing(RuntimeError):
@@ -103,6 +106,13 @@ class sx_resnet_layer(C.Structure):
 class sx_resnet_net(C.Structure):
     _fields_ = [('layer', sx_resnet_layer * 4), ('n_layers', C.c_int32), ('dim', C.c_int32), ('act', C.c_int32),
                 ('final_act', C.c_int32), ('n_wrapped', C.c_int32), ('pad_', C.c_int32)]
+
+
+class sx_attention_args(C.Structure):
+    _fields_ = [('q', C.c_void_p), ('k', C.c_void_p), ('v', C.c_void_p), ('q_bs', C.c_int64), ('q_rs', C.c_int64),
+                ('k_bs', C.c_int64), ('k_rs', C.c_int64), ('v_bs', C.c_int64), ('v_rs', C.c_int64), ('mask', C.c_void_p),
+                ('mask_bs', C.c_int64), ('R', C.c_int64), ('Nq', C.c_int32), ('Nk', C.c_int32), ('E', C.c_int32),
+                ('n_heads', C.c_int32), ('mask_diagonal', C.c_int32), ('out_mask', C.c_int32)]
 
 
 class sx_sn_layer(C.Structure):
@@ -219,6 +229,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_resnet_flow.argtypes = [C.POINTER(sx_resnet_net), vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sx_spectral_sigma.restype = i32
     lib.sx_spectral_sigma.argtypes = [C.POINTER(sx_sn_job), i32, vp, vp]
+    lib.sx_attention_fwd.restype = i32
+    lib.sx_attention_fwd.argtypes = [C.POINTER(sx_attention_args), vp, vp, vp]
+    lib.sx_attention_bwd.restype = i32
+    lib.sx_attention_bwd.argtypes = [C.POINTER(sx_attention_args), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

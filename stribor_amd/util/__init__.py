@@ -1,5 +1,6 @@
 from . import mask
 from .mask import get_mask
+from .safe_softmax import safe_softmax
 
 
 def quadratic_spline_latent_dim(dim: int, n_bins: int) -> int:

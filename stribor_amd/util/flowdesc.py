@@ -16,6 +16,10 @@ A description is a list of dicts, e.g.
     {"kind": "flip"}
     {"kind": "iresnet", "dim": 2, "hidden": [32, 64], "n_power_iterations": 5}     activation / final_activation optional
     {"kind": "continuous_iresnet", "dim": 2, "hidden": [32, 32], "time_kind": "tanh"}   (+ "time_hidden" for Fourier)
+A coupling's conditioner is a net.MLP unless "net" says otherwise: "hand" (HandNet below), "self_attention" or
+"induced_self_attention" (net.SelfAttention / net.InducedSelfAttention with "hidden" as hidden_dims, "n_heads" and "n_points"
+optional), e.g. {"kind": "coupling_affine", "dim": 4, "hidden": [32], "mask": "ordered_left_half", "latent_dim": 3,
+"set_data": true, "net": "self_attention", "n_heads": 4}.
 """
 from __future__ import annotations
 
@@ -46,8 +50,14 @@ class HandNet(torch.nn.Module):
 
 
 def _make_net(st, d: Dict, in_dim: int, out_dim: int):
-    if d.get('net', 'mlp') == 'hand':
+    kind = d.get('net', 'mlp')
+    if kind == 'hand':
         return HandNet(in_dim, d['hidden'][0], out_dim)
+    if kind == 'self_attention':
+        return st.net.SelfAttention(in_dim, list(d['hidden']), out_dim, n_heads=d.get('n_heads', 1))
+    if kind == 'induced_self_attention':
+        return st.net.InducedSelfAttention(in_dim, list(d['hidden']), out_dim, n_heads=d.get('n_heads', 1),
+                                           n_points=d.get('n_points', 32))
     return st.net.MLP(in_dim, list(d['hidden']), out_dim)
 
 
