@@ -683,6 +683,44 @@ typedef struct {
 } sx_sn_job;
 int sx_spectral_sigma(const sx_sn_job *job_host, int32_t n_calls, float *sigma, void *stream);
 
+/* ---- continuous normalizing flow on a fixed grid (ContinuousTransform, stribor/flows/cnf.py:13-262; net/diffeq.py:51-75) ----
+ * The ODE function is DiffeqMLP: an MLP over the columns [t, x (dim), latent (latent_dim)] with one or two hidden layers and no
+ * final activation.  One launch integrates x from t0 to t1 and, on request, the exact divergence along the path. */
+#define SX_CNF_MAX_DIM 64
+#define SX_CNF_LDS_BYTES (160 * 1024)
+#define SX_CNF_EULER    0               /* y += dt f(t, y)                                                            */
+#define SX_CNF_MIDPOINT 1               /* y += dt f(t + dt/2, y + dt/2 f(t, y))                                      */
+#define SX_CNF_RK4      2               /* the 3/8 rule: k2 at t + dt/3, k3 at t + 2dt/3, k4 at t + dt; y += dt (k1 + 3 (k2 + k3) + k4) / 8 */
+typedef struct {
+    const float *W;        /* [out_dim, in_dim] row-major                                                              */
+    const float *b;        /* [out_dim] or NULL                                                                        */
+    int32_t out_dim, in_dim;
+} sx_cnf_layer;
+typedef struct {
+    sx_cnf_layer layer[3];
+    int32_t n_layers;      /* Linear layers: 2 (one hidden layer) or 3 (two); layer 0 reads 1 + dim + latent_dim columns  */
+    int32_t dim;           /* 1..SX_CNF_MAX_DIM                                                                         */
+    int32_t latent_dim;    /* 1 + dim + latent_dim <= 128                                                               */
+    int32_t act;           /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU (the derivative is taken from the activation's output) */
+    const float *trace;    /* the weight-only constants of tr df/dx, W1x = layer 0's x columns (needed iff want_ldj):
+                              n_layers == 2: c [H1], c_j = sum_i W2[i, j] W1x[j, i]
+                              n_layers == 3: C [P, P] row-major, P = 32 * tiles(max(H1, H2)), tiles(n) = 1, 2 or 4 tiles of 32,
+                                             C[k, j] = W2[k, j] (W1x W3)[j, k], zero beyond [H2, H1]                   */
+} sx_cnf_net;
+
+/* Bytes of LDS the launch stages for this network (0 for one outside the coverage above).  With two hidden layers the matrix C
+ * joins the weights in LDS when the sum stays within SX_CNF_LDS_BYTES and is read from global memory otherwise; a network whose
+ * weights alone exceed the budget is refused. */
+size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj);
+
+/* x, y: fp32 [n_rows, dim] (may alias); latent: fp32 [n_rows, latent_dim] or NULL; ldj: fp32 [n_rows] (written iff want_ldj):
+ * the integral of tr df/dx over the grid with the solver's own tableau and signed dt (cnf.py:99, 219: the forward log-det for
+ * t0 < t1, minus it for t0 > t1).  The grid has n_steps steps: point i is t0 + sign(t1 - t0) * (i * step_size) in fp32 and point
+ * n_steps is t1 (n_steps == 1: the single step [t0, t1]; step_size is then unused).  Exact fp32 arithmetic
+ * (v_mfma_f32_32x32x2_f32) in every set_gemm_precision mode. */
+int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
+
 /* ---- multi-head attention core (stribor/net/attention.py:8-49 with util/safe_softmax.py:3-14) ---------------------------------
  * q [R, Nq, E], k / v [R, Nk, E]: element (r, n, e) at base + r * bs + n * rs + e (unit column stride; bs = 0 broadcasts one
  * [N, E] block over R).  n_heads heads of width dh = E / n_heads (1..SX_ATTENTION_MAX_HEAD_DIM), scale (1 / dh) ** 0.5

@@ -59,12 +59,18 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_wgrad_scratch_floats', 'sx_wgrad_layer_scratch_floats', 'sx_flow_bwd_max_steps', 'sx_flow_bwd_partials',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
-           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd']
+           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
+           'sx_cnf_flow']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
 RESNET_LDS_BYTES = 160 * 1024
 RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
+
+# continuous normalizing flow on a fixed grid (include/stribor_hip.h: sx_cnf_flow)
+CNF_MAX_DIM = 64
+CNF_LDS_BYTES = 160 * 1024
+CNF_SOLVERS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
 
 # multi-head attention core (include/stribor_hip.h: sx_attention_fwd / sx_attention_bwd)
 ATTENTION_MAX_HEAD_DIM = 128
@@ -106,6 +112,15 @@ class sx_resnet_layer(C.Structure):
 class sx_resnet_net(C.Structure):
     _fields_ = [('layer', sx_resnet_layer * 4), ('n_layers', C.c_int32), ('dim', C.c_int32), ('act', C.c_int32),
                 ('final_act', C.c_int32), ('n_wrapped', C.c_int32), ('pad_', C.c_int32)]
+
+
+class sx_cnf_layer(C.Structure):
+    _fields_ = [('W', C.c_void_p), ('b', C.c_void_p), ('out_dim', C.c_int32), ('in_dim', C.c_int32)]
+
+
+class sx_cnf_net(C.Structure):
+    _fields_ = [('layer', sx_cnf_layer * 3), ('n_layers', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32),
+                ('trace', C.c_void_p)]
 
 
 class sx_attention_args(C.Structure):
@@ -233,6 +248,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_attention_fwd.argtypes = [C.POINTER(sx_attention_args), vp, vp, vp]
     lib.sx_attention_bwd.restype = i32
     lib.sx_attention_bwd.argtypes = [C.POINTER(sx_attention_args), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.sx_cnf_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_lds_bytes.argtypes = [C.POINTER(sx_cnf_net), i32]
+    lib.sx_cnf_flow.restype = i32
+    lib.sx_cnf_flow.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

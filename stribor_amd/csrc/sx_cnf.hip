@@ -1,0 +1,502 @@
+// Continuous normalizing flow (ContinuousTransform, stribor/flows/cnf.py:13-262, with net/diffeq.py's DiffeqMLP) on a fixed grid,
+// in one launch per call.
+//
+// sx_cnf_flow -- the solve dx/dt = f(t, x, latent), f = MLP([t, x, latent]) with one or two hidden layers and no final
+// activation, from t0 to t1 by euler / midpoint / rk4 (the 3/8 rule) over the grid of DESIGN.md "CNF", together with the exact
+// divergence tr df/dx and its integral (the log-det):
+//   * one wave = 32 rows, laid out as in sx_resnet.hip: rows on the MFMA column (lane & 31), features on the C rows, a 32-feature
+//     tile of a row = one f32x16 C fragment = the B operand of the next GEMM.  The state, every stage vector, the hidden
+//     activations and the per-row log-det accumulator stay in registers for the whole grid;
+//   * the x columns of W1 and the later layers are staged into LDS once per workgroup (A-fragment order, zero-padded to tiles of
+//     32, the layer image of sx_resnet.hip); the workgroup then walks its 32-row groups;
+//   * time is uniform over rows: per stage the first layer's bias is b1 + t_stage * W1[:, 0];
+//   * the latent columns are constant along the solve: W1[:, latent] . latent_row is one GEMM per row group before the loop (its
+//     A fragments come straight from global memory: once per group, no LDS spent on it);
+//   * the trace (d_l = act'(hidden layer l), W1x = the x columns of W1):
+//       one hidden layer   tr J = sum_j d1_j c_j,           c_j = sum_i W2[i, j] W1x[j, i]
+//       two hidden layers  tr J = d2^T C d1,                 C[k, j] = W2[k, j] (W1x W3)[j, k]     (one extra H2 x H1 GEMM)
+//     c / C depend on the weights only and are passed in (fp32, derived in fp64 by the caller).  c and -- where the LDS budget
+//     allows -- C sit in LDS beside the weights; a C that does not fit (two hidden layers of 128 units) is read from global
+//     memory (L2-resident: 64 KiB shared by every wave);
+//   * arithmetic: exact fp32, v_mfma_f32_32x32x2_f32, library tanhf / expf; unfused multiply-adds in the tableau (the file is
+//     compiled with -ffp-contract=off) so a step is the reference solver's sequence of roundings.  set_gemm_precision is ignored.
+//
+// Coverage: dim <= 64 (<= 32 with two hidden layers wider than 64 units: that kernel would spill), 1 + dim + latent_dim <= 128,
+// one or two hidden layers of <= 128 units, activations Identity / Tanh /
+// ReLU / Sigmoid / ELU / Softplus / LeakyReLU (the ones whose derivative is a function of the activation's OUTPUT).
+#include "sx_common.h"
+
+#define SX_CNF_WAVES 4
+#define SX_CNF_THREADS (SX_CNF_WAVES * 64)
+
+namespace {
+
+__host__ __device__ inline int cn_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+extern __shared__ __attribute__((aligned(16))) float cn_smem[];
+
+__device__ __forceinline__ float cn_act(float v, int act) {
+    switch (act) {
+        case SX_ACT_TANH: return tanhf(v);
+        case SX_ACT_RELU: return fmaxf(v, 0.f);
+        case SX_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
+        case SX_ACT_ELU: return v > 0.f ? v : expm1f(v);
+        case SX_ACT_SOFTPLUS: return v > 20.f ? v : log1pf(expf(v));
+        case SX_ACT_LEAKYRELU: return v > 0.f ? v : 0.01f * v;
+        default: return v;
+    }
+}
+
+// act'(v) from a = act(v)
+__device__ __forceinline__ float cn_dact(float a, int act) {
+    switch (act) {
+        case SX_ACT_TANH: return 1.f - a * a;
+        case SX_ACT_RELU: return a > 0.f ? 1.f : 0.f;
+        case SX_ACT_SIGMOID: return a * (1.f - a);
+        case SX_ACT_ELU: return a > 0.f ? 1.f : a + 1.f;
+        case SX_ACT_SOFTPLUS: return 1.f - expf(-a);            // sigmoid(v) = 1 - exp(-softplus(v))
+        case SX_ACT_LEAKYRELU: return a > 0.f ? 1.f : 0.01f;
+        default: return 1.f;
+    }
+}
+
+// (inlined on purpose: an out-of-line call would spill the live stage vectors around it)
+__device__ __forceinline__ void cn_act_tile(f32x16 *v, int act) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) (*v)[r] = cn_act((*v)[r], act);
+}
+
+__device__ __forceinline__ void cn_dact_tile(f32x16 *v, int act) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) (*v)[r] = cn_dact((*v)[r], act);
+}
+
+template <int T>
+struct ctile {
+    f32x16 v[T];
+};
+
+// LDS image of a matrix block: MT x KT A-operand tiles of 1024 floats (tile (m, c), float g*256 + lane*4 + j holds
+// W[32m + (lane & 31)][col0 + 32c + kmap(4g + j, lane >> 5)]), W row-major with row stride ld
+__device__ __forceinline__ void cn_stage(const float *__restrict__ W, int out_dim, int in_dim, int ld, int col0, int MT, int KT, int base) {
+    const int n_w = MT * KT * 1024;
+    for (int e = threadIdx.x; e < n_w; e += SX_CNF_THREADS) {
+        const int tile = e >> 10, rem = e & 1023;
+        const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
+        const int m = tile / KT, c = tile - m * KT;
+        const int row = 32 * m + (lane & 31), col = 32 * c + cn_kmap(4 * g + j, lane >> 5);
+        cn_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * ld + col0 + col] : 0.f;
+    }
+}
+
+// a vector of n_pad floats (entries beyond n: 0), element i at stride `stride` of src (NULL: zeros)
+__device__ __forceinline__ void cn_stage_vec(const float *__restrict__ src, int n, int stride, int n_pad, int base) {
+    for (int i = threadIdx.x; i < n_pad; i += SX_CNF_THREADS)
+        cn_smem[base + i] = (src != nullptr && i < n) ? src[(int64_t)i * stride] : 0.f;
+}
+
+// out[m] = (W . in)[m], m < MT; W: an image at `wb` (already offset by lane * 4), KT input tiles
+template <int KT, int MT>
+__device__ __forceinline__ void cn_gemm(const ctile<KT> &in, ctile<MT> &out, const float *wb) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        f32x16 acc = {};
+#pragma unroll
+        for (int c = 0; c < KT; ++c) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(wb + (m * KT + c) * 1024 + g * 256);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in.v[c][4 * g + 0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in.v[c][4 * g + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in.v[c][4 * g + 2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in.v[c][4 * g + 3], acc, 0, 0, 0);
+            }
+        }
+        out.v[m] = acc;
+    }
+}
+
+// the same product with the matrix read from global memory: row-major [MT * 32][KT * 32], zero-padded (a lane's four A values
+// of k-group g are the contiguous columns 32c + 8g + 4h .. + 3 of row 32m + (lane & 31))
+template <int KT, int MT>
+__device__ __forceinline__ void cn_gemm_global(const ctile<KT> &in, ctile<MT> &out, const float *__restrict__ W, int lane) {
+    const float *wl = W + (int64_t)(lane & 31) * (KT * 32) + 4 * (lane >> 5);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        f32x16 acc = {};
+#pragma unroll
+        for (int c = 0; c < KT; ++c) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(wl + (int64_t)m * 32 * (KT * 32) + 32 * c + 8 * g);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in.v[c][4 * g + 0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in.v[c][4 * g + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in.v[c][4 * g + 2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in.v[c][4 * g + 3], acc, 0, 0, 0);
+            }
+        }
+        out.v[m] = acc;
+    }
+}
+
+// feature 32m + kmap(r, h) of a padded vector at `vb` (already offset by 4 * h)
+__device__ __forceinline__ float cn_vec(const float *vb, int m, int r) { return vb[32 * m + 8 * (r >> 2) + (r & 3)]; }
+
+template <int T>
+__device__ __forceinline__ void cn_act_all(ctile<T> &v, int act) {
+#pragma unroll
+    for (int m = 0; m < T; ++m) {
+        if (act == SX_ACT_RELU) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v.v[m][r] = fmaxf(v.v[m][r], 0.f);
+        } else if (act != SX_ACT_IDENTITY) {
+            cn_act_tile(&v.v[m], act);
+        }
+    }
+}
+
+struct cn_args {
+    sx_cnf_net net;
+    int base_w[3];          // LDS float offset of W1x, W2(, W3)
+    int base_b[3];          // ... of the biases
+    int base_w0;            // ... of W1[:, 0] (the time column)
+    int base_tr;            // ... of c (one hidden layer) or C (two, when c_in_lds)
+    const float *x;
+    const float *latent;
+    float *y;
+    float *ldj;
+    int64_t n_rows;
+    int solver, n_steps, want_ldj, c_in_lds;
+    float t0, t1, step_size;
+};
+
+// f(t, x) and -- when `want` -- tr = tr df/dx for the wave's 32 rows
+template <int DT, int HT, int NH>
+__device__ __forceinline__ void cn_eval(const cn_args &a, const ctile<DT> &xin, float t, const ctile<HT> &lat, ctile<DT> &k, bool want, float &tr,
+                                        int lane) {
+    const int h = lane >> 5, act = a.net.act;
+    // the weights in LDS never change, so their loads are loop-invariant: without this the compiler hoists them out of the step
+    // loop and holds whole matrices in registers
+    asm volatile("" ::: "memory");
+    const float *b1 = cn_smem + a.base_b[0] + 4 * h, *w0 = cn_smem + a.base_w0 + 4 * h;
+    ctile<HT> h1;
+    cn_gemm<DT, HT>(xin, h1, cn_smem + a.base_w[0] + lane * 4);
+#pragma unroll
+    for (int m = 0; m < HT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h1.v[m][r] = (h1.v[m][r] + lat.v[m][r]) + (cn_vec(b1, m, r) + t * cn_vec(w0, m, r));
+    cn_act_all<HT>(h1, act);
+    float s = 0.f;
+    if (NH == 1) {
+        if (want) {
+            const float *cv = cn_smem + a.base_tr + 4 * h;
+#pragma unroll
+            for (int m = 0; m < HT; ++m) {
+                f32x16 d = h1.v[m];
+                if (act != SX_ACT_IDENTITY) cn_dact_tile(&d, act);
+                else d = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s += d[r] * cn_vec(cv, m, r);
+            }
+        }
+        cn_gemm<HT, DT>(h1, k, cn_smem + a.base_w[1] + lane * 4);
+        const float *b2 = cn_smem + a.base_b[1] + 4 * h;
+#pragma unroll
+        for (int m = 0; m < DT; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) k.v[m][r] += cn_vec(b2, m, r);
+    } else {
+        ctile<HT> h2;
+        cn_gemm<HT, HT>(h1, h2, cn_smem + a.base_w[1] + lane * 4);
+        const float *b2 = cn_smem + a.base_b[1] + 4 * h;
+#pragma unroll
+        for (int m = 0; m < HT; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) h2.v[m][r] += cn_vec(b2, m, r);
+        cn_act_all<HT>(h2, act);
+        if (want) {
+            // h1 <- d1, v = C d1, s = d2 . v
+#pragma unroll
+            for (int m = 0; m < HT; ++m) {
+                if (act != SX_ACT_IDENTITY) cn_dact_tile(&h1.v[m], act);
+                else h1.v[m] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+            }
+            // v = C d1 one 32-row tile at a time, consumed at once: s += d2 . v
+#pragma unroll
+            for (int m = 0; m < HT; ++m) {
+                ctile<1> v;
+                if (a.c_in_lds) cn_gemm<HT, 1>(h1, v, cn_smem + a.base_tr + m * HT * 1024 + lane * 4);
+                else cn_gemm_global<HT, 1>(h1, v, a.net.trace + (int64_t)m * 32 * (HT * 32), lane);
+                f32x16 d = h2.v[m];
+                if (act != SX_ACT_IDENTITY) cn_dact_tile(&d, act);
+                else d = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s += d[r] * v.v[0][r];
+            }
+        }
+        asm volatile("" ::: "memory");
+        cn_gemm<HT, DT>(h2, k, cn_smem + a.base_w[2] + lane * 4);
+        const float *b3 = cn_smem + a.base_b[2] + 4 * h;
+#pragma unroll
+        for (int m = 0; m < DT; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) k.v[m][r] += cn_vec(b3, m, r);
+    }
+    if (want) tr = s + __shfl_xor(s, 32, 64);          // the two lane halves hold the two feature halves of a row
+}
+
+template <int DT, int HT, int NH>
+__global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args a) {
+    const sx_cnf_net &net = a.net;
+    const int D = net.dim, L = net.latent_dim, in_dim = 1 + D + L, H1 = net.layer[0].out_dim;
+    cn_stage(net.layer[0].W, H1, D, in_dim, 1, HT, DT, a.base_w[0]);
+    cn_stage_vec(net.layer[0].b, H1, 1, HT * 32, a.base_b[0]);
+    cn_stage_vec(net.layer[0].W, H1, in_dim, HT * 32, a.base_w0);
+    if (NH == 1) {
+        cn_stage(net.layer[1].W, D, H1, H1, 0, DT, HT, a.base_w[1]);
+        cn_stage_vec(net.layer[1].b, D, 1, DT * 32, a.base_b[1]);
+        cn_stage_vec(a.want_ldj ? net.trace : nullptr, H1, 1, HT * 32, a.base_tr);
+    } else {
+        const int H2 = net.layer[1].out_dim;
+        cn_stage(net.layer[1].W, H2, H1, H1, 0, HT, HT, a.base_w[1]);
+        cn_stage_vec(net.layer[1].b, H2, 1, HT * 32, a.base_b[1]);
+        cn_stage(net.layer[2].W, D, H2, H2, 0, DT, HT, a.base_w[2]);
+        cn_stage_vec(net.layer[2].b, D, 1, DT * 32, a.base_b[2]);
+        if (a.want_ldj && a.c_in_lds) cn_stage(net.trace, HT * 32, HT * 32, HT * 32, 0, HT, HT, a.base_tr);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const bool want = a.want_ldj != 0;
+    const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
+    const int64_t n_groups = (a.n_rows + 31) >> 5;
+    for (int64_t grp = (int64_t)blockIdx.x * SX_CNF_WAVES + (threadIdx.x >> 6); grp < n_groups;
+         grp += (int64_t)gridDim.x * SX_CNF_WAVES) {
+        const int64_t row = grp * 32 + (lane & 31);
+        const bool live = row < a.n_rows;
+        ctile<DT> y;
+#pragma unroll
+        for (int c = 0; c < DT; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = 32 * c + cn_kmap(r, h);
+                y.v[c][r] = (live && f < D) ? a.x[row * D + f] : 0.f;
+            }
+        // the latent share of the first layer: W1[:, 1 + D ..] . latent_row, once per row
+        ctile<HT> lat;
+#pragma unroll
+        for (int m = 0; m < HT; ++m) lat.v[m] = f32x16{};
+        if (L > 0) {
+            const float *W1 = net.layer[0].W;
+            for (int c = 0; c < (L + 31) >> 5; ++c) {
+                f32x16 lb;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int f = 32 * c + cn_kmap(r, h);
+                    lb[r] = (live && f < L) ? a.latent[row * L + f] : 0.f;
+                }
+#pragma unroll
+                for (int m = 0; m < HT; ++m) {
+                    const int wr = 32 * m + (lane & 31);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int f = 32 * c + cn_kmap(q, h);
+                        const float av = (wr < H1 && f < L) ? W1[(int64_t)wr * in_dim + 1 + D + f] : 0.f;
+                        lat.v[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, lb[q], lat.v[m], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        float l = 0.f;
+        const int n_stages = a.solver == SX_CNF_EULER ? 1 : a.solver == SX_CNF_MIDPOINT ? 2 : 4;
+        const float third = 1.f / 3.f, two_thirds = 2.f / 3.f;
+        for (int i = 0; i < a.n_steps; ++i) {
+            // the grid: t_i = t0 +- i * step_size, the last point replaced by t1
+            const float ta = i == 0 ? a.t0 : a.t0 + sgn * ((float)i * a.step_size);
+            const float tb = i + 1 == a.n_steps ? a.t1 : a.t0 + sgn * ((float)(i + 1) * a.step_size);
+            const float dt = tb - ta, half = 0.5f * dt;
+            ctile<DT> k1, k2, xs = y;          // (rk4: after stage 3, k1 holds k1 + 3 (k2 + k3))
+            float q1 = 0.f, q2 = 0.f, ts = ta;
+            // one copy of the network's code serves every stage: the stage index is wave-uniform
+            for (int st = 0; st < n_stages; ++st) {
+                ctile<DT> k;
+                float q = 0.f;
+                cn_eval<DT, HT, NH>(a, xs, ts, lat, k, want, q, lane);
+                if (a.solver == SX_CNF_EULER) {                       // y += dt f(t, y)
+#pragma unroll
+                    for (int c = 0; c < DT; ++c)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) y.v[c][r] = y.v[c][r] + dt * k.v[c][r];
+                    l = l + dt * q;
+                } else if (a.solver == SX_CNF_MIDPOINT) {             // y += dt f(t + dt/2, y + f(t, y) dt/2)
+                    if (st == 0) {
+#pragma unroll
+                        for (int c = 0; c < DT; ++c)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + k.v[c][r] * half;
+                        ts = ta + half;
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < DT; ++c)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) y.v[c][r] = y.v[c][r] + dt * k.v[c][r];
+                        l = l + dt * q;
+                    }
+                } else if (st == 0) {                                 // rk4, the 3/8 rule
+                    k1 = k; q1 = q;
+#pragma unroll
+                    for (int c = 0; c < DT; ++c)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + (dt * k1.v[c][r]) * third;
+                    ts = ta + dt * third;
+                } else if (st == 1) {
+                    k2 = k; q2 = q;
+#pragma unroll
+                    for (int c = 0; c < DT; ++c)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + dt * (k2.v[c][r] - k1.v[c][r] * third);
+                    ts = ta + dt * two_thirds;
+                } else if (st == 2) {
+#pragma unroll
+                    for (int c = 0; c < DT; ++c)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            xs.v[c][r] = y.v[c][r] + dt * ((k1.v[c][r] - k2.v[c][r]) + k.v[c][r]);
+                            k1.v[c][r] = k1.v[c][r] + 3.f * (k2.v[c][r] + k.v[c][r]);
+                        }
+                    q1 = q1 + 3.f * (q2 + q);
+                    ts = tb;
+                } else {
+#pragma unroll
+                    for (int c = 0; c < DT; ++c)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            y.v[c][r] = y.v[c][r] + ((k1.v[c][r] + k.v[c][r]) * dt) * 0.125f;
+                    l = l + ((q1 + q) * dt) * 0.125f;
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int c = 0; c < DT; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int f = 32 * c + cn_kmap(r, h);
+                    if (f < D) a.y[row * D + f] = y.v[c][r];
+                }
+            if (want && h == 0) a.ldj[row] = l;
+        }
+    }
+}
+
+inline int cn_tiles(int n) { return n <= 32 ? 1 : n <= 64 ? 2 : 4; }
+
+// the LDS plan: float offsets into `a` (may be null), -> floats used.  C goes into LDS when it fits beside the rest.
+size_t cn_plan(const sx_cnf_net &net, int want_ldj, cn_args *a) {
+    const int DT = cn_tiles(net.dim), NH = net.n_layers - 1;
+    int HT = 1;
+    for (int l = 0; l < NH; ++l) HT = cn_tiles(net.layer[l].out_dim) > HT ? cn_tiles(net.layer[l].out_dim) : HT;
+    size_t off = 0;
+    int bw[3] = {0, 0, 0}, bb[3] = {0, 0, 0};
+    for (int l = 0; l <= NH; ++l) {
+        const int KT = l == 0 ? DT : HT, MT = l == NH ? DT : HT;
+        bw[l] = (int)off; off += (size_t)MT * KT * 1024;
+        bb[l] = (int)off; off += (size_t)MT * 32;
+    }
+    const int base_w0 = (int)off; off += (size_t)HT * 32;
+    const int base_tr = (int)off;
+    int c_in_lds = 1;
+    if (NH == 1) off += (size_t)HT * 32;
+    else if (want_ldj) {
+        const size_t c_floats = (size_t)HT * HT * 1024;
+        if ((off + c_floats) * 4 <= SX_CNF_LDS_BYTES) off += c_floats;
+        else c_in_lds = 0;
+    }
+    if (a) {
+        for (int l = 0; l < 3; ++l) { a->base_w[l] = bw[l]; a->base_b[l] = bb[l]; }
+        a->base_w0 = base_w0; a->base_tr = base_tr; a->c_in_lds = c_in_lds;
+    }
+    return off;
+}
+
+int cn_check_net(const sx_cnf_net *net_host) {
+    SX_REQUIRE(net_host != nullptr, "sx_cnf_flow: null network");
+    const sx_cnf_net &net = *net_host;
+    SX_REQUIRE(net.n_layers == 2 || net.n_layers == 3, "sx_cnf_flow: one or two hidden layers (got %d Linear layers)", net.n_layers);
+    SX_REQUIRE(net.dim >= 1 && net.dim <= SX_CNF_MAX_DIM, "sx_cnf_flow: dim must be in 1..%d (got %d)", SX_CNF_MAX_DIM, net.dim);
+    SX_REQUIRE(net.latent_dim >= 0 && 1 + net.dim + net.latent_dim <= 128, "sx_cnf_flow: 1 + dim + latent_dim must be <= 128");
+    SX_REQUIRE(net.act >= SX_ACT_IDENTITY && net.act <= SX_ACT_LEAKYRELU, "sx_cnf_flow: activation %d has no in-kernel derivative", net.act);
+    for (int l = 0; l < net.n_layers; ++l) {
+        const sx_cnf_layer &L = net.layer[l];
+        SX_REQUIRE(L.W != nullptr, "sx_cnf_flow: layer %d has no weight", l);
+        SX_REQUIRE(L.in_dim == (l == 0 ? 1 + net.dim + net.latent_dim : net.layer[l - 1].out_dim), "sx_cnf_flow: layer %d input width", l);
+        SX_REQUIRE(L.out_dim >= 1 && L.out_dim <= 128, "sx_cnf_flow: layer %d width must be in 1..128", l);
+    }
+    SX_REQUIRE(net.layer[net.n_layers - 1].out_dim == net.dim, "sx_cnf_flow: the last layer must map back to dim");
+    // two hidden layers of four tiles beside a two-tile state do not fit the register file (the build would spill): not offered
+    SX_REQUIRE(!(net.n_layers == 3 && net.dim > 32 && (net.layer[0].out_dim > 64 || net.layer[1].out_dim > 64)),
+               "sx_cnf_flow: two hidden layers wider than 64 units need dim <= 32 (got dim %d)", net.dim);
+    return SX_OK;
+}
+
+template <int DT, int HT, int NH>
+int cn_launch(const cn_args &a, size_t lds, void *stream) {
+    auto kern = cnf_flow_kernel<DT, HT, NH>;
+    static bool raised_on[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!raised_on[dev & 63]) {
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SX_CNF_LDS_BYTES);
+        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+        raised_on[dev & 63] = true;
+    }
+    int cus = 0, per_cu = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, SX_CNF_THREADS, lds);
+    if (cus < 1) cus = 1;
+    if (per_cu < 1) per_cu = 1;
+    const int64_t n_groups = (a.n_rows + 31) / 32;
+    const int64_t want = (n_groups + SX_CNF_WAVES - 1) / SX_CNF_WAVES;
+    const int64_t cap = (int64_t)cus * per_cu;
+    const int grid = (int)(want < cap ? want : cap);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(SX_CNF_THREADS), lds, sx_stream(stream), a);
+    SX_LAUNCH_CHECK();
+    return SX_OK;
+}
+
+}  // namespace
+
+extern "C" size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj) {
+    if (cn_check_net(net_host) != SX_OK) return 0;
+    return cn_plan(*net_host, want_ldj, nullptr) * 4;
+}
+
+extern "C" int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                           int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream) {
+    const int rc = cn_check_net(net_host);
+    if (rc != SX_OK) return rc;
+    const sx_cnf_net &net = *net_host;
+    SX_REQUIRE(solver >= SX_CNF_EULER && solver <= SX_CNF_RK4, "sx_cnf_flow: solver must be euler (0), midpoint (1) or rk4 (2), got %d", solver);
+    SX_REQUIRE(n_rows >= 0 && n_steps >= 0, "sx_cnf_flow: negative n_rows / n_steps");
+    SX_REQUIRE(n_steps <= 1 || step_size > 0.f, "sx_cnf_flow: a grid of %d steps needs step_size > 0", n_steps);
+    SX_REQUIRE(x != nullptr && y != nullptr, "sx_cnf_flow: null input / output");
+    SX_REQUIRE(net.latent_dim == 0 || latent != nullptr, "sx_cnf_flow: latent rows missing");
+    SX_REQUIRE(!want_ldj || (ldj != nullptr && net.trace != nullptr), "sx_cnf_flow: want_ldj needs ldj and the trace constants");
+    cn_args a{};
+    a.net = net;
+    const size_t lds = cn_plan(net, want_ldj ? 1 : 0, &a) * 4;
+    SX_REQUIRE(lds <= SX_CNF_LDS_BYTES, "sx_cnf_flow: the padded weights need %zu bytes of LDS (budget %d)", lds, SX_CNF_LDS_BYTES);
+    if (n_rows == 0) return SX_OK;
+    a.x = x; a.latent = latent; a.y = y; a.ldj = ldj; a.n_rows = n_rows;
+    a.solver = solver; a.n_steps = n_steps; a.want_ldj = want_ldj ? 1 : 0;
+    a.t0 = t0; a.t1 = t1; a.step_size = step_size;
+    const int DT = cn_tiles(net.dim), NH = net.n_layers - 1;
+    int HT = 1;
+    for (int l = 0; l < NH; ++l) HT = cn_tiles(net.layer[l].out_dim) > HT ? cn_tiles(net.layer[l].out_dim) : HT;
+#define CN_CASE(D_, H_) \
+    if (DT == D_ && HT == H_) return NH == 1 ? cn_launch<D_, H_, 1>(a, lds, stream) : cn_launch<D_, H_, 2>(a, lds, stream);
+    CN_CASE(1, 1) CN_CASE(1, 2) CN_CASE(1, 4) CN_CASE(2, 1) CN_CASE(2, 2)
+#undef CN_CASE
+    if (DT == 2 && HT == 4 && NH == 1) return cn_launch<2, 4, 1>(a, lds, stream);
+    sx_set_error("sx_cnf_flow: no kernel for %d x %d tiles", DT, HT);
+    return SX_E_BADARG;
+}

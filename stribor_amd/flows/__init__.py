@@ -5,3 +5,4 @@ from .spline import Spline
 from .linear import AffineLU, MatrixExponential
 from .pointwise import ELU, Cumsum, Diff, Identity, LeakyReLU, Logit, Sigmoid
 from .iresnet import ContinuousIResNet, IResNet
+from .cnf import ContinuousTransform

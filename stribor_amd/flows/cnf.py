@@ -1,0 +1,359 @@
+"""Continuous normalizing flow (reference: stribor/flows/cnf.py:13-262): ``ContinuousTransform``.
+
+Same constructor, methods and ``state_dict`` keys (``odefunc.diffeq.net.net.0.weight``, ..., ``odefunc._num_evals``).  The solve
+runs on a FIXED grid with ``solver='euler' | 'midpoint' | 'rk4'`` (torchdiffeq 0.2.2's fixed-grid family; ``rk4`` is the 3/8
+rule); the adaptive and Adams solver names are accepted -- they are the reference's defaults and checkpoints must load -- and
+raise ``NotImplementedError`` when evaluated (DESIGN.md "CNF").
+
+Without an autograd graph, a ``DiffeqMLP`` with one or two hidden layers is ONE launch of ``sx_cnf_flow``: the state, the stage
+vectors and the log-det accumulator stay in registers for the whole grid, the weights sit in LDS, and the exact divergence comes
+from a closed form whose weight-only constants (``trace_constants``) are derived once in fp64.  Everything else -- other nets,
+``mask``, ``set_data``, the Hutchinson estimator of training mode, and every call that has to build a graph -- runs the same grid
+and tableau as a loop of torch ops over the module (``_solve_composed``); gradients are those of the discretised steps.
+"""
+import ctypes
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _hip
+from ..flow import Transform, flatten_rows, graph_wanted
+from ..fused import ProgramCache
+from ..net.diffeq import DiffeqMLP
+from ..net.mlp import MLP
+from ..util.divergence import divergence_approx, divergence_exact, divergence_exact_for_sets
+
+__all__ = ['ContinuousTransform']
+
+FIXED_SOLVERS = ('euler', 'midpoint', 'rk4')
+STAGES = {'euler': 1, 'midpoint': 2, 'rk4': 4}
+_ACT_DEFAULTS = {nn.LeakyReLU: lambda m: m.negative_slope == 0.01, nn.ELU: lambda m: m.alpha == 1.0,
+                 nn.Softplus: lambda m: m.beta == 1 and m.threshold == 20}
+_DIVERGENCES = ('compute', 'compute_set', 'approximate', 'exact', 'none')
+
+
+def fixed_grid(t0: float, t1: float, step_size: Optional[float] = None) -> np.ndarray:
+    """The time grid of a fixed-step solve as fp32 points (the solver specification, DESIGN.md "CNF"): without `step_size` the
+    single step [t0, t1]; with it ceil(|t1 - t0| / step_size + 1) points t0 +- i * step_size, the last one replaced by t1.  All
+    arithmetic is fp32, as the reference solver's is on fp32 integration times."""
+    f = np.float32
+    t0, t1 = f(t0), f(t1)
+    if step_size is None:
+        return np.array([t0, t1], dtype=f)
+    h = f(step_size)
+    if not h > 0:
+        raise ValueError(f'step_size must be positive (got {step_size})')
+    n = int(np.ceil(f(f(abs(f(t1 - t0))) / h) + f(1)))
+    sgn = f(-1.0) if t1 < t0 else f(1.0)
+    grid = (t0 + sgn * (np.arange(n, dtype=f) * h)).astype(f)
+    grid[-1] = t1
+    return grid
+
+
+def trace_constants(weights, dim: int):
+    """The weight-only constants of tr df/dx for f = MLP([t, x, latent]) without a final activation, W1x = the x columns
+    1 .. dim of the first weight:  one hidden layer: c [H1], c_j = sum_i W2[i, j] W1x[j, i];  two: C [H2, H1],
+    C[k, j] = W2[k, j] (W1x W3)[j, k].  Then tr J = sum_j d1_j c_j, resp. d2^T C d1, with d_l = act'(hidden layer l).
+    fp64 in, fp64 out (the caller rounds once)."""
+    W1x = weights[0][:, 1:1 + dim]
+    if len(weights) == 2:
+        return (weights[1].t() * W1x).sum(-1)
+    W2, W3 = weights[1], weights[2]
+    return W2 * (W1x @ W3).t()
+
+
+class ODEfunc(nn.Module):
+    """The augmented dynamics of cnf.py:13-99: d/dt (x, a) = (f(t, x), -div f), with a kept per feature."""
+
+    def __init__(self, diffeq, divergence=None, rademacher=False, has_latent=False, set_data=False, **kwargs):
+        super().__init__()
+        assert divergence in _DIVERGENCES
+        self.diffeq = diffeq
+        self.rademacher = rademacher
+        self.divergence = divergence
+        self.has_latent = has_latent
+        self.set_data = set_data
+        self.register_buffer('_num_evals', torch.tensor(0.))
+        self._e = None
+
+    def before_odeint(self, e=None):
+        self._e = e
+        self._num_evals.fill_(0)
+
+    def num_evals(self):
+        return self._num_evals.item()
+
+    def exact_trace(self) -> bool:
+        """Does this setting evaluate the exact divergence of a row-wise net (cnf.py:91-95)?"""
+        return not self.set_data and (self.divergence == 'compute' or (self.divergence == 'approximate' and not self.training))
+
+    def forward(self, t, states):
+        """states = (x, a[, latent][, mask]) -> their time derivatives (zeros for latent and mask)."""
+        y = states[0]
+        t = torch.as_tensor(t).reshape(1).to(y)
+        latent = mask = None
+        if len(states) == 4:
+            latent, mask = states[2], states[3]
+        elif len(states) == 3:
+            if self.has_latent:
+                latent = states[2]
+            else:
+                mask = states[2]
+        tail = tuple(torch.zeros_like(s) for s in states[2:])
+        if self.divergence == 'none':
+            # cnf.py:82-84 returns a tuple one element short of the state; here the log-det share is an explicit zero
+            return (self.diffeq(t, y, latent=latent, mask=mask), torch.zeros_like(y)) + tail
+        if self.divergence == 'exact':
+            dy, div = self.diffeq(t, y, latent=latent, mask=mask)
+            return (dy, -div) + tail
+        if self._e is None and self.divergence == 'approximate':          # (drawn in eval mode too, where it is not used)
+            if self.rademacher:
+                self._e = torch.randint(low=0, high=2, size=y.shape).to(y) * 2 - 1          # cnf.py:76-80
+            else:
+                self._e = torch.randn_like(y)
+        with torch.enable_grad():
+            if not y.requires_grad:
+                y = y.detach().requires_grad_(True)
+            dy = self.diffeq(t, y, latent=latent, mask=mask)
+            if not self.training or 'compute' in self.divergence:
+                if self.set_data or self.divergence == 'compute_set':
+                    div = divergence_exact_for_sets(dy, y)
+                else:
+                    div = divergence_exact(dy, y)
+            else:
+                div = divergence_approx(dy, y, self._e)
+        return (dy, -div) + tail
+
+
+def _rk_step(func, solver: str, t, t_next, y):
+    """One step of the fixed-grid family on a tuple state: -> the increments.  Scalars t, t_next are fp32 numpy scalars, so stage
+    times are fp32; the operation order is the kernel's (and the fixture solver's)."""
+    f32 = np.float32
+    dt = t_next - t
+    h = float(dt)                       # (tensor * python float: the fp32 value, exactly)
+    k1 = func(t, y)
+    if solver == 'euler':
+        return tuple(k * h for k in k1)
+    if solver == 'midpoint':
+        half = f32(0.5) * dt
+        k2 = func(t + half, tuple(a + k * float(half) for a, k in zip(y, k1)))
+        return tuple(k * h for k in k2)
+    third, two_thirds = f32(1.0 / 3.0), f32(2.0 / 3.0)
+    th = float(third)
+    k2 = func(t + dt * third, tuple(a + (k * h) * th for a, k in zip(y, k1)))
+    k3 = func(t + dt * two_thirds, tuple(a + (b - k * th) * h for a, k, b in zip(y, k1, k2)))
+    k4 = func(t_next, tuple(a + ((k - b) + c) * h for a, k, b, c in zip(y, k1, k2, k3)))
+    return tuple((((k + (b + c) * 3.0) + d) * h) * 0.125 for k, b, c, d in zip(k1, k2, k3, k4))
+
+
+class ContinuousTransform(Transform):
+    """Continuous normalizing flow dx/dt = net(t, x, latent) from 0 to T (cnf.py:102-262).
+
+    >>> f = stribor_amd.ContinuousTransform(dim, net=stribor_amd.net.DiffeqMLP(dim + 1, [64], dim), solver='rk4',
+    ...                                      solver_options={'step_size': 0.05})
+
+    solver: 'euler', 'midpoint' or 'rk4' run (fixed grid; ``solver_options={'step_size': h}``, else the single step [0, T]).  The
+    reference's default 'dopri5' and the other adaptive / Adams names construct and load but raise ``NotImplementedError`` when
+    evaluated: pass ``solver='rk4', solver_options={'step_size': ...}``.  ``use_adjoint`` is recorded and does not change the
+    arithmetic: gradients are those of ``odeint`` through the discretised steps (``odeint_adjoint``'s differ from them by
+    discretisation error only).  ``atol`` / ``rtol`` are recorded; a fixed grid does not use them."""
+
+    def __init__(self, dim: int, net: nn.Module = None, T: float = 1.0, divergence: str = 'approximate', use_adjoint: bool = True,
+                 has_latent: bool = False, solver: str = 'dopri5', solver_options: Optional[Dict] = {}, test_solver: str = None,
+                 test_solver_options: Optional[Dict] = None, set_data: bool = False, rademacher: bool = False, atol: float = 1e-5,
+                 rtol: float = 1e-3, **kwargs):
+        super().__init__()
+        self.T = T
+        self.dim = dim
+        self.odefunc = ODEfunc(net, divergence, rademacher, has_latent, set_data)
+        self.use_adjoint = use_adjoint
+        self.solver = solver
+        self.solver_options = solver_options
+        self.test_solver = test_solver or solver
+        self.test_solver_options = solver_options if test_solver_options is None else test_solver_options
+        self.atol = atol
+        self.rtol = rtol
+        self._trace = ProgramCache()
+        self._last_path = None             # 'kernel' | 'composed': which path the last call took (tests, tools/bench_cnf.py)
+
+    # ---- the grid ---------------------------------------------------------------------------------------------------------------
+    def _solver(self):
+        name = self.solver if self.training else self.test_solver
+        opts = self.solver_options if self.training else self.test_solver_options
+        if name not in FIXED_SOLVERS:
+            raise NotImplementedError(
+                f'stribor_amd: solver {name!r} is not implemented; the implemented solvers are {", ".join(FIXED_SOLVERS)} on a fixed '
+                f"grid -- e.g. solver='rk4', solver_options={{'step_size': 0.05}}")
+        opts = dict(opts or {})
+        step = opts.pop('step_size', None)
+        if opts:
+            raise NotImplementedError(f'stribor_amd: solver options {sorted(opts)} are not implemented (step_size only)')
+        return name, (None if step is None else float(step))
+
+    def _grid(self, reverse: bool):
+        name, step = self._solver()
+        t0, t1 = (self.T, 0.0) if reverse else (0.0, self.T)
+        return name, step, fixed_grid(t0, t1, step)
+
+    # ---- the kernel plan --------------------------------------------------------------------------------------------------------
+    def _kernel_net(self, latent_dim: int, want_ldj: bool, device):
+        """(sx_cnf_net, keep-alive list) for sx_cnf_flow, or None when the ODE function is outside its coverage."""
+        diffeq = self.odefunc.diffeq
+        if type(diffeq) is not DiffeqMLP or type(diffeq.net) is not MLP:
+            return None
+        mlp = diffeq.net
+        if mlp._wrapped or mlp.final_activation_name is not None or _hip.ACT_CODES.get(mlp.activation_name, 99) > 6:
+            return None
+        layers = list(mlp.net)
+        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters (MLP also takes an instance)
+        for m in layers[1::2]:
+            if type(m) is not getattr(nn, mlp.activation_name) or _ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True:
+                return None
+        lins = [m for m in layers if isinstance(m, nn.Linear)]
+        if len(lins) not in (2, 3) or len(layers) != 2 * len(lins) - 1 or any(isinstance(m, nn.Linear) != (i % 2 == 0)
+                                                                              for i, m in enumerate(layers)):
+            return None
+        if not 1 <= self.dim <= _hip.CNF_MAX_DIM or lins[0].in_features != 1 + self.dim + latent_dim or lins[0].in_features > 128:
+            return None
+        if lins[-1].out_features != self.dim or any(l.out_features > 128 for l in lins[:-1]):
+            return None
+        d = _hip.sx_cnf_net()
+        keep = []
+        for i, lin in enumerate(lins):
+            W, b = lin.weight.detach(), (None if lin.bias is None else lin.bias.detach())
+            if W.dtype != torch.float32 or not W.is_contiguous() or W.device != device:
+                return None
+            if b is not None and (b.dtype != torch.float32 or not b.is_contiguous()):
+                return None
+            keep += [W, b]
+            d.layer[i].W, d.layer[i].b = W.data_ptr(), (0 if b is None else b.data_ptr())
+            d.layer[i].out_dim, d.layer[i].in_dim = W.shape
+        d.n_layers, d.dim, d.latent_dim, d.act = len(lins), self.dim, latent_dim, _hip.ACT_CODES[mlp.activation_name]
+        if want_ldj:
+            tc = self._trace_constants([l.weight for l in lins], device)
+            keep.append(tc)
+            d.trace = tc.data_ptr()
+        lds = _hip.lib().sx_cnf_lds_bytes(d, int(want_ldj))
+        if lds == 0 or lds > _hip.CNF_LDS_BYTES:
+            return None
+        return d, keep
+
+    def _trace_constants(self, weights, device):
+        """c / C of `trace_constants` as the kernel reads them: fp32 on the device, C zero-padded to a square of whole tiles.
+        Derived in fp64 with batched torch ops; cached until a weight changes (ProgramCache: (data_ptr, _version) guards and the
+        structure epoch)."""
+        def build():
+            with torch.no_grad():
+                tc = trace_constants([w.detach().to(torch.float64) for w in weights], self.dim)
+                if tc.dim() == 2:
+                    tiles = lambda n: 1 if n <= 32 else 2 if n <= 64 else 4
+                    P = 32 * max(tiles(tc.shape[0]), tiles(tc.shape[1]))
+                    full = torch.zeros(P, P, dtype=torch.float64, device=device)
+                    full[:tc.shape[0], :tc.shape[1]] = tc
+                    tc = full
+                return tc.to(torch.float32).contiguous()
+        return self._trace.get(('trace', str(device)), build, guards=list(weights))
+
+    # ---- the two paths ----------------------------------------------------------------------------------------------------------
+    def _solve_kernel(self, plan, x2, lat2, name, step, grid, want_ldj):
+        d, keep = plan
+        n = x2.shape[0]
+        y = torch.empty_like(x2)
+        ldj = torch.empty(n, dtype=torch.float32, device=x2.device) if want_ldj else None
+        if n:
+            _hip.call('sx_cnf_flow', x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), y.data_ptr(), _hip.ptr(ldj), n,
+                      _hip.CNF_SOLVERS[name], len(grid) - 1, float(grid[0]), float(grid[-1]), float(step or 0.0), int(want_ldj))
+        del keep
+        return y, ldj
+
+    def _solve_composed(self, x, latent, mask, name, grid, keep_graph: bool):
+        """The same grid and tableau as torch ops over the module, on any leading shape -> (y, log-det [..., 1])."""
+        func = self.odefunc
+        func.before_odeint()
+        state = (x, torch.zeros_like(x))
+        if latent is not None:
+            state += (latent,)
+        if mask is not None:
+            state += (mask,)
+        for i in range(len(grid) - 1):
+            inc = _rk_step(func, name, grid[i], grid[i + 1], state)
+            state = tuple(a + b for a, b in zip(state[:2], inc[:2])) + state[2:]
+            if not keep_graph:
+                state = tuple(s.detach() for s in state)
+        return state[0], -state[1].sum(-1, keepdim=True)
+
+    def _composed_reference(self, x, latent=None, mask=None, reverse: bool = False):
+        """The composition path without a graph (tests and tools/bench_cnf.py compare the kernel with it)."""
+        name, step, grid = self._grid(reverse)
+        with torch.no_grad():
+            return self._solve_composed(x.to(torch.float32), latent, mask, name, grid, False)
+
+    def _solve(self, x, latent, mask, reverse: bool, want_ldj: bool):
+        _hip.require_device(x, 'x')
+        name, step, grid = self._grid(reverse)
+        func = self.odefunc
+        out_dtype = x.dtype
+        x = x.to(torch.float32)
+        if latent is not None:
+            latent = latent.to(device=x.device, dtype=torch.float32).expand(*x.shape[:-1], latent.shape[-1])
+        n_evals = (len(grid) - 1) * STAGES[name]
+        graph = graph_wanted(self, x, latent)
+        plan = None
+        if not graph and mask is None and (func.divergence == 'none' or func.exact_trace()):
+            ld = 0 if latent is None else latent.shape[-1]
+            trace = want_ldj and func.divergence != 'none'
+            plan = self._kernel_net(ld, trace, x.device)
+        if plan is not None:
+            x2, lead = flatten_rows(x)
+            lat2 = None if latent is None else flatten_rows(latent)[0]
+            with torch.no_grad():
+                y2, ldj = self._solve_kernel(plan, x2, lat2, name, step, grid, trace)
+                if want_ldj and ldj is None:
+                    ldj = torch.zeros(x2.shape[0], dtype=torch.float32, device=x.device)
+            y = y2.reshape(*lead, self.dim)
+            ldj = None if ldj is None else ldj.reshape(*lead, 1)
+            self._last_path = 'kernel'
+        else:
+            if graph:
+                y, ldj = self._solve_composed(x, latent, mask, name, grid, True)
+            else:
+                with torch.no_grad():
+                    y, ldj = self._solve_composed(x, latent, mask, name, grid, False)
+            self._last_path = 'composed'
+        func._num_evals.fill_(n_evals)
+        if out_dtype == torch.bfloat16:
+            y = y.to(out_dtype)
+        return y, ldj
+
+    # ---- reference method set ---------------------------------------------------------------------------------------------------
+    def forward_and_log_det_jacobian(self, x, latent=None, mask=None, *, reverse=False, **kwargs):
+        return self._solve(x, latent, mask, bool(reverse), True)
+
+    def inverse_and_log_det_jacobian(self, y, latent=None, mask=None, **kwargs):
+        return self._solve(y, latent, mask, True, True)
+
+    def forward(self, x, latent=None, mask=None, **kwargs):
+        return self._solve(x, latent, mask, False, False)[0]
+
+    def inverse(self, y, latent=None, mask=None, **kwargs):
+        return self._solve(y, latent, mask, True, False)[0]
+
+    def log_det_jacobian(self, x, y=None, mask=None, latent=None, **kwargs):
+        return self._solve(x, latent, mask, False, True)[1]
+
+    def _num_evals(self):
+        return self.odefunc._num_evals.item()
+
+    # ---- inside a NormalizingFlow that trains layer by layer ----------------------------------------------------------------
+    def _autograd_supported(self) -> bool:
+        return True
+
+    def _autograd_forward(self, x2, lat2=None):
+        y, ldj = self._solve(x2, lat2, None, False, True)
+        return y, ldj.reshape(-1)
+
+    def _autograd_inverse(self, y2, lat2=None, pre=None):
+        x, ldj = self._solve(y2, lat2, None, True, True)
+        return x, ldj.reshape(-1)

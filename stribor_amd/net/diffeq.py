@@ -1,0 +1,47 @@
+"""Differential-equation nets of the continuous normalizing flow (reference: stribor/net/diffeq.py:13-75).
+
+Same constructors and ``state_dict`` keys (``net.net.0.weight``, ...); ``DiffeqMLP`` builds the product ``net.MLP``, so its
+construction order and RNG draws are the MLP's.  The input columns are [t, x, latent] in this order (diffeq.py:44-47).
+``ContinuousTransform`` does not call a ``DiffeqMLP`` on its kernel path at all: ``sx_cnf_flow`` consumes the weights directly.
+"""
+from abc import ABCMeta, abstractmethod
+from typing import List
+
+import torch
+import torch.nn as nn
+
+from .mlp import MLP
+
+__all__ = ['DiffeqNet', 'DiffeqConcat', 'DiffeqMLP']
+
+
+class DiffeqNet(nn.Module, metaclass=ABCMeta):
+    @abstractmethod
+    def forward(self, t, x, latent=None, **kwargs):
+        ...
+
+
+class DiffeqConcat(DiffeqNet):
+    """dx/dt = net([t, x, latent]) with the scalar time broadcast into a leading column (diffeq.py:25-48)."""
+
+    def __init__(self, net):
+        super().__init__()
+        self.net = net
+
+    def forward(self, t, x, latent=None, **kwargs):
+        cols = [torch.ones_like(x[..., :1]) * t, x]
+        if latent is not None:
+            cols.append(latent)
+        inp = torch.cat(cols, -1)
+        if type(self.net) is MLP and torch.is_grad_enabled():
+            # the divergence differentiates this call, and training differentiates the divergence
+            return self.net.forward_twice_differentiable(inp)
+        return self.net(inp, **kwargs)
+
+
+class DiffeqMLP(DiffeqConcat):
+    """``DiffeqMLP(dim + 1 (+ latent), hidden_dims, dim)`` (diffeq.py:51-75)."""
+
+    def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, activation: str = 'Tanh',
+                 final_activation: str = None, **kwargs):
+        super().__init__(MLP(in_dim, hidden_dims, out_dim, activation, final_activation))

@@ -252,6 +252,11 @@ class MLP(StructureTracked, nn.Module):
             h = layer(h)
         return h
 
+    def forward_twice_differentiable(self, x: torch.Tensor) -> torch.Tensor:
+        """The network through its plain torch layers (library GEMMs): differentiable to any order, where `forward_autograd`'s
+        MFMA ops are differentiable once.  For callers that differentiate a derivative (a CNF's divergence in training)."""
+        return self.net(x)
+
     # -- standalone evaluation ---------------------------------------------------------------------------
     def _program(self, device):
         def build():

@@ -1,0 +1,80 @@
+"""Timing of ContinuousTransform on sx_cnf_flow: the log_prob-direction solve (inverse_and_log_det_jacobian: x and the log-det)
+at dim 2 / [64] and dim 32 / [128, 128], 2^18 rows, rk4 at 16 steps, against the composition path (the same grid as torch ops,
+the divergence by one reverse pass per feature) on the same build.
+
+FLOP count per row and network evaluation: 2 x (dim H1 + H1 H2 + H2 dim) for the forward GEMMs (2 x (dim H + H dim) with one
+hidden layer) plus 2 x H2 H1 for the trace GEMM of two hidden layers; 64 evaluations per solve.  The fraction of peak is against
+157.3 TF (fp32 MFMA).  Times are device events around `REPS` calls.
+
+    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import stribor_amd as st
+
+PEAK_F32_MFMA = 157.3e12
+
+
+def timed(fn, reps, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rows', type=int, default=1 << 18)
+    ap.add_argument('--fallback-rows', type=int, default=1 << 14, help='rows of the composition-path timing (scaled to --rows)')
+    ap.add_argument('--steps', type=int, default=16)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--json', default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'bench_cnf needs a GPU'
+    results = {}
+    for dim, hidden in ((2, [64]), (32, [128, 128])):
+        torch.manual_seed(0)
+        f = st.ContinuousTransform(dim, net=st.net.DiffeqMLP(dim + 1, hidden, dim), divergence='compute', solver='rk4',
+                                   solver_options={'step_size': 1.0 / a.steps}).eval().to('cuda')
+        y = torch.randn(a.rows, dim, device='cuda')
+        ys = y[:a.fallback_rows]
+        widths = [dim] + hidden + [dim]
+        flop_eval = 2 * sum(p * q for p, q in zip(widths[:-1], widths[1:])) + (2 * hidden[0] * hidden[1] if len(hidden) == 2 else 0)
+        evals = 4 * a.steps
+        with torch.no_grad():
+            ms = timed(lambda: f.inverse_and_log_det_jacobian(y), a.reps)
+            assert f._last_path == 'kernel'
+            ms_x = timed(lambda: f.inverse(y), a.reps)
+            fb = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=1) * (a.rows / ys.shape[0])
+            xk, lk = f.inverse_and_log_det_jacobian(ys)
+            xc, lc = f._composed_reference(ys, reverse=True)
+        fl = a.rows * evals * flop_eval
+        key = f'dim{dim}_h{"x".join(map(str, hidden))}'
+        results[key] = {'solve_ldj_ms': ms, 'solve_only_ms': ms_x, 'composed_ms_scaled': fb, 'rows_per_s': a.rows / ms * 1e3,
+                        'tflops': fl / ms / 1e9, 'frac_of_peak': fl / (ms * 1e-3) / PEAK_F32_MFMA, 'composed_over_kernel': fb / ms,
+                        'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item()}
+        r = results[key]
+        print(f'dim {dim} {hidden} N={a.rows} rk4 x {a.steps}: solve + log-det {ms:.2f} ms ({r["rows_per_s"]:.3g} rows/s, '
+              f'{r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path '
+              f'{fb:.0f} ms (timed at {ys.shape[0]} rows, scaled) = {r["composed_over_kernel"]:.0f} x; kernel vs composition max abs '
+              f'x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
+    results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows}
+    if a.json:
+        with open(a.json, 'w') as fh:
+            json.dump(results, fh, indent=1)
+
+
+if __name__ == '__main__':
+    main()
