@@ -29,6 +29,8 @@ from abc import ABCMeta
 from . import _hip
 
 ALLOWED_TILES = (1, 2, 4)
+LOG2E = 1.4426950408889634
+BOUNDARY_DERIVATIVE = 0.5397424172369522      # log(exp(1 - 1e-3) - 1), rational_quadratic_spline.py:81
 
 
 # ---- validity of cached programs -------------------------------------------------------------------------------
@@ -663,6 +665,118 @@ class ProgramBuilder:
         self.blob_floats += n
         return off, n
 
+    # -- the rules every coupling planner shares, one place each ---------------------------------------------------
+    def _step(self, kind: int, off: int, n: int, *, c0=0, ct=0, t0=0, tt=0, reverse=0, act=0, ldj_scale=0.0, ldj_const=0.0,
+              pad_=None) -> None:
+        step = dict(kind=kind, c0=c0, ct=ct, t0=t0, tt=tt, reverse=int(reverse), act=act, blob_off=off, blob_floats=n,
+                    ldj_scale=ldj_scale, ldj_const=ldj_const)
+        if pad_ is not None:
+            step['pad_'] = pad_
+        self.steps.append(step)
+
+    def _hidden_idx(self, width: int, rows=None) -> np.ndarray:
+        """Hidden-tile index list: the first `width` entries = `rows` (default 0 .. width - 1), the padding -1."""
+        idx = np.full(32 * self.h_tiles, -1, dtype=np.int64)
+        idx[:width] = np.arange(width) if rows is None else rows
+        return idx
+
+    def _coupling_slots(self, mask) -> Tuple[np.ndarray, np.ndarray]:
+        """(slot_cond, slot_live): which state slots hold a conditioning / a transformed column under `mask` (padding: neither)."""
+        mask = np.asarray(mask, dtype=np.float64).reshape(-1)
+        if mask.size == 1:
+            mask = np.full(self.dim, mask[0])
+        cond_col, live_col = mask > 0.5, mask <= 0.5
+        if self.dim == 1:
+            cond_col = np.zeros(1, dtype=bool)          # z = z * 0 (coupling.py:62-63, 151-152)
+        ok = self.col_of_slot >= 0
+        col = np.where(ok, self.col_of_slot, 0)
+        return ok & cond_col[col], ok & live_col[col]
+
+    def _cond_variant(self, slot_cond, slot_live, tiles: Optional[int] = None):
+        """(c0, ct, t0, tt) tile ranges: pruned low / high halves when the masks align with the tiles, else dense (any mask, zero
+        weights outside it).  `tiles`: the tiles the choice runs over (backward programs: the x tiles, not the adjoint ones)."""
+        T = self.tiles if tiles is None else tiles
+        half = 16 * T
+        if T >= 2 and self.latent_dim == 0 and self.x_tiles == T:
+            if not slot_cond[half:].any() and not slot_live[:half].any():
+                return 0, T // 2, T // 2, T // 2
+            if not slot_cond[:half].any() and not slot_live[half:].any():
+                return T // 2, T // 2, 0, T // 2
+        return 0, T, 0, T
+
+    def _cond_cols(self, slot_cond, c0: int, ct: int, time_at: Optional[Tuple[int, int]] = None) -> np.ndarray:
+        """GEMM-1 operand: W1's column per slot of tiles [c0, c0 + ct) -- a conditioning slot's own column, behind the data slots
+        the latent columns at D + li (cat([z, latent]), coupling.py:64-65, 153-154) and, for `time_at` = (li, column), the time
+        slot (cat([z, t]), coupling.py:155-156); -1 elsewhere."""
+        p = np.arange(32 * c0, 32 * (c0 + ct))
+        data, li = p < self.n_slots, p - self.n_slots
+        col_idx = np.full(len(p), -1, dtype=np.int64)
+        col_idx[data] = np.where(slot_cond[p[data]], self.col_of_slot[p[data]], -1)
+        latent = (li >= 0) & (li < self.latent_dim)
+        col_idx[latent] = self.dim + li[latent]
+        if time_at is not None:
+            col_idx[li == time_at[0]] = time_at[1]
+        return col_idx
+
+    def _affine_rows(self, slot_live, t0: int, tt: int) -> Tuple[np.ndarray, np.ndarray]:
+        """GEMM-2 operand: per transformed tile of [t0, t0 + tt), 32 log_scale rows then 32 shift rows (affine.py:66; coupling.py:194
+        chunk(2)) -> (row2, ls_col); ls_col = per slot of those tiles its column when transformed, else -1."""
+        p = np.arange(32 * t0, 32 * (t0 + tt))
+        live = p < self.n_slots
+        live[live] = slot_live[p[live]]
+        ls_col = np.full(32 * tt, -1, dtype=np.int64)
+        ls_col[live] = self.col_of_slot[p[live]]
+        sh_col = np.where(ls_col >= 0, self.dim + ls_col, -1)
+        return np.concatenate([ls_col.reshape(tt, 32), sh_col.reshape(tt, 32)], axis=1).reshape(-1), ls_col
+
+    def _folded_tanh(self, reverse: bool, tt: int):
+        """Tanh hot path: fold the constants of tanh(z) = 1 - 2/(exp2(2 log2e z) + 1) and exp(x) = exp2(log2e x)
+        into the packed weights (exact re-parametrisation; fp32 MFMA shares the VALU, so every saved VALU
+        instruction is saved wall time):  hidden r = 1/(exp2(c z) + 1);  W2 tanh + b2 = (-2 W2) r + (b2 + W2 1).
+        -> (rs1, rs2, bs2, kk): row (= bias) scale of GEMM 1, row and bias scales of GEMM 2 over `tt` transformed tiles (the packer
+        adds the folded W2 1: fold_ones = 1), and kk of exp(-ls) / exp(+ls) -> exp2(kk ls); the step's ldj_scale is divided by kk."""
+        kk = (-LOG2E) if reverse else LOG2E
+        rs1 = np.full(32 * self.h_tiles, 2.0 * LOG2E)
+        rs2 = np.tile(np.repeat([-2.0 * kk, -2.0], 32), tt)
+        bs2 = np.tile(np.repeat([kk, 1.0], 32), tt)
+        return rs1, rs2, bs2, kk
+
+    def _hidden_chain(self, linears: Sequence[Tuple], col_idx, c0: int, ct: int, act: int) -> int:
+        """CPL_HIDDEN (state -> hidden), then CPL_HIDDEN2 for every further layer; the hidden activations stay in registers
+        between the steps.  -> width of the last layer."""
+        HT = self.h_tiles
+        prev = None
+        for (W, b) in linears:
+            first = prev is None
+            off, n = self._alloc(_hip.packed_linear_floats(HT, ct if first else HT))
+            self.jobs.append(_PackJob(W, b, self._hidden_idx(W.shape[0]), col_idx if first else self._hidden_idx(prev), HT,
+                                      ct if first else HT, off))
+            if first:
+                self._step(_hip.STEP_CPL_HIDDEN, off, n, c0=c0, ct=ct, act=act)
+            else:
+                self._step(_hip.STEP_CPL_HIDDEN2, off, n, act=act)
+            prev = W.shape[0]
+        return prev
+
+    def _register_order(self):
+        """(blob index t * 32 + h * 16 + r, column | -1) of every data slot, in C-fragment register order."""
+        for t in range(self.x_tiles):
+            for h in range(2):
+                for r in range(16):
+                    yield t * 32 + h * 16 + r, self.col_of_slot[32 * t + _kmap(r, h)]
+
+    def _out_tiles(self, W, b, out_rows, cL: np.ndarray, accumulate: bool, transpose: bool = False) -> None:
+        """One MLP_OUT_TILE step per 32 output columns: column i = row out_rows[i] of W over the hidden columns cL."""
+        out_rows = np.asarray(out_rows, dtype=np.int64)
+        self.mlp_out_dim = len(out_rows)
+        for u in range(_ceil_div(len(out_rows), 32)):
+            r = np.full(32, -1, dtype=np.int64)
+            seg = out_rows[32 * u:32 * u + 32]
+            r[:len(seg)] = seg
+            off, n = self._alloc(_hip.packed_linear_floats(1, self.h_tiles))
+            self.jobs.append(_PackJob(W, b, r, cL, 1, self.h_tiles, off, transpose=transpose))
+            self._step(_hip.STEP_MLP_OUT_TILE, off, n, t0=u, tt=1, reverse=accumulate)
+
     # -- steps -------------------------------------------------------------------------------------
     def add_permutation(self, perm: np.ndarray, reverse: bool) -> None:
         """forward: y[j] = x[perm[j]]; inverse: x[j] = y[inv[j]]  (permute.py:71,75) — a relabelling."""
@@ -677,95 +791,36 @@ class ProgramBuilder:
     def add_coupling_affine(self, W1, b1, W2, b2, mask: np.ndarray, act: int, reverse: bool, ldj_scale: float,
                             hidden: int) -> None:
         self._freeze_input()
-        D, T, HT = self.dim, self.tiles, self.h_tiles
-        mask = np.asarray(mask, dtype=np.float64).reshape(-1)
-        if mask.size == 1:
-            mask = np.full(D, mask[0])
-        cond_col = mask > 0.5
-        if D == 1:
-            cond_col = np.zeros(1, dtype=bool)          # z = z * 0 (coupling.py:62-63)
-        live_col = mask <= 0.5
-        col = self.col_of_slot
-        slot_cond = np.array([c >= 0 and cond_col[c] for c in col])
-        slot_live = np.array([c >= 0 and live_col[c] for c in col])
-        half = 16 * T
-        variant = 'dense'
-        if T >= 2 and self.latent_dim == 0 and self.x_tiles == T:
-            if not slot_cond[half:].any() and not slot_live[:half].any():
-                variant = 'low'
-            elif not slot_cond[:half].any() and not slot_live[half:].any():
-                variant = 'high'
-        if variant == 'low':
-            c0, ct, t0, tt = 0, T // 2, T // 2, T // 2
-        elif variant == 'high':
-            c0, ct, t0, tt = T // 2, T // 2, 0, T // 2
-        else:
-            c0, ct, t0, tt = 0, T, 0, T
-        # GEMM-1 operand: hidden rows x conditioning slots
-        k_slots = np.arange(32 * c0, 32 * (c0 + ct))
-        col_idx = np.full(len(k_slots), -1, dtype=np.int64)
-        for i, p in enumerate(k_slots):
-            if p < self.n_slots:
-                if slot_cond[p]:
-                    col_idx[i] = col[p]
-            else:
-                li = p - self.n_slots
-                if li < self.latent_dim:
-                    col_idx[i] = D + li                    # cat([z, latent]) (coupling.py:64-65)
+        HT = self.h_tiles
+        slot_cond, slot_live = self._coupling_slots(mask)
+        c0, ct, t0, tt = self._cond_variant(slot_cond, slot_live)
+        col_idx = self._cond_cols(slot_cond, c0, ct)
         n1 = _hip.packed_linear_floats(HT, ct)
         n2 = _hip.packed_linear_floats(2 * tt, HT)
         wide = hidden > 32 * HT
-        if (wide or self.wide_state) and (act != _hip.ACT_CODES['Tanh'] or variant == 'dense'):
+        if (wide or self.wide_state) and (act != _hip.ACT_CODES['Tanh'] or ct == self.tiles):
             raise NotImplementedError('hidden layers wider than the program\'s hidden tiles: Tanh conditioners, masks that split the tiles')
-        # Tanh hot path: fold the constants of tanh(z) = 1 - 2/(exp2(2 log2e z) + 1) and exp(x) = exp2(log2e x)
-        # into the packed weights (exact re-parametrisation; fp32 MFMA shares the VALU, so every saved VALU
-        # instruction is saved wall time):  hidden r = 1/(exp2(c z) + 1);  W2 tanh + b2 = (-2 W2) r + (b2 + W2 1).
-        folded = act == _hip.ACT_CODES['Tanh']
-        LOG2E = 1.4426950408889634
-        rs1 = bs1 = rs2 = bs2 = None
+        rs1 = rs2 = bs2 = None
         fold = 0.0
-        if folded:
-            kk = (-LOG2E) if reverse else LOG2E              # exp(-ls) / exp(+ls) -> exp2(kk ls)
-            rs1 = np.full(32 * HT, 2.0 * LOG2E)
-            bs1 = rs1
-            rs2 = np.empty(32 * 2 * tt)
-            bs2 = np.empty(32 * 2 * tt)
-            for t in range(tt):
-                rs2[32 * (2 * t):32 * (2 * t + 1)] = -2.0 * kk
-                bs2[32 * (2 * t):32 * (2 * t + 1)] = kk
-                rs2[32 * (2 * t + 1):32 * (2 * t + 2)] = -2.0
-                bs2[32 * (2 * t + 1):32 * (2 * t + 2)] = 1.0
-            fold = 1.0
-            act = _hip.ACT_TANH_FOLDED
-            ldj_scale = ldj_scale / kk
-        # GEMM-2 operand: per transformed tile, 32 log_scale rows then 32 shift rows (affine.py:66)
-        row2 = np.full(32 * 2 * tt, -1, dtype=np.int64)
-        for t in range(tt):
-            for i in range(32):
-                p = 32 * (t0 + t) + i
-                if p < self.n_slots and slot_live[p]:
-                    row2[32 * (2 * t) + i] = col[p]
-                    row2[32 * (2 * t + 1) + i] = D + col[p]
+        if act == _hip.ACT_CODES['Tanh']:
+            rs1, rs2, bs2, kk = self._folded_tanh(reverse, tt)
+            fold, act, ldj_scale = 1.0, _hip.ACT_TANH_FOLDED, ldj_scale / kk
+        row2, _ = self._affine_rows(slot_live, t0, tt)
         if self.wide_state:
             # eight state tiles: hidden step + one step per transformed tile (sx_flow_kernel.h wide_hidden / wide_affine_tile)
             if wide:
                 raise NotImplementedError('129 .. 256 columns: hidden layers of up to 128 units')
-            row_idx = np.full(32 * HT, -1, dtype=np.int64)
-            row_idx[:hidden] = np.arange(hidden)
-            col2 = np.full(32 * HT, -1, dtype=np.int64)
-            col2[:hidden] = np.arange(hidden)
             off, n = self._alloc(n1)
-            self.jobs.append(_PackJob(W1, b1, row_idx, col_idx, HT, ct, off, rs1, bs1, 0.0))
-            self.steps.append(dict(kind=_hip.STEP_WIDE_HIDDEN, c0=c0, ct=ct, t0=t0, tt=tt, reverse=int(reverse), act=act, blob_off=off,
-                                   blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+            self.jobs.append(_PackJob(W1, b1, self._hidden_idx(hidden), col_idx, HT, ct, off, rs1, rs1, 0.0))
+            self._step(_hip.STEP_WIDE_HIDDEN, off, n, c0=c0, ct=ct, t0=t0, tt=tt, reverse=reverse, act=act)
             nt = _hip.packed_linear_floats(2, HT)
             for t in range(tt):
-                if not (row2[64 * t:64 * t + 64] >= 0).any():
+                tile = slice(64 * t, 64 * t + 64)
+                if not (row2[tile] >= 0).any():
                     continue                              # a tile of padding only
                 off, n = self._alloc(nt)
-                self.jobs.append(_PackJob(W2, b2, row2[64 * t:64 * t + 64], col2, 2, HT, off, rs2[64 * t:64 * t + 64], bs2[64 * t:64 * t + 64], fold))
-                self.steps.append(dict(kind=_hip.STEP_WIDE_AFFINE_TILE, c0=0, ct=0, t0=t0 + t, tt=1, reverse=int(reverse), act=act,
-                                       blob_off=off, blob_floats=n, ldj_scale=ldj_scale, ldj_const=0.0))
+                self.jobs.append(_PackJob(W2, b2, row2[tile], self._hidden_idx(hidden), 2, HT, off, rs2[tile], bs2[tile], fold))
+                self._step(_hip.STEP_WIDE_AFFINE_TILE, off, n, t0=t0 + t, tt=1, reverse=reverse, act=act, ldj_scale=ldj_scale)
             return
         # one step per chunk of 32 HT hidden units (one chunk = the whole layer up to that width).  W2 tanh(W1 z + b1) + b2 is a SUM
         # over hidden-unit chunks: a chunk step evaluates its slice of the hidden layer and adds its share of (log_scale, shift) to
@@ -775,95 +830,36 @@ class ProgramBuilder:
         n_chunks = _ceil_div(hidden, chunk)
         for c in range(n_chunks):
             hsel = np.arange(c * chunk, min(hidden, (c + 1) * chunk))
-            row_idx = np.full(32 * HT, -1, dtype=np.int64)
-            row_idx[:len(hsel)] = hsel
-            col2 = np.full(32 * HT, -1, dtype=np.int64)
-            col2[:len(hsel)] = hsel
             off, n = self._alloc(n1 + n2)
-            self.jobs.append(_PackJob(W1, b1, row_idx, col_idx, HT, ct, off, rs1, bs1, 0.0))
-            self.jobs.append(_PackJob(W2, b2 if c == 0 else None, row2, col2, 2 * tt, HT, off + n1, rs2, bs2, fold))
-            step = dict(kind=_hip.STEP_COUPLING_AFFINE_HC if wide else _hip.STEP_COUPLING_AFFINE, c0=c0, ct=ct, t0=t0, tt=tt,
-                        reverse=int(reverse), act=act, blob_off=off, blob_floats=n, ldj_scale=ldj_scale, ldj_const=0.0)
-            if wide:
-                step['pad_'] = int(c == 0) | (int(c == n_chunks - 1) << 1)
-            self.steps.append(step)
+            self.jobs.append(_PackJob(W1, b1, self._hidden_idx(len(hsel), hsel), col_idx, HT, ct, off, rs1, rs1, 0.0))
+            self.jobs.append(_PackJob(W2, b2 if c == 0 else None, row2, self._hidden_idx(len(hsel), hsel), 2 * tt, HT, off + n1,
+                                      rs2, bs2, fold))
+            self._step(_hip.STEP_COUPLING_AFFINE_HC if wide else _hip.STEP_COUPLING_AFFINE, off, n, c0=c0, ct=ct, t0=t0, tt=tt,
+                       reverse=reverse, act=act, ldj_scale=ldj_scale,
+                       pad_=int(c == 0) | (int(c == n_chunks - 1) << 1) if wide else None)
 
     def add_coupling_affine_deep(self, linears: Sequence[Tuple], mask: np.ndarray, act: int, reverse: bool,
                                  ldj_scale: float) -> None:
         """Affine coupling whose conditioner has two or more hidden layers (linears = [(W1, b1), ..., (W_out, b_out)]):
         CPL_HIDDEN (state -> hidden), CPL_HIDDEN2 for every middle layer, COUPLING_AFFINE_DEEP (last hidden layer,
-        output layer, affine map); the hidden activations stay in registers between the steps."""
+        output layer, affine map)."""
         self._narrow_only('deep conditioners')
         self._freeze_input()
         assert len(linears) >= 3
-        D, T, HT = self.dim, self.tiles, self.h_tiles
+        HT = self.h_tiles
         if max(W.shape[0] for (W, _) in linears[:-1]) > 32 * HT:
             raise NotImplementedError('conditioners with several hidden layers fuse up to 128 units per layer')
-        mask = np.asarray(mask, dtype=np.float64).reshape(-1)
-        if mask.size == 1:
-            mask = np.full(D, mask[0])
-        cond_col = mask > 0.5
-        if D == 1:
-            cond_col = np.zeros(1, dtype=bool)
-        live_col = mask <= 0.5
-        col = self.col_of_slot
-        slot_cond = np.array([c >= 0 and cond_col[c] for c in col])
-        slot_live = np.array([c >= 0 and live_col[c] for c in col])
+        slot_cond, slot_live = self._coupling_slots(mask)
         c0, ct, t0, tt = self._cond_variant(slot_cond, slot_live)
-        k_slots = np.arange(32 * c0, 32 * (c0 + ct))
-        col_idx = np.full(len(k_slots), -1, dtype=np.int64)
-        for i, p in enumerate(k_slots):
-            if p < self.n_slots:
-                if slot_cond[p]:
-                    col_idx[i] = col[p]
-            else:
-                li = p - self.n_slots
-                if li < self.latent_dim:
-                    col_idx[i] = D + li
-
-        def hidden_idx(width):
-            idx = np.full(32 * HT, -1, dtype=np.int64)
-            idx[:width] = np.arange(width)
-            return idx
-
-        (W1, b1) = linears[0]
-        off, n = self._alloc(_hip.packed_linear_floats(HT, ct))
-        self.jobs.append(_PackJob(W1, b1, hidden_idx(W1.shape[0]), col_idx, HT, ct, off))
-        self.steps.append(dict(kind=_hip.STEP_CPL_HIDDEN, c0=c0, ct=ct, t0=0, tt=0, reverse=0, act=act, blob_off=off,
-                               blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
-        prev = W1.shape[0]
-        for (Wk, bk) in linears[1:-2]:
-            off, n = self._alloc(_hip.packed_linear_floats(HT, HT))
-            self.jobs.append(_PackJob(Wk, bk, hidden_idx(Wk.shape[0]), hidden_idx(prev), HT, HT, off))
-            self.steps.append(dict(kind=_hip.STEP_CPL_HIDDEN2, c0=0, ct=0, t0=0, tt=0, reverse=0, act=act, blob_off=off,
-                                   blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
-            prev = Wk.shape[0]
+        prev = self._hidden_chain(linears[:-2], self._cond_cols(slot_cond, c0, ct), c0, ct, act)
         (WL, bL), (Wo, bo) = linears[-2], linears[-1]
         n1 = _hip.packed_linear_floats(HT, HT)
         n2 = _hip.packed_linear_floats(2 * tt, HT)
         off, n = self._alloc(n1 + n2)
-        self.jobs.append(_PackJob(WL, bL, hidden_idx(WL.shape[0]), hidden_idx(prev), HT, HT, off))
-        row2 = np.full(32 * 2 * tt, -1, dtype=np.int64)
-        for t in range(tt):
-            for i in range(32):
-                p = 32 * (t0 + t) + i
-                if p < self.n_slots and slot_live[p]:
-                    row2[32 * (2 * t) + i] = col[p]                 # log_scale rows, then shift rows (affine.py:66)
-                    row2[32 * (2 * t + 1) + i] = D + col[p]
-        self.jobs.append(_PackJob(Wo, bo, row2, hidden_idx(WL.shape[0]), 2 * tt, HT, off + n1))
-        self.steps.append(dict(kind=_hip.STEP_COUPLING_AFFINE_DEEP, c0=0, ct=0, t0=t0, tt=tt, reverse=int(reverse),
-                               act=act, blob_off=off, blob_floats=n, ldj_scale=ldj_scale, ldj_const=0.0))
-
-    def _cond_variant(self, slot_cond, slot_live):
-        """(c0, ct, t0, tt) tile ranges: pruned low / high halves when the masks align with the tiles, else dense."""
-        T = self.tiles
-        half = 16 * T
-        if T >= 2 and self.latent_dim == 0 and self.x_tiles == T:
-            if not slot_cond[half:].any() and not slot_live[:half].any():
-                return 0, T // 2, T // 2, T // 2
-            if not slot_cond[:half].any() and not slot_live[half:].any():
-                return T // 2, T // 2, 0, T // 2
-        return 0, T, 0, T
+        self.jobs.append(_PackJob(WL, bL, self._hidden_idx(WL.shape[0]), self._hidden_idx(prev), HT, HT, off))
+        row2, _ = self._affine_rows(slot_live, t0, tt)
+        self.jobs.append(_PackJob(Wo, bo, row2, self._hidden_idx(WL.shape[0]), 2 * tt, HT, off + n1))
+        self._step(_hip.STEP_COUPLING_AFFINE_DEEP, off, n, t0=t0, tt=tt, reverse=reverse, act=act, ldj_scale=ldj_scale)
 
     def add_coupling_rqs(self, W1, b1, W2, b2, mask: np.ndarray, reverse: bool, ldj_scale: float, hidden: int,
                          n_bins: int, left: float, right: float, bottom: float, top: float, middle=(), cubic: bool = False) -> None:
@@ -874,71 +870,33 @@ class ProgramBuilder:
         two boundary derivatives; phase steps with act = 1, kernel MODE 12 / 13)."""
         self._narrow_only('spline couplings')
         self._freeze_input()
-        D, T, HT, K = self.dim, self.tiles, self.h_tiles, n_bins
+        HT, K = self.h_tiles, n_bins
         if max([hidden] + [Wk.shape[0] for (Wk, _) in middle]) > 32 * HT:
             raise NotImplementedError('spline couplings fuse with hidden layers of up to 128 units')
         if K > (16 if cubic else 32):
             raise NotImplementedError('fused spline coupling supports n_bins <= 16 (cubic) / 32 (rational-quadratic)')
         P = 2 * K + 2 if cubic else 3 * K - 1
-        mask = np.asarray(mask, dtype=np.float64).reshape(-1)
-        if mask.size == 1:
-            mask = np.full(D, mask[0])
-        cond_col = mask > 0.5
-        if D == 1:
-            cond_col = np.zeros(1, dtype=bool)
-        live_col = mask <= 0.5
         col = self.col_of_slot
-        slot_cond = np.array([c >= 0 and cond_col[c] for c in col])
-        slot_live = np.array([c >= 0 and live_col[c] for c in col])
+        slot_cond, slot_live = self._coupling_slots(mask)
         c0, ct, t0, tt = self._cond_variant(slot_cond, slot_live)
-        LOG2E = 1.4426950408889634
-        # hidden layer (folded tanh: r = 1/(exp2(2 log2e z) + 1))
-        k_slots = np.arange(32 * c0, 32 * (c0 + ct))
-        col_idx = np.full(len(k_slots), -1, dtype=np.int64)
-        for i, p in enumerate(k_slots):
-            if p < self.n_slots:
-                if slot_cond[p]:
-                    col_idx[i] = col[p]
-            else:
-                li = p - self.n_slots
-                if li < self.latent_dim:
-                    col_idx[i] = D + li
-        def hidden_idx(width):
-            idx = np.full(32 * HT, -1, dtype=np.int64)
-            idx[:width] = np.arange(width)
-            return idx
-
+        col_idx = self._cond_cols(slot_cond, c0, ct)
+        # last hidden layer (folded tanh: r = 1/(exp2(2 log2e z) + 1)); pad_ bits 8..: the layer's ordinal (side outputs of a
+        # whole-flow program), bit 0: its source = the hidden state kept by the CPL_HIDDEN steps
         sc = np.full(32 * HT, 2.0 * LOG2E)
         if not middle:
             off, n = self._alloc(_hip.packed_linear_floats(HT, ct))
-            self.jobs.append(_PackJob(W1, b1, hidden_idx(hidden), col_idx, HT, ct, off, sc, sc, 0.0))
-            step = dict(kind=_hip.STEP_RQS_HIDDEN, c0=c0, ct=ct, t0=t0, tt=tt, reverse=int(reverse),
-                        act=_hip.ACT_TANH_FOLDED, blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0)
-            step['pad_'] = self._spline_layers << 8          # the layer's ordinal (side outputs of a whole-flow program)
-            self.steps.append(step)
+            self.jobs.append(_PackJob(W1, b1, self._hidden_idx(hidden), col_idx, HT, ct, off, sc, sc, 0.0))
+            self._step(_hip.STEP_RQS_HIDDEN, off, n, c0=c0, ct=ct, t0=t0, tt=tt, reverse=reverse, act=_hip.ACT_TANH_FOLDED,
+                       pad_=self._spline_layers << 8)
         else:
-            tanh = _hip.ACT_CODES['Tanh']
-            off, n = self._alloc(_hip.packed_linear_floats(HT, ct))
-            self.jobs.append(_PackJob(W1, b1, hidden_idx(W1.shape[0]), col_idx, HT, ct, off))
-            self.steps.append(dict(kind=_hip.STEP_CPL_HIDDEN, c0=c0, ct=ct, t0=0, tt=0, reverse=0, act=tanh, blob_off=off,
-                                   blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
-            prev = W1.shape[0]
-            for (Wk, bk) in middle[:-1]:
-                off, n = self._alloc(_hip.packed_linear_floats(HT, HT))
-                self.jobs.append(_PackJob(Wk, bk, hidden_idx(Wk.shape[0]), hidden_idx(prev), HT, HT, off))
-                self.steps.append(dict(kind=_hip.STEP_CPL_HIDDEN2, c0=0, ct=0, t0=0, tt=0, reverse=0, act=tanh,
-                                       blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
-                prev = Wk.shape[0]
+            prev = self._hidden_chain([(W1, b1)] + list(middle[:-1]), col_idx, c0, ct, _hip.ACT_CODES['Tanh'])
             WL, bL = middle[-1]
             hidden = WL.shape[0]
             off, n = self._alloc(_hip.packed_linear_floats(HT, HT))
-            self.jobs.append(_PackJob(WL, bL, hidden_idx(hidden), hidden_idx(prev), HT, HT, off, sc, sc, 0.0))
-            step = dict(kind=_hip.STEP_RQS_HIDDEN, c0=0, ct=0, t0=t0, tt=tt, reverse=int(reverse),
-                        act=_hip.ACT_TANH_FOLDED, blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0)
-            step['pad_'] = 1 | (self._spline_layers << 8)    # 1: source = the hidden state kept by the CPL_HIDDEN steps
-            self.steps.append(step)
-        col2 = np.full(32 * HT, -1, dtype=np.int64)
-        col2[:hidden] = np.arange(hidden)
+            self.jobs.append(_PackJob(WL, bL, self._hidden_idx(hidden), self._hidden_idx(prev), HT, HT, off, sc, sc, 0.0))
+            self._step(_hip.STEP_RQS_HIDDEN, off, n, t0=t0, tt=tt, reverse=reverse, act=_hip.ACT_TANH_FOLDED,
+                       pad_=1 | (self._spline_layers << 8))
+        col2 = self._hidden_idx(hidden)
         # forward searches the widths on [left, right], inverse the heights on [bottom, top]
         blocks = [(K, K, bottom, top), (0, K, left, right)] if reverse else [(0, K, left, right), (K, K, bottom, top)]
         blocks.append((2 * K, 2, left, right) if cubic else (2 * K, K - 1, 0.0, 0.0))      # cubic: the evaluation needs the domain
@@ -995,7 +953,7 @@ class ProgramBuilder:
                             # always at least one -- at the boundary-derivative constant log(exp(1 - 1e-3) - 1) of
                             # rational_quadratic_spline.py:81 (D[K - 1] then needs no select).
                             # Bias block of the pack: [tile][lane half][register] behind the 4 x HT fragment tiles.
-                            first, pad = (K, -1e30) if phase < 2 else (K - 1, 0.5397424172369522)
+                            first, pad = (K, -1e30) if phase < 2 else (K - 1, BOUNDARY_DERIVATIVE)
                             for qi, q in enumerate(elems):
                                 for h in range(2):
                                     if slot_live[32 * t + q + 8 * g + 4 * h]:
@@ -1008,10 +966,8 @@ class ProgramBuilder:
                                             pad_off += list(range(base + first, base + 16))
                                             pad_val += [pad] * (16 - first)
                         s_scale = (-ldj_scale if reverse else ldj_scale) if phase == 2 else 0.0
-                        step = dict(kind=_hip.STEP_RQS_PHASE, c0=g, ct=phase, t0=t, tt=K, reverse=int(reverse),
-                                    act=int(cubic) | (half << 1), blob_off=off, blob_floats=n, ldj_scale=s_scale, ldj_const=0.0)
-                        step['pad_'] = live_mask - (1 << 32) if live_mask >= (1 << 31) else live_mask
-                        self.steps.append(step)
+                        self._step(_hip.STEP_RQS_PHASE, off, n, c0=g, ct=phase, t0=t, tt=K, reverse=reverse, act=int(cubic) | (half << 1),
+                                   ldj_scale=s_scale, pad_=live_mask - (1 << 32) if live_mask >= (1 << 31) else live_mask)
 
         if pad_off:
             self.jobs.append(_PadJob(W2, np.asarray(pad_off, dtype=np.int64), np.asarray(pad_val, dtype=np.float32)))
@@ -1031,67 +987,35 @@ class ProgramBuilder:
         kernel's per-row factors into weight gradients."""
         self._narrow_only('backward programs')
         self._freeze_input()
-        XT = self.x_tiles
+        XT, HT = self.x_tiles, self.h_tiles
         assert self.tiles == 2 * XT
-        D, HT = self.dim, self.h_tiles
         if hidden > 32 * HT:         # (h_tiles of a builder for > 128 hidden units is the forward's chunk width: no backward chunk steps)
             raise NotImplementedError(f'backward programs hold hidden layers of up to {32 * HT} units')
-        mask = np.asarray(mask, dtype=np.float64).reshape(-1)
-        if mask.size == 1:
-            mask = np.full(D, mask[0])
-        cond_col, live_col = mask > 0.5, mask <= 0.5
-        if D == 1:
-            cond_col = np.zeros(1, dtype=bool)
-        col = self.col_of_slot
-        slot_cond = np.array([c >= 0 and cond_col[c] for c in col])
-        slot_live = np.array([c >= 0 and live_col[c] for c in col])
-        half = 16 * XT
-        if XT >= 2 and not slot_cond[half:].any() and not slot_live[:half].any():
-            c0, ct, t0, tt = 0, XT // 2, XT // 2, XT // 2
-        elif XT >= 2 and not slot_cond[:half].any() and not slot_live[half:].any():
-            c0, ct, t0, tt = XT // 2, XT // 2, 0, XT // 2
-        else:
-            c0, ct, t0, tt = 0, XT, 0, XT                     # dense: any mask, zero weights outside it
-        LOG2E = 1.4426950408889634
-        kk = -LOG2E                                              # log_prob direction: scale = exp(-log_scale)
-        col_idx = np.array([col[p] if slot_cond[p] else -1 for p in range(32 * c0, 32 * (c0 + ct))], dtype=np.int64)
-        row_h = np.full(32 * HT, -1, dtype=np.int64)
-        row_h[:hidden] = np.arange(hidden)
-        row2 = np.full(64 * tt, -1, dtype=np.int64)
-        for t in range(tt):
-            for i in range(32):
-                p = 32 * (t0 + t) + i
-                if slot_live[p]:
-                    row2[64 * t + i] = col[p]
-                    row2[64 * t + 32 + i] = D + col[p]
+        slot_cond, slot_live = self._coupling_slots(mask)
+        c0, ct, t0, tt = self._cond_variant(slot_cond, slot_live, XT)
+        col_idx = self._cond_cols(slot_cond, c0, ct)
+        row_h = self._hidden_idx(hidden)
+        row2, _ = self._affine_rows(slot_live, t0, tt)
+        rs1, rs2, bs2, _ = self._folded_tanh(True, tt)           # log_prob direction: scale = exp(-log_scale)
         n1, n2 = _hip.packed_linear_floats(HT, ct), _hip.packed_linear_floats(2 * tt, HT)
         n3, n4 = _hip.packed_linear_floats(HT, 2 * tt), _hip.packed_linear_floats(ct, HT)
-        rs1 = np.full(32 * HT, 2.0 * LOG2E)
-        rs2 = np.concatenate([np.concatenate([np.full(32, -2.0 * kk), np.full(32, -2.0)]) for _ in range(tt)])
-        bs2 = np.concatenate([np.concatenate([np.full(32, kk), np.full(32, 1.0)]) for _ in range(tt)])
         if XT == 4:
             # 128-column flows: the four operands (100 KB) do not fit the double-buffered LDS ring together -> two steps, the
             # forward operands (BWD_A) and the transposed ones (BWD_B); halves only (a dense mask would need 8 x 8 tiles)
             if (ct, tt) != (2, 2):
                 raise NotImplementedError('backward of 128-column couplings: conditioner / transformed columns must be the tile halves')
-            offa, na = self._alloc(n1 + n2)
-            self.jobs.append(_PackJob(W1, b1, row_h, col_idx, HT, ct, offa, rs1, rs1, 0.0))
-            self.jobs.append(_PackJob(W2, b2, row2, row_h, 2 * tt, HT, offa + n1, rs2, bs2, 1.0))
-            offb, nb = self._alloc(n3 + n4)
-            self.jobs.append(_PackJob(W2, None, row_h, row2, HT, 2 * tt, offb, transpose=True))            # W2^T
-            self.jobs.append(_PackJob(W1, None, col_idx, row_h, ct, HT, offb + n3, transpose=True))        # W1^T
-            for kind, off, n in ((_hip.STEP_COUPLING_AFFINE_BWD_A, offa, na), (_hip.STEP_COUPLING_AFFINE_BWD_B, offb, nb)):
-                self.steps.append(dict(kind=kind, c0=c0, ct=ct, t0=t0, tt=layer_slot, reverse=1, act=_hip.ACT_TANH_FOLDED,
-                                       blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
-            return dict(kind='coupling', cond_cols=col_idx, out_rows=row2, hidden=hidden, ct=ct, tt=tt,
-                        side_width=32 * ct + 64 * HT + 64 * tt)
-        off, n = self._alloc(n1 + n2 + n3 + n4)
-        self.jobs.append(_PackJob(W1, b1, row_h, col_idx, HT, ct, off, rs1, rs1, 0.0))
-        self.jobs.append(_PackJob(W2, b2, row2, row_h, 2 * tt, HT, off + n1, rs2, bs2, 1.0))
-        self.jobs.append(_PackJob(W2, None, row_h, row2, HT, 2 * tt, off + n1 + n2, transpose=True))      # W2^T
-        self.jobs.append(_PackJob(W1, None, col_idx, row_h, ct, HT, off + n1 + n2 + n3, transpose=True))  # W1^T
-        self.steps.append(dict(kind=_hip.STEP_COUPLING_AFFINE_BWD, c0=c0, ct=ct, t0=t0, tt=layer_slot, reverse=1,
-                               act=_hip.ACT_TANH_FOLDED, blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+            (offa, na), (offb, nb) = self._alloc(n1 + n2), self._alloc(n3 + n4)
+            steps = ((_hip.STEP_COUPLING_AFFINE_BWD_A, offa, na), (_hip.STEP_COUPLING_AFFINE_BWD_B, offb, nb))
+        else:
+            offa, na = self._alloc(n1 + n2 + n3 + n4)
+            offb = offa + n1 + n2
+            steps = ((_hip.STEP_COUPLING_AFFINE_BWD, offa, na),)
+        self.jobs.append(_PackJob(W1, b1, row_h, col_idx, HT, ct, offa, rs1, rs1, 0.0))
+        self.jobs.append(_PackJob(W2, b2, row2, row_h, 2 * tt, HT, offa + n1, rs2, bs2, 1.0))
+        self.jobs.append(_PackJob(W2, None, row_h, row2, HT, 2 * tt, offb, transpose=True))            # W2^T
+        self.jobs.append(_PackJob(W1, None, col_idx, row_h, ct, HT, offb + n3, transpose=True))        # W1^T
+        for kind, off, n in steps:
+            self._step(kind, off, n, c0=c0, ct=ct, t0=t0, tt=layer_slot, reverse=1, act=_hip.ACT_TANH_FOLDED)
         return dict(kind='coupling', cond_cols=col_idx, out_rows=row2, hidden=hidden, ct=ct, tt=tt,
                     side_width=32 * ct + 64 * HT + 64 * tt)
 
@@ -1110,8 +1034,7 @@ class ProgramBuilder:
         for c0, fn, t0, rev in ((0, fn_fwd, 4, 0), (4, fn_adj, 0, 1)):
             off, n = self._alloc(n_lin)
             self.jobs.append(_DerivedLinearJob(sources, fn, [(col, col, XT, off, XT)]))
-            self.steps.append(dict(kind=_hip.STEP_LINEAR_BWD, c0=c0, ct=XT, t0=t0, tt=layer_slot, reverse=rev, act=0,
-                                   blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+            self._step(_hip.STEP_LINEAR_BWD, off, n, c0=c0, ct=XT, t0=t0, tt=layer_slot, reverse=rev)
         return dict(kind='dense', slot_cols=col, side_width=256)
 
     def add_affine_const(self, log_scale, shift, reverse: bool, ldj_scale: float) -> None:
@@ -1119,16 +1042,12 @@ class ProgramBuilder:
         D, T = self.dim, self.tiles
         off, n = self._alloc(2 * 32 * T)
         gather = np.full(2 * 32 * T, 2 * D, dtype=np.int64)    # index 2D = the appended zero
-        for t in range(self.x_tiles):
-            for h in range(2):
-                for r in range(16):
-                    c = self.col_of_slot[32 * t + _kmap(r, h)]
-                    if c >= 0:
-                        gather[t * 32 + h * 16 + r] = c
-                        gather[(T + t) * 32 + h * 16 + r] = D + c
+        for i, c in self._register_order():
+            if c >= 0:
+                gather[i] = c
+                gather[32 * T + i] = D + c
         self.jobs.append(_ConstJob(log_scale, shift, D, gather, off))
-        self.steps.append(dict(kind=_hip.STEP_AFFINE_CONST, c0=0, ct=0, t0=0, tt=T, reverse=int(reverse), act=0,
-                               blob_off=off, blob_floats=n, ldj_scale=ldj_scale, ldj_const=0.0))
+        self._step(_hip.STEP_AFFINE_CONST, off, n, tt=T, reverse=reverse, ldj_scale=ldj_scale)
 
     def add_coupling_time(self, W1, b1, W2, b2, mask: np.ndarray, act: int, reverse: bool, ldj_scale: float, hidden: int,
                           time_col: Optional[int], time_sel: int, time_net) -> None:
@@ -1145,26 +1064,8 @@ class ProgramBuilder:
         XT = next(c for c in (max(T // 4, 1), max(T // 2, 1), T) if c >= _ceil_div(D, 32))
         if time_sel >= self.time_slots and time_col is not None:
             raise NotImplementedError('time coupling: no slot for this time')
-        mask = np.asarray(mask, dtype=np.float64).reshape(-1)
-        if mask.size == 1:
-            mask = np.full(D, mask[0])
-        cond_col, live_col = mask > 0.5, mask <= 0.5
-        if D == 1:
-            cond_col = np.zeros(1, dtype=bool)                # coupling.py:151-152
-        col = self.col_of_slot
-        col_idx = np.full(32 * T, -1, dtype=np.int64)
-        for p in range(32 * T):
-            if p < self.n_slots:
-                if col[p] >= 0 and cond_col[col[p]]:
-                    col_idx[p] = col[p]
-            else:
-                li = p - self.n_slots
-                if li < L:
-                    col_idx[p] = D + li                       # cat([z, latent]) (coupling.py:153-154)
-                elif li == L + time_sel and time_col is not None:
-                    col_idx[p] = time_col                     # cat([z, t]) (coupling.py:155-156)
-        row_idx = np.full(32 * HT, -1, dtype=np.int64)
-        row_idx[:hidden] = np.arange(hidden)
+        slot_cond, slot_live = self._coupling_slots(mask)
+        col_idx = self._cond_cols(slot_cond, 0, T, None if time_col is None else (L + time_sel, time_col))
         kind = int(time_net.kind)
         K = int(time_net.hidden_dim) if kind == 4 else 0
         if kind == 4 and not (1 <= K <= 64):
@@ -1173,40 +1074,18 @@ class ProgramBuilder:
         n2 = _hip.packed_linear_floats(2 * XT, HT)
         n3 = 0 if kind == 0 else (XT * K * 128 if kind == 4 else XT * 64)
         off, n = self._alloc(n1 + n2 + n3)
-        folded = act == _hip.ACT_CODES['Tanh']
-        LOG2E = 1.4426950408889634
-        rs1 = bs1 = rs2 = bs2 = None
+        rs1 = rs2 = bs2 = None
         fold = 0.0
-        if folded:                                            # as add_coupling_affine: tanh's and exp's constants live in the weights
-            kk = (-LOG2E) if reverse else LOG2E
-            rs1 = np.full(32 * HT, 2.0 * LOG2E)
-            bs1 = rs1
-            rs2, bs2 = np.empty(64 * XT), np.empty(64 * XT)
-            for t in range(XT):
-                rs2[64 * t:64 * t + 32], bs2[64 * t:64 * t + 32] = -2.0 * kk, kk
-                rs2[64 * t + 32:64 * t + 64], bs2[64 * t + 32:64 * t + 64] = -2.0, 1.0
-            fold = 1.0
-            act = _hip.ACT_TANH_FOLDED
-            ldj_scale = ldj_scale / kk
-        self.jobs.append(_PackJob(W1, b1, row_idx, col_idx, HT, T, off, rs1, bs1, 0.0))
-        row2 = np.full(64 * XT, -1, dtype=np.int64)
-        ls_col = np.full(32 * XT, -1, dtype=np.int64)         # per data slot: its column when transformed (else -1)
-        for t in range(XT):
-            for i in range(32):
-                p = 32 * t + i
-                if p < self.n_slots and col[p] >= 0 and live_col[col[p]]:
-                    row2[64 * t + i] = col[p]                 # log_scale rows, then shift rows (coupling.py:194 chunk(2))
-                    row2[64 * t + 32 + i] = D + col[p]
-                    ls_col[p] = col[p]
-        col2 = np.full(32 * HT, -1, dtype=np.int64)
-        col2[:hidden] = np.arange(hidden)
-        self.jobs.append(_PackJob(W2, b2, row2, col2, 2 * XT, HT, off + n1, rs2, bs2, fold))
+        if act == _hip.ACT_CODES['Tanh']:
+            rs1, rs2, bs2, kk = self._folded_tanh(reverse, XT)
+            fold, act, ldj_scale = 1.0, _hip.ACT_TANH_FOLDED, ldj_scale / kk
+        self.jobs.append(_PackJob(W1, b1, self._hidden_idx(hidden), col_idx, HT, T, off, rs1, rs1, 0.0))
+        row2, ls_col = self._affine_rows(slot_live, 0, XT)
+        self.jobs.append(_PackJob(W2, b2, row2, self._hidden_idx(hidden), 2 * XT, HT, off + n1, rs2, bs2, fold))
         if kind != 0:
             self.jobs.append(_TimeConstJob(time_net, kind, K, D, XT, ls_col, off + n1 + n2))
-        step = dict(kind=_hip.STEP_COUPLING_TIME, c0=0, ct=T, t0=0, tt=XT, reverse=int(reverse), act=act, blob_off=off,
-                    blob_floats=n, ldj_scale=ldj_scale, ldj_const=0.0)
-        step['pad_'] = kind | (int(time_sel) << 8) | (K << 16)
-        self.steps.append(step)
+        self._step(_hip.STEP_COUPLING_TIME, off, n, ct=T, tt=XT, reverse=reverse, act=act, ldj_scale=ldj_scale,
+                   pad_=kind | (int(time_sel) << 8) | (K << 16))
 
     def add_pointwise(self, kind: int, param: float, log_slope: float, ldj_coeff: float) -> None:
         """One point-wise flow on the data columns (sigmoid.py:9-56, activations.py:11-101): `kind` = the sx_pointwise kind for the
@@ -1216,37 +1095,31 @@ class ProgramBuilder:
         T = self.tiles
         off, n = self._alloc(32 * T + 1)
         vals = np.zeros(32 * T + 1, dtype=np.float64)
-        for t in range(self.x_tiles):
-            for h in range(2):
-                for r in range(16):
-                    if self.col_of_slot[32 * t + _kmap(r, h)] >= 0:
-                        vals[t * 32 + h * 16 + r] = 1.0
+        for i, c in self._register_order():
+            if c >= 0:
+                vals[i] = 1.0
         vals[32 * T] = log_slope
         self.jobs.append(_ScalarsJob(vals, off))
-        self.steps.append(dict(kind=_hip.STEP_POINTWISE, c0=0, ct=0, t0=0, tt=T, reverse=0, act=int(kind), blob_off=off,
-                               blob_floats=n, ldj_scale=float(ldj_coeff), ldj_const=float(param)))
+        self._step(_hip.STEP_POINTWISE, off, n, tt=T, act=int(kind), ldj_scale=float(ldj_coeff), ldj_const=float(param))
 
     def add_linear(self, sources, fn, ldj_fn=None) -> None:
         """y = W . x + b on the data columns (W, b = fn(device), torch Linear layout [out, in]): one LINEAR_TILE step
         for the whole layer; ldj_fn(device) -> its log-det term (0-dim tensor, signed and scaled) or None for 0."""
         self._narrow_only('dense linear layers')
         self._freeze_input()
-        D, T = self.dim, self.tiles
+        T, XT = self.tiles, self.x_tiles
         col = self.col_of_slot
         col_idx = np.full(32 * T, -1, dtype=np.int64)
         col_idx[:self.n_slots] = col                       # input slot -> W column (= logical column)
-        XT = self.x_tiles
         # the whole layer in ONE step (all output slabs, one barrier / one weight refill; at most 4 x 4 tiles = 64 KiB,
         # which fits the LDS ring twice): act = number of slabs
         row_idx = col[:32 * XT].copy()                     # output slot keeps its logical column
         n_lin = _hip.packed_linear_floats(XT, T)
         off, n = self._alloc(n_lin + 1)                    # + the log-det term behind the bias
-        targets = [(row_idx, col_idx, T, off, XT)]
-        self.steps.append(dict(kind=_hip.STEP_LINEAR_TILE, c0=0, ct=T, t0=0, tt=1, reverse=0, act=XT, blob_off=off,
-                               blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+        self._step(_hip.STEP_LINEAR_TILE, off, n, ct=T, tt=1, act=XT)
         if ldj_fn is None:
             ldj_fn = lambda dev: torch.zeros((), dtype=torch.float32, device=dev)
-        self.jobs.append(_DerivedLinearJob(sources, fn, targets, ldj_fn, off + n_lin))
+        self.jobs.append(_DerivedLinearJob(sources, fn, [(row_idx, col_idx, T, off, XT)], ldj_fn, off + n_lin))
 
     def add_row_scale_exp(self, diag, reverse: bool, ldj_scale: float, log_time: bool, t_const: float) -> None:
         """state *= exp(+-diag * t_row) (MatrixExponential with a per-row time, affine.py:263)."""
@@ -1255,16 +1128,12 @@ class ProgramBuilder:
         T = self.tiles
         off, n = self._alloc(32 * T)
         gather = np.full(32 * T, self.dim, dtype=np.int64)      # index dim = appended zero
-        for t in range(self.x_tiles):
-            for h in range(2):
-                for r in range(16):
-                    c = self.col_of_slot[32 * t + _kmap(r, h)]
-                    if c >= 0:
-                        gather[t * 32 + h * 16 + r] = c
+        for i, c in self._register_order():
+            if c >= 0:
+                gather[i] = c
         self.jobs.append(_VectorJob(diag, self.dim, gather, off))
-        self.steps.append(dict(kind=_hip.STEP_ROW_SCALE_EXP, c0=0, ct=0, t0=0, tt=T, reverse=int(reverse),
-                               act=int(log_time), blob_off=off, blob_floats=n, ldj_scale=ldj_scale,
-                               ldj_const=float(t_const)))
+        self._step(_hip.STEP_ROW_SCALE_EXP, off, n, tt=T, reverse=reverse, act=int(log_time), ldj_scale=ldj_scale,
+                   ldj_const=float(t_const))
 
     def add_mlp(self, linears: Sequence[Tuple], act: int, in_cols_live: Optional[np.ndarray],
                 out_rows: np.ndarray, hidden_rows: Optional[np.ndarray] = None, accumulate: bool = False,
@@ -1301,36 +1170,17 @@ class ProgramBuilder:
         #  program has no chunk steps -- its caller splits single-hidden-layer conditioners itself, deeper ones take the next tier)
         if max([h_prev] + [W.shape[0] for (W, _) in linears[1:-1]]) > 32 * HT:
             raise NotImplementedError(f'MLP programs hold hidden layers of up to {32 * HT} units here')
-        row_idx = np.full(32 * HT, -1, dtype=np.int64)
-        row_idx[:h_prev] = hsel
         off, n = self._alloc(_hip.packed_linear_floats(HT, T))
-        self.jobs.append(_PackJob(W0, b0, row_idx, col_idx, HT, T, off))
-        self.steps.append(dict(kind=_hip.STEP_MLP_HIDDEN, c0=0, ct=T, t0=0, tt=0, reverse=0, act=act, blob_off=off,
-                               blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+        self.jobs.append(_PackJob(W0, b0, self._hidden_idx(h_prev, hsel), col_idx, HT, T, off))
+        self._step(_hip.STEP_MLP_HIDDEN, off, n, ct=T, act=act)
         for (W, b) in linears[1:-1]:
-            h_cur = W.shape[0]
-            r = np.full(32 * HT, -1, dtype=np.int64)
-            r[:h_cur] = np.arange(h_cur)
-            c = np.full(32 * HT, -1, dtype=np.int64)
-            c[:h_prev] = np.arange(h_prev)
             off, n = self._alloc(_hip.packed_linear_floats(HT, HT))
-            self.jobs.append(_PackJob(W, b, r, c, HT, HT, off))
-            self.steps.append(dict(kind=_hip.STEP_MLP_HIDDEN2, c0=0, ct=0, t0=0, tt=0, reverse=0, act=act,
-                                   blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
-            h_prev = h_cur
+            self.jobs.append(_PackJob(W, b, self._hidden_idx(W.shape[0]), self._hidden_idx(h_prev), HT, HT, off))
+            self._step(_hip.STEP_MLP_HIDDEN2, off, n, act=act)
+            h_prev = W.shape[0]
         WL, bL = linears[-1]
-        out_rows = np.asarray(out_rows, dtype=np.int64)
-        self.mlp_out_dim = len(out_rows)
-        cL = np.full(32 * HT, -1, dtype=np.int64)
-        cL[:h_prev] = hsel if hidden_rows is not None else np.arange(h_prev)
-        for u in range(_ceil_div(len(out_rows), 32)):
-            r = np.full(32, -1, dtype=np.int64)
-            seg = out_rows[32 * u:32 * u + 32]
-            r[:len(seg)] = seg
-            off, n = self._alloc(_hip.packed_linear_floats(1, HT))
-            self.jobs.append(_PackJob(WL, None if accumulate else bL, r, cL, 1, HT, off))
-            self.steps.append(dict(kind=_hip.STEP_MLP_OUT_TILE, c0=0, ct=0, t0=u, tt=1, reverse=int(accumulate), act=0,
-                                   blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+        cL = self._hidden_idx(h_prev, None if hidden_rows is None else hsel)
+        self._out_tiles(WL, None if accumulate else bL, out_rows, cL, accumulate)
 
     def add_single_linear(self, W, b, out_rows: np.ndarray, transpose: bool = False, k0: int = 0, accumulate: bool = False) -> None:
         """ONE nn.Linear as a program (round 6, VERDICT r5 #7: the layer-wise training path's `F.linear` / `gy @ W` were library
@@ -1344,20 +1194,9 @@ class ProgramBuilder:
         T, HT = self.tiles, self.h_tiles
         assert T <= HT and self.latent_dim == 0, (T, HT)
         off, n = self._alloc(256)
-        self.steps.append(dict(kind=_hip.STEP_MLP_INPUT, c0=0, ct=T, t0=0, tt=0, reverse=0, act=0, blob_off=off, blob_floats=n,
-                               ldj_scale=0.0, ldj_const=0.0))
-        out_rows = np.asarray(out_rows, dtype=np.int64)
-        self.mlp_out_dim = len(out_rows)
-        cL = np.full(32 * HT, -1, dtype=np.int64)
-        cL[:self.n_slots] = np.where(self.col_of_slot >= 0, self.col_of_slot + k0, -1)
-        for u in range(_ceil_div(len(out_rows), 32)):
-            r = np.full(32, -1, dtype=np.int64)
-            seg = out_rows[32 * u:32 * u + 32]
-            r[:len(seg)] = seg
-            off, n = self._alloc(_hip.packed_linear_floats(1, HT))
-            self.jobs.append(_PackJob(W, b, r, cL, 1, HT, off, transpose=transpose))
-            self.steps.append(dict(kind=_hip.STEP_MLP_OUT_TILE, c0=0, ct=0, t0=u, tt=1, reverse=int(accumulate), act=0,
-                                   blob_off=off, blob_floats=n, ldj_scale=0.0, ldj_const=0.0))
+        self._step(_hip.STEP_MLP_INPUT, off, n, ct=T)
+        cL = self._hidden_idx(self.n_slots, np.where(self.col_of_slot >= 0, self.col_of_slot + k0, -1))
+        self._out_tiles(W, b, out_rows, cL, accumulate, transpose)
 
     # -- finish ------------------------------------------------------------------------------------
     def build(self, device: torch.device) -> CompiledProgram:
