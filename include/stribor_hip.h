@@ -721,6 +721,50 @@ size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj);
 int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                 int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- exact-trace continuous normalizing flow (ContinuousTransform with divergence='exact' over DiffeqExactTraceMLP:
+ * stribor/net/diffeq_exact_trace.py:48-72, diffeq_zero_trace.py:14-56, made.py, diagjac.py) ----
+ * f_i = g(t, x_i, h_i, latent) with h = MADE_1(x) + MADE_2(x) (d_h values per dimension, dh_i/dx_i = 0) and g one MLP shared by
+ * every dimension; jac_i = dg/dx_i at fixed h_i is the Jacobian diagonal exactly.  The same solvers, grid and roundings as
+ * sx_cnf_flow.  The caller stages everything the kernel keeps in LDS into ONE image (mask * weight: the kernel never sees a mask):
+ * tiles of 1024 floats in A-fragment order -- tile (m, c) of an MT x KT image at float (m * KT + c) * 1024, float
+ * g * 256 + lane * 4 + j of it = Wp[32m + (lane & 31)][32c + kmap(4g + j, lane >> 5)], kmap(r, h) = (r & 3) + 8 (r >> 2) + 4h --
+ * over matrices Wp padded with zeros and indexed by POSITIONS:
+ *   state / first MADE layer input   dimension i at position kmap(i, 0)
+ *   hidden units                     unit j at position j;  HT = 1 (every hidden width <= 32) or 2 tiles
+ *   MADE output                      column kk * dim + i (slot kk < d_h of dimension i) at position 32 (kk >> 1) + kmap(i, kk & 1);
+ *                                    OT = 1 (d_h <= 2), 2 (d_h <= 4) or 4 tiles
+ *   dimwise first layer input        x_i at position kmap(0, 0) = 0, slot kk at position kmap(1 + (kk >> 1), kk & 1)
+ * and vectors of 32 floats per tile indexed by the same positions.  Order of the image, sizes in floats:
+ *   for e in MADE_1, MADE_2:  W1 [HT x 1 tiles], b1 [32 HT], (two hidden layers: W2 [HT x HT tiles], b2 [32 HT],)
+ *                             W_last [OT x HT tiles], b_last [32 OT]
+ *   dimwise:  W1 [HT x 1 tiles], b1 [32 HT], W1[:, 0] (time) [32 HT], W1[:, 1] (x) [32 HT], (W2 [HT x HT tiles], b2 [32 HT],)
+ *             w_last [32 HT], b_last [32: the first float] */
+#define SX_CNF_EXACT_MAX_DIM    16
+#define SX_CNF_EXACT_MAX_DH     8
+#define SX_CNF_EXACT_MAX_LATENT 64
+#define SX_CNF_EXACT_MAX_HIDDEN 64
+typedef struct {
+    const float *image;     /* device, 16-byte aligned: the LDS image above                                             */
+    const float *w_latent;  /* device, 16-byte aligned: the dimwise W1[:, 2 + d_h ..], row-major [32 HT][32 ceil(latent_dim / 32)],
+                               zero-padded; NULL iff latent_dim == 0                                                     */
+    int32_t image_floats;   /* must equal sx_cnf_exact_lds_bytes / 4                                                    */
+    int32_t dim;            /* 1..SX_CNF_EXACT_MAX_DIM                                                                  */
+    int32_t d_h;            /* 1..SX_CNF_EXACT_MAX_DH                                                                   */
+    int32_t latent_dim;     /* 0..SX_CNF_EXACT_MAX_LATENT                                                               */
+    int32_t n_hidden;       /* 1 or 2 hidden layers, the same widths in both MADEs and the dimwise net                 */
+    int32_t hidden[2];      /* 1..SX_CNF_EXACT_MAX_HIDDEN each                                                          */
+    int32_t act;            /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU, the same in the three nets                          */
+} sx_cnf_exact_net;
+
+/* Bytes of the LDS image of this network (at most SX_CNF_LDS_BYTES inside the coverage); 0 for a network outside the coverage. */
+size_t sx_cnf_exact_lds_bytes(const sx_cnf_exact_net *net_host);
+
+/* The arguments of sx_cnf_flow: x, y fp32 [n_rows, dim] (may alias), latent fp32 [n_rows, latent_dim] or NULL, ldj fp32 [n_rows]
+ * (written iff want_ldj): the integral of sum_i jac_i with the solver's tableau and signed dt.  want_ldj == 0 skips the tangent.
+ * Exact fp32 arithmetic (v_mfma_f32_32x32x2_f32) in every set_gemm_precision mode. */
+int sx_cnf_exact_flow(const sx_cnf_exact_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                      int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
+
 /* ---- multi-head attention core (stribor/net/attention.py:8-49 with util/safe_softmax.py:3-14) ---------------------------------
  * q [R, Nq, E], k / v [R, Nk, E]: element (r, n, e) at base + r * bs + n * rs + e (unit column stride; bs = 0 broadcasts one
  * [N, E] block over R).  n_heads heads of width dh = E / n_heads (1..SX_ATTENTION_MAX_HEAD_DIM), scale (1 / dh) ** 0.5

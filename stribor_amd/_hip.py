@@ -60,7 +60,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
-           'sx_cnf_flow']
+           'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
@@ -121,6 +121,11 @@ class sx_cnf_layer(C.Structure):
 class sx_cnf_net(C.Structure):
     _fields_ = [('layer', sx_cnf_layer * 3), ('n_layers', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32),
                 ('trace', C.c_void_p)]
+
+
+class sx_cnf_exact_net(C.Structure):
+    _fields_ = [('image', C.c_void_p), ('w_latent', C.c_void_p), ('image_floats', C.c_int32), ('dim', C.c_int32), ('d_h', C.c_int32),
+                ('latent_dim', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 2), ('act', C.c_int32)]
 
 
 class sx_attention_args(C.Structure):
@@ -252,6 +257,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_lds_bytes.argtypes = [C.POINTER(sx_cnf_net), i32]
     lib.sx_cnf_flow.restype = i32
     lib.sx_cnf_flow.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_exact_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_exact_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_net)]
+    lib.sx_cnf_exact_flow.restype = i32
+    lib.sx_cnf_exact_flow.argtypes = [C.POINTER(sx_cnf_exact_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

@@ -10,6 +10,11 @@ vectors and the log-det accumulator stay in registers for the whole grid, the we
 from a closed form whose weight-only constants (``trace_constants``) are derived once in fp64.  Everything else -- other nets,
 ``mask``, ``set_data``, the Hutchinson estimator of training mode, and every call that has to build a graph -- runs the same grid
 and tableau as a loop of torch ops over the module (``_solve_composed``); gradients are those of the discretised steps.
+
+``divergence='exact'`` over a ``net.DiffeqExactTraceMLP`` (two MADEs + a dimwise MLP, one or two hidden layers of <= 64 units,
+dim <= 16, d_h <= 8, latent <= 64) is ONE launch of ``sx_cnf_exact_flow`` under the same conditions: the masked weights are staged
+into the kernel's LDS image once (cached, guarded on weights and masks) and the Jacobian diagonal is a forward-mode tangent beside the
+value.  Any other net under 'exact' runs the composition path over ``net.FuncAndDiagJac``.
 """
 import ctypes
 from typing import Dict, Optional
@@ -21,6 +26,7 @@ import torch.nn as nn
 from .. import _hip
 from ..flow import Transform, flatten_rows, graph_wanted
 from ..fused import ProgramCache
+from ..net import diffeq_exact_trace as exact_trace
 from ..net.diffeq import DiffeqMLP
 from ..net.mlp import MLP
 from ..util.divergence import divergence_approx, divergence_exact, divergence_exact_for_sets
@@ -256,14 +262,41 @@ class ContinuousTransform(Transform):
                 return tc.to(torch.float32).contiguous()
         return self._trace.get(('trace', str(device)), build, guards=list(weights))
 
+    def _exact_kernel_net(self, latent_dim: int, device):
+        """(sx_cnf_exact_net, keep-alive list) for sx_cnf_exact_flow, or None when the ODE function is outside its coverage."""
+        s = exact_trace.kernel_coverage(self.odefunc.diffeq, self.dim, latent_dim)
+        if s is None:
+            return None
+        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
+        if any(_ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True for m in s['activations']):
+            return None
+        guards = exact_trace.kernel_tensors(s)
+        if any(g.dtype != torch.float32 or g.device != device for g in guards):
+            return None
+
+        def build():
+            image, w_latent = exact_trace.kernel_image(s)
+            image = torch.from_numpy(image).to(device)
+            return image, (None if w_latent is None else torch.from_numpy(w_latent).contiguous().to(device))
+        image, w_latent = self._trace.get(('exact', str(device)), build, guards=guards)
+        d = _hip.sx_cnf_exact_net()
+        d.image, d.w_latent, d.image_floats = image.data_ptr(), (0 if w_latent is None else w_latent.data_ptr()), image.numel()
+        d.dim, d.d_h, d.latent_dim, d.n_hidden, d.act = self.dim, s['d_h'], latent_dim, len(s['hidden']), _hip.ACT_CODES[s['act']]
+        for i, w in enumerate(s['hidden']):
+            d.hidden[i] = w
+        lds = _hip.lib().sx_cnf_exact_lds_bytes(d)
+        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * image.numel():
+            return None
+        return d, [image, w_latent]
+
     # ---- the two paths ----------------------------------------------------------------------------------------------------------
-    def _solve_kernel(self, plan, x2, lat2, name, step, grid, want_ldj):
+    def _solve_kernel(self, plan, x2, lat2, name, step, grid, want_ldj, entry='sx_cnf_flow'):
         d, keep = plan
         n = x2.shape[0]
         y = torch.empty_like(x2)
         ldj = torch.empty(n, dtype=torch.float32, device=x2.device) if want_ldj else None
         if n:
-            _hip.call('sx_cnf_flow', x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), y.data_ptr(), _hip.ptr(ldj), n,
+            _hip.call(entry, x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), y.data_ptr(), _hip.ptr(ldj), n,
                       _hip.CNF_SOLVERS[name], len(grid) - 1, float(grid[0]), float(grid[-1]), float(step or 0.0), int(want_ldj))
         del keep
         return y, ldj
@@ -300,16 +333,19 @@ class ContinuousTransform(Transform):
             latent = latent.to(device=x.device, dtype=torch.float32).expand(*x.shape[:-1], latent.shape[-1])
         n_evals = (len(grid) - 1) * STAGES[name]
         graph = graph_wanted(self, x, latent)
-        plan = None
+        plan, entry = None, 'sx_cnf_flow'
         if not graph and mask is None and (func.divergence == 'none' or func.exact_trace()):
             ld = 0 if latent is None else latent.shape[-1]
             trace = want_ldj and func.divergence != 'none'
             plan = self._kernel_net(ld, trace, x.device)
+        elif not graph and mask is None and func.divergence == 'exact' and not func.set_data:
+            trace, entry = want_ldj, 'sx_cnf_exact_flow'
+            plan = self._exact_kernel_net(0 if latent is None else latent.shape[-1], x.device)
         if plan is not None:
             x2, lead = flatten_rows(x)
             lat2 = None if latent is None else flatten_rows(latent)[0]
             with torch.no_grad():
-                y2, ldj = self._solve_kernel(plan, x2, lat2, name, step, grid, trace)
+                y2, ldj = self._solve_kernel(plan, x2, lat2, name, step, grid, trace, entry)
                 if want_ldj and ldj is None:
                     ldj = torch.zeros(x2.shape[0], dtype=torch.float32, device=x.device)
             y = y2.reshape(*lead, self.dim)

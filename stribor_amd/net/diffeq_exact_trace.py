@@ -1,0 +1,259 @@
+"""Differential-equation nets with a closed-form Jacobian diagonal (reference: stribor/net/diffeq_exact_trace.py:12-72): for
+``ContinuousTransform(..., divergence='exact')``.
+
+``DiffeqExactTrace(exclusive_net, dimwise_net)``: f_i = dimwise_net(t, x_i, h_i, latent) with h = exclusive_net(t, x) hollow, so
+df_i/dx_i = d dimwise_net / d x_i at fixed h_i -- one pass for the divergence instead of one reverse pass per dimension.  The
+general evaluation is ``net.FuncAndDiagJac`` (any two modules, any device, a graph).  ``DiffeqExactTraceMLP`` is the MLP instance
+(two MADEs + a ``DiffeqMLP``); same constructors and ``state_dict`` keys as the reference (``exclusive_net.net1.net.0.{weight,bias,
+mask}``, ``dimwise_net.net.net.0.weight``), construction order net1, net2, dimwise net.
+
+For the MLP instance this module also holds what ``sx_cnf_exact_flow`` consumes: ``kernel_image`` stages ``mask * weight`` and the
+dimwise weights into the kernel's LDS image (include/stribor_hip.h), and ``closed_form`` is the same arithmetic as torch ops --
+value and forward-mode tangent side by side, no autograd -- in any dtype (tests hold it to ``autograd.functional.jacobian``).
+"""
+from typing import List
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from ..util.flatten_params import flatten_params
+from .diagjac import FuncAndDiagJac
+from .diffeq import DiffeqMLP
+from .diffeq_zero_trace import DiffeqZeroTraceMLP
+from .made import MADE, MaskedLinear
+from .mlp import MLP
+
+__all__ = ['DiffeqExactTrace', 'DiffeqExactTraceMLP']
+
+MAX_DIM, MAX_DH, MAX_LATENT, MAX_HIDDEN = 16, 8, 64, 64          # sx_cnf_exact_flow's coverage (SX_CNF_EXACT_MAX_*)
+
+
+class DiffeqExactTrace(nn.Module):
+    """forward(t [1], x [..., D], latent [..., L] | None) -> (f, Jacobian diagonal), or f alone with return_log_det_jac=False."""
+
+    def __init__(self, exclusive_net, dimwise_net, return_log_det_jac: bool = True, **kwargs):
+        super().__init__()
+        self.exclusive_net = exclusive_net
+        self.dimwise_net = dimwise_net
+        self.return_log_det_jac = return_log_det_jac
+
+    def forward(self, t, x, latent=None, **kwargs):
+        params = flatten_params(self.exclusive_net, self.dimwise_net)
+        y, jac = FuncAndDiagJac.apply(self.exclusive_net, self.dimwise_net, t, x, latent, params)
+        return (y, jac) if self.return_log_det_jac else y
+
+
+class DiffeqExactTraceMLP(DiffeqExactTrace):
+    """``DiffeqExactTraceMLP(dim, hidden_dims, dim, d_h, latent_dim)``: exclusive net DiffeqZeroTraceMLP(dim, hidden_dims, d_h * dim),
+    dimwise net DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1) over the columns [t, x_i, h_i, latent]."""
+
+    def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, d_h: int, latent_dim: int = 0, return_log_det_jac: bool = True,
+                 **kwargs):
+        exclusive_net = DiffeqZeroTraceMLP(in_dim, hidden_dims, d_h * out_dim, return_log_det_jac=False, return_per_dim=True)
+        dimwise_net = DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1)
+        super().__init__(exclusive_net, dimwise_net, return_log_det_jac)
+
+
+# ---- the MLP instance, layer by layer ---------------------------------------------------------------------------------------------
+_ACTS = {'Identity': (lambda v: v, lambda a: torch.ones_like(a)),
+         'Tanh': (torch.tanh, lambda a: 1 - a * a),
+         'ReLU': (torch.relu, lambda a: (a > 0).to(a.dtype)),
+         'Sigmoid': (torch.sigmoid, lambda a: a * (1 - a)),
+         'ELU': (nn.functional.elu, lambda a: torch.where(a > 0, torch.ones_like(a), a + 1)),
+         'Softplus': (nn.functional.softplus, lambda a: 1 - torch.exp(-a)),
+         'LeakyReLU': (nn.functional.leaky_relu, lambda a: torch.where(a > 0, torch.ones_like(a), torch.full_like(a, 0.01)))}
+
+
+def _structure(net):
+    """The layers of a DiffeqExactTraceMLP-shaped module -> dict, or None when it is not the plain instance: two MADEs without a final
+    activation, a DiffeqMLP over a plain MLP without one, one activation name and the same hidden widths in all three."""
+    if type(net.exclusive_net) is not DiffeqZeroTraceMLP or type(net.dimwise_net) is not DiffeqMLP or type(net.dimwise_net.net) is not MLP:
+        return None
+    mades = [net.exclusive_net.net1, net.exclusive_net.net2]
+    mlp = net.dimwise_net.net
+    if any(type(m) is not MADE or m.final_activation is not None for m in mades) or mlp._wrapped or mlp.final_activation_name is not None:
+        return None
+    act = mlp.activation_name
+    stacks = [list(m.net) for m in mades] + [list(mlp.net)]
+    for stack, kind in zip(stacks, (MaskedLinear, MaskedLinear, nn.Linear)):
+        if len(stack) % 2 != 1 or any(not isinstance(l, kind) for l in stack[0::2]):
+            return None
+        if any(type(a) is not getattr(nn, act, None) for a in stack[1::2]):
+            return None
+    if any(m.activation != act for m in mades):
+        return None
+    lins = [stack[0::2] for stack in stacks]
+    hidden = [l.out_features for l in lins[2][:-1]]
+    if any([l.out_features for l in ls[:-1]] != hidden for ls in lins[:2]):
+        return None
+    D = lins[0][0].in_features
+    if lins[1][0].in_features != D or lins[2][-1].out_features != 1:
+        return None
+    out = lins[0][-1].out_features
+    if out % D or lins[1][-1].out_features != out:
+        return None
+    d_h = out // D
+    L = lins[2][0].in_features - 2 - d_h
+    if L < 0:
+        return None
+    return {'D': D, 'd_h': d_h, 'L': L, 'hidden': hidden, 'act': act, 'made': lins[:2], 'dimwise': lins[2],
+            'activations': [a for stack in stacks for a in stack[1::2]]}
+
+
+def closed_form(net, t, x, latent=None, want_jac: bool = True, dtype=None):
+    """(f, jac) of a plain DiffeqExactTraceMLP by its closed form, as torch ops without autograd, in `dtype` (default: x's):
+        h     = MADE_1(x) + MADE_2(x)                           (mask * weight)
+        z_1   = W1[:, 0] t + W1[:, 1] x_i + W1[:, 2:2+d_h] h_i + W1[:, 2+d_h:] latent + b1,   tau_1 = act'(z_1) * W1[:, 1]
+        z_l   = W_l act(z_{l-1}) + b_l,                                                       tau_l = act'(z_l) * (W_l tau_{l-1})
+        f_i   = w_last . act(z_last) + b_last,                                                jac_i = w_last . tau_last
+    (act' from the activation's OUTPUT, as the kernel takes it).  This is what sx_cnf_exact_flow evaluates per stage."""
+    s = _structure(net)
+    if s is None or s['act'] not in _ACTS or not s['hidden']:
+        raise NotImplementedError('closed_form: a plain DiffeqExactTraceMLP with hidden layers and an activation of the kernel\'s set')
+    act, dact = _ACTS[s['act']]
+    dtype = dtype or x.dtype
+    D, d_h = s['D'], s['d_h']
+    cast = lambda p: None if p is None else p.detach().to(device=x.device, dtype=dtype)
+    x = x.detach().to(dtype)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, D)
+    raw = 0
+    for lins in s['made']:
+        a = x2
+        for i, l in enumerate(lins):
+            a = nn.functional.linear(a, cast(l.mask) * cast(l.weight), cast(l.bias))
+            if i + 1 < len(lins):
+                a = act(a)
+        raw = raw + a
+    h = raw.reshape(-1, d_h, D).transpose(-1, -2)                     # [N, D, d_h]: column kk * D + i -> [i, kk]
+    dw = s['dimwise']
+    W1, b1 = cast(dw[0].weight), cast(dw[0].bias)
+    tt = (t.detach() if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).to(device=x.device, dtype=dtype).reshape(())
+    z = x2.unsqueeze(-1) * W1[:, 1] + h @ W1[:, 2:2 + d_h].t() + tt * W1[:, 0]
+    if b1 is not None:
+        z = z + b1
+    if latent is not None:
+        lat2 = latent.detach().to(dtype).reshape(-1, latent.shape[-1])
+        z = z + (lat2 @ W1[:, 2 + d_h:].t()).unsqueeze(-2)
+    a = act(z)
+    tau = dact(a) * W1[:, 1] if want_jac else None
+    for l in dw[1:-1]:
+        W, b = cast(l.weight), cast(l.bias)
+        a_next = act(nn.functional.linear(a, W, b))
+        if want_jac:
+            tau = dact(a_next) * (tau @ W.t())
+        a = a_next
+    wl, bl = cast(dw[-1].weight)[0], cast(dw[-1].bias)
+    f = a @ wl + (0 if bl is None else bl[0])
+    jac = (tau @ wl).reshape(*lead, D) if want_jac else None
+    return f.reshape(*lead, D), jac
+
+
+# ---- the kernel's LDS image -------------------------------------------------------------------------------------------------------
+def _kmap(r, h):
+    return (r & 3) + 8 * (r >> 2) + 4 * h
+
+
+def _tiles(n: int) -> int:
+    return 1 if n <= 32 else 2
+
+
+def _out_tiles(d_h: int) -> int:
+    return 1 if d_h <= 2 else 2 if d_h <= 4 else 4
+
+
+_E = np.arange(1024)
+_TILE_ROW = (_E >> 2) & 31
+_TILE_COL = _kmap(4 * (_E >> 8) + (_E & 3), (_E >> 7) & 1)          # lane = (e >> 2) & 63, its upper half = bit 7 of e
+
+
+def _fragment_image(Wp: np.ndarray) -> np.ndarray:
+    """A zero-padded position-space matrix [32 MT, 32 KT] -> its MT x KT tiles of 1024 floats in A-fragment order."""
+    MT, KT = Wp.shape[0] // 32, Wp.shape[1] // 32
+    tiles = [Wp[32 * m + _TILE_ROW, 32 * c + _TILE_COL] for m in range(MT) for c in range(KT)]
+    return np.concatenate(tiles).astype(np.float32)
+
+
+def kernel_coverage(net, dim: int, latent_dim: int):
+    """The structure dict of `net` when sx_cnf_exact_flow covers it for rows of `dim` features and `latent_dim` latent columns, else
+    None."""
+    from .. import _hip
+    if type(net) is not DiffeqExactTraceMLP or not net.return_log_det_jac:
+        return None
+    s = _structure(net)
+    if s is None or s['D'] != dim or s['L'] != latent_dim:
+        return None
+    if not 1 <= dim <= MAX_DIM or not 1 <= s['d_h'] <= MAX_DH or latent_dim > MAX_LATENT:
+        return None
+    if len(s['hidden']) not in (1, 2) or any(not 1 <= w <= MAX_HIDDEN for w in s['hidden']):
+        return None
+    if _hip.ACT_CODES.get(s['act'], 99) > 6:
+        return None
+    return s
+
+
+def kernel_tensors(s):
+    """Every tensor the image is made of: the cache guards (weights, biases AND masks)."""
+    ts = []
+    for lins in s['made']:
+        for l in lins:
+            ts += [l.weight, l.mask] + ([] if l.bias is None else [l.bias])
+    for l in s['dimwise']:
+        ts += [l.weight] + ([] if l.bias is None else [l.bias])
+    return ts
+
+
+def kernel_image(s):
+    """-> (image [floats] fp32 numpy, w_latent [32 HT, 32 LT] fp32 numpy | None): the layout of include/stribor_hip.h
+    (sx_cnf_exact_net).  The masks are multiplied in HERE: a weight entry under a zero mask never reaches the kernel."""
+    D, d_h, L, hidden = s['D'], s['d_h'], s['L'], s['hidden']
+    HT, OT, NH = max(_tiles(w) for w in hidden), _out_tiles(d_h), len(hidden)
+    npy = lambda p: p.detach().cpu().numpy().astype(np.float32)
+    pos_x = _kmap(np.arange(D), 0)
+    cols = np.arange(d_h * D)
+    pos_raw = 32 * ((cols // D) >> 1) + _kmap(cols % D, (cols // D) & 1)
+    kk = np.arange(d_h)
+    pos_in = _kmap(1 + (kk >> 1), kk & 1)
+    parts = []
+
+    def vec(n_tiles, pos, values):
+        v = np.zeros(32 * n_tiles, np.float32)
+        if values is not None:
+            v[pos] = values
+        parts.append(v)
+
+    def mat(mt, kt, rpos, cpos, W):
+        Wp = np.zeros((32 * mt, 32 * kt), np.float32)
+        Wp[np.ix_(rpos, cpos)] = W
+        parts.append(_fragment_image(Wp))
+
+    for lins in s['made']:
+        in_pos = pos_x
+        for i, l in enumerate(lins):
+            last = i + 1 == len(lins)
+            out_pos = pos_raw if last else np.arange(l.out_features)
+            W = npy(l.mask) * npy(l.weight)
+            W = np.where(npy(l.mask) != 0, W, np.float32(0))          # (0 * inf is not 0)
+            mat(OT if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W)
+            vec(OT if last else HT, out_pos, None if l.bias is None else npy(l.bias))
+            in_pos = out_pos
+    dw = s['dimwise']
+    W1 = npy(dw[0].weight)
+    h1 = np.arange(W1.shape[0])
+    mat(HT, 1, h1, np.concatenate([[0], pos_in]), W1[:, 1:2 + d_h])
+    vec(HT, h1, None if dw[0].bias is None else npy(dw[0].bias))
+    vec(HT, h1, W1[:, 0])
+    vec(HT, h1, W1[:, 1])
+    if NH == 2:
+        W2 = npy(dw[1].weight)
+        mat(HT, HT, np.arange(W2.shape[0]), h1, W2)
+        vec(HT, np.arange(W2.shape[0]), None if dw[1].bias is None else npy(dw[1].bias))
+    wl = npy(dw[-1].weight)
+    vec(HT, np.arange(wl.shape[1]), wl[0])
+    vec(1, np.arange(1), None if dw[-1].bias is None else npy(dw[-1].bias))
+    w_latent = None
+    if L:
+        w_latent = np.zeros((32 * HT, 32 * ((L + 31) // 32)), np.float32)
+        w_latent[:W1.shape[0], :L] = W1[:, 2 + d_h:]
+    return np.concatenate(parts), w_latent

@@ -6,6 +6,11 @@ FLOP count per row and network evaluation: 2 x (dim H1 + H1 H2 + H2 dim) for the
 hidden layer) plus 2 x H2 H1 for the trace GEMM of two hidden layers; 64 evaluations per solve.  The fraction of peak is against
 157.3 TF (fp32 MFMA).  Times are device events around `REPS` calls.
 
+The exact-trace line: divergence='exact' over DiffeqExactTraceMLP(8, [64, 64], 8, d_h = 4) on sx_cnf_exact_flow, the same grid and row
+count, against its composition path (FuncAndDiagJac: one autograd.grad with a graph per evaluation).  FLOPs per row and evaluation:
+the two MADEs 2 x 2 (D H1 + H1 H2 + H2 d_h D), and per dimension the dimwise net 2 (1 + d_h) H1 + 2 H1 H2 + 2 H2 for the value and
+2 H1 H2 + 2 H2 for the tangent (the latent-free case; padding to tiles of 32 is not counted).
+
     python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json]
 """
 import argparse
@@ -70,6 +75,31 @@ def main():
               f'{r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path '
               f'{fb:.0f} ms (timed at {ys.shape[0]} rows, scaled) = {r["composed_over_kernel"]:.0f} x; kernel vs composition max abs '
               f'x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
+    # the exact-trace net
+    torch.manual_seed(0)
+    D, d_h, hidden = 8, 4, [64, 64]
+    f = st.ContinuousTransform(D, net=st.net.DiffeqExactTraceMLP(D, hidden, D, d_h), divergence='exact', solver='rk4',
+                               solver_options={'step_size': 1.0 / a.steps}).eval().to('cuda')
+    y = torch.randn(a.rows, D, device='cuda')
+    ys = y[:a.fallback_rows]
+    H1, H2 = hidden
+    flop_eval = 4 * (D * H1 + H1 * H2 + H2 * d_h * D) + D * (2 * (1 + d_h) * H1 + 4 * H1 * H2 + 4 * H2)
+    with torch.no_grad():
+        ms = timed(lambda: f.inverse_and_log_det_jacobian(y), a.reps)
+        assert f._last_path == 'kernel'
+        ms_x = timed(lambda: f.inverse(y), a.reps)
+        fb = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=1) * (a.rows / ys.shape[0])
+        xk, lk = f.inverse_and_log_det_jacobian(ys)
+        xc, lc = f._composed_reference(ys, reverse=True)
+    fl = a.rows * 4 * a.steps * flop_eval
+    r = results[f'exact_dim{D}_dh{d_h}_h{"x".join(map(str, hidden))}'] = {
+        'solve_ldj_ms': ms, 'solve_only_ms': ms_x, 'composed_ms_scaled': fb, 'rows_per_s': a.rows / ms * 1e3, 'tflops': fl / ms / 1e9,
+        'frac_of_peak': fl / (ms * 1e-3) / PEAK_F32_MFMA, 'composed_over_kernel': fb / ms,
+        'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item()}
+    print(f'exact trace dim {D} d_h {d_h} {hidden} N={a.rows} rk4 x {a.steps}: solve + log-det {ms:.2f} ms ({r["rows_per_s"]:.3g} rows/s, '
+          f'{r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path '
+          f'{fb:.0f} ms (timed at {ys.shape[0]} rows, scaled) = {r["composed_over_kernel"]:.1f} x; kernel vs composition max abs '
+          f'x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
     results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows}
     if a.json:
         with open(a.json, 'w') as fh:
