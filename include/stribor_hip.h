@@ -765,6 +765,51 @@ size_t sx_cnf_exact_lds_bytes(const sx_cnf_exact_net *net_host);
 int sx_cnf_exact_flow(const sx_cnf_exact_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                       int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- continuous normalizing flow over sets (ContinuousTransform with set_data=True or divergence='compute_set' over DiffeqDeepset:
+ * stribor/net/diffeq.py:78-94 around net/equivariant.py's EquivariantNet) ----
+ * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  Equivariant layer l is
+ *   z_l,i = A_l h_i + G_l sum_j h_j + bias_l      (j over the set of row i; layer 0 reads the columns [t, x, latent])
+ * with A_l the layer's l1 weight, G_l its l2 weight / N and bias_l = l1.bias + l2.bias / N: G, bias, w0 and the trace constants are
+ * derived by the caller (in fp64, rounded once).  The log-det is the integral of the divergence of the whole set's dynamics, kept
+ * per element: tr_i = sum over the features of row i of d f / d x at that feature (its sum over a set is the set's divergence).
+ * The same solvers, grid and roundings as sx_cnf_flow; exact fp32 (v_mfma_f32_32x32x2_f32). */
+#define SX_CNF_SET_MAX_DIM    32
+#define SX_CNF_SET_MAX_IN     64        /* 1 + dim + latent_dim                                                         */
+#define SX_CNF_SET_MAX_HIDDEN 64
+#define SX_CNF_SET_MAX_SIZE   128
+typedef struct {
+    const float *A[3];      /* l1 weights, [out_dim, in_dim] row-major                                                  */
+    const float *G[3];      /* l2 weights / set_size, the same shapes                                                   */
+    const float *bias[3];   /* l1.bias + l2.bias / set_size, [out_dim]                                                  */
+    const float *w0;        /* A[0][:, 0] + l2 weight of layer 0 [:, 0] (the time column; NOT divided), [out_dim[0]]     */
+    const float *trace;     /* needed iff want_ldj.  With E1 = A[0][:, 1 : 1 + dim], F1 = G[0][:, 1 : 1 + dim],
+                               c(P, Q)_h = sum_a P[a, h] Q[h, a] and C(Q, R, P) = Q o (R P)^T (elementwise, [H2, H1]):
+                               n_layers == 2: [2][H1]: c_d = c(A2, E1 + F1) + c(G2, E1), then c_s = c(G2, F1);
+                                              tr_i = d1_i . c_d + sum_j d1_j . c_s
+                               n_layers == 3: [5][P][P] row-major, P = 32 * tiles(max(H1, H2)) (1 or 2 tiles of 32), zero beyond
+                                              [H2, H1], 16-byte aligned, in this order:
+                                              C_abd = C(A2, E1 + F1, A3) + C(G2, E1, A3) + C(A2, E1, G3),  C_c = C(G2, F1, A3),
+                                              C_e = C(A2, F1, G3),  C_f = C(G2, E1, G3),  C_g = C(G2, F1, G3);
+                                              tr_i = d2_i^T (C_abd d1_i + C_c s1) + s2^T (C_f d1_i + C_g s1) + sum_j d2_j^T C_e d1_j,
+                                              d_l = act'(hidden layer l), s_l = sum_j d_l,j                              */
+    int32_t n_layers;       /* equivariant layers: 2 (one hidden layer) or 3 (two)                                      */
+    int32_t dim;            /* 1..SX_CNF_SET_MAX_DIM                                                                    */
+    int32_t latent_dim;     /* 1 + dim + latent_dim <= SX_CNF_SET_MAX_IN                                                */
+    int32_t act;            /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU                                                      */
+    int32_t set_size;       /* 1..SX_CNF_SET_MAX_SIZE                                                                   */
+    int32_t out_dim[3];     /* hidden widths 1..SX_CNF_SET_MAX_HIDDEN, the last one == dim                              */
+} sx_cnf_set_net;
+
+/* Bytes of LDS the launch stages for this network: the A and G images, the vectors, the set-sum scratch and as many of the C
+ * matrices as fit SX_CNF_LDS_BYTES (the others are read from global memory); 0 for a network outside the coverage above.  Reads
+ * the integer fields only. */
+size_t sx_cnf_set_lds_bytes(const sx_cnf_set_net *net_host, int32_t want_ldj);
+
+/* The arguments of sx_cnf_flow; n_rows must be a multiple of set_size.  A workgroup takes floor(128 / set_size) whole sets at a
+ * time; a set's result does not depend on its position in the batch or on the other sets. */
+int sx_cnf_set_flow(const sx_cnf_set_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                    int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
+
 /* ---- multi-head attention core (stribor/net/attention.py:8-49 with util/safe_softmax.py:3-14) ---------------------------------
  * q [R, Nq, E], k / v [R, Nk, E]: element (r, n, e) at base + r * bs + n * rs + e (unit column stride; bs = 0 broadcasts one
  * [N, E] block over R).  n_heads heads of width dh = E / n_heads (1..SX_ATTENTION_MAX_HEAD_DIM), scale (1 / dh) ** 0.5

@@ -60,7 +60,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
-           'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow']
+           'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
@@ -71,6 +71,8 @@ RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
 CNF_MAX_DIM = 64
 CNF_LDS_BYTES = 160 * 1024
 CNF_SOLVERS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
+# ... over sets (sx_cnf_set_flow)
+CNF_SET_MAX_DIM, CNF_SET_MAX_IN, CNF_SET_MAX_HIDDEN, CNF_SET_MAX_SIZE = 32, 64, 64, 128
 
 # multi-head attention core (include/stribor_hip.h: sx_attention_fwd / sx_attention_bwd)
 ATTENTION_MAX_HEAD_DIM = 128
@@ -121,6 +123,12 @@ class sx_cnf_layer(C.Structure):
 class sx_cnf_net(C.Structure):
     _fields_ = [('layer', sx_cnf_layer * 3), ('n_layers', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32),
                 ('trace', C.c_void_p)]
+
+
+class sx_cnf_set_net(C.Structure):
+    _fields_ = [('A', C.c_void_p * 3), ('G', C.c_void_p * 3), ('bias', C.c_void_p * 3), ('w0', C.c_void_p), ('trace', C.c_void_p),
+                ('n_layers', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32), ('set_size', C.c_int32),
+                ('out_dim', C.c_int32 * 3)]
 
 
 class sx_cnf_exact_net(C.Structure):
@@ -261,6 +269,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_exact_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_net)]
     lib.sx_cnf_exact_flow.restype = i32
     lib.sx_cnf_exact_flow.argtypes = [C.POINTER(sx_cnf_exact_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_set_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_set_lds_bytes.argtypes = [C.POINTER(sx_cnf_set_net), i32]
+    lib.sx_cnf_set_flow.restype = i32
+    lib.sx_cnf_set_flow.argtypes = [C.POINTER(sx_cnf_set_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

@@ -11,6 +11,12 @@ from a closed form whose weight-only constants (``trace_constants``) are derived
 ``mask``, ``set_data``, the Hutchinson estimator of training mode, and every call that has to build a graph -- runs the same grid
 and tableau as a loop of torch ops over the module (``_solve_composed``); gradients are those of the discretised steps.
 
+Sets of shape (..., N, dim): a ``net.DiffeqDeepset`` over a ``net.EquivariantNet`` (one or two hidden layers of <= 64 units, N <= 128,
+dim <= 32, 1 + dim + latent <= 64, no final activation) under ``set_data=True`` / ``divergence='compute_set'`` (or ``'none'``) is ONE
+launch of ``sx_cnf_set_flow`` under the same conditions: the per-element share of the set's divergence -- what
+``divergence_exact_for_sets(...).sum(-1)`` gives with N * dim reverse passes per evaluation -- comes from a closed form whose
+weight-only constants (``set_trace_constants``; they depend on N) are derived once per N in fp64 (DESIGN.md "CNF on sets").
+
 ``divergence='exact'`` over a ``net.DiffeqExactTraceMLP`` (two MADEs + a dimwise MLP, one or two hidden layers of <= 64 units,
 dim <= 16, d_h <= 8, latent <= 64) is ONE launch of ``sx_cnf_exact_flow`` under the same conditions: the masked weights are staged
 into the kernel's LDS image once (cached, guarded on weights and masks) and the Jacobian diagonal is a forward-mode tangent beside the
@@ -27,7 +33,8 @@ from .. import _hip
 from ..flow import Transform, flatten_rows, graph_wanted
 from ..fused import ProgramCache
 from ..net import diffeq_exact_trace as exact_trace
-from ..net.diffeq import DiffeqMLP
+from ..net.diffeq import DiffeqDeepset, DiffeqMLP
+from ..net.equivariant import EquivariantLayer, EquivariantNet
 from ..net.mlp import MLP
 from ..util.divergence import divergence_approx, divergence_exact, divergence_exact_for_sets
 
@@ -70,6 +77,26 @@ def trace_constants(weights, dim: int):
     return W2 * (W1x @ W3).t()
 
 
+def set_trace_constants(weights, dim: int, n: int):
+    """The weight-only constants of the per-element divergence of f = EquivariantNet([t, x, latent]) over sets of n elements, no
+    final activation.  `weights`: per layer (A_l, B_l) = (l1.weight, l2.weight).  With E1 = A_1[:, 1 : 1 + dim], F1 = B_1[:, 1 : 1 +
+    dim] / n, G_l = B_l / n, c(P, Q)_h = sum_a P[a, h] Q[h, a] and C(Q, R, P) = Q o (R P)^T (elementwise, [H2, H1]):
+      one hidden layer: [2, H1] = (c_d, c_s), c_d = c(A2, E1 + F1) + c(G2, E1), c_s = c(G2, F1);
+          tr_i = d1_i . c_d + s1 . c_s
+      two: [5, H2, H1] = (C_abd, C_c, C_e, C_f, C_g), C_abd = C(A2, E1 + F1, A3) + C(G2, E1, A3) + C(A2, E1, G3),
+          C_c = C(G2, F1, A3), C_e = C(A2, F1, G3), C_f = C(G2, E1, G3), C_g = C(G2, F1, G3);
+          tr_i = d2_i^T C_abd d1_i + d2_i^T C_c s1 + s2^T C_f d1_i + [sum_j d2_j^T C_e d1_j + s2^T C_g s1]
+    with d_l,i = act'(hidden layer l of element i) and s_l = sum_j d_l,j over the set.  fp64 in, fp64 out (the caller rounds once)."""
+    (A1, B1), (A2, B2) = weights[0], weights[1]
+    E1, F1, G2 = A1[:, 1:1 + dim], B1[:, 1:1 + dim] / n, B2 / n
+    if len(weights) == 2:
+        c = lambda P, Q: (P.t() * Q).sum(-1)
+        return torch.stack([c(A2, E1 + F1) + c(G2, E1), c(G2, F1)])
+    A3, G3 = weights[2][0], weights[2][1] / n
+    C = lambda Q, R, P: Q * (R @ P).t()
+    return torch.stack([C(A2, E1 + F1, A3) + C(G2, E1, A3) + C(A2, E1, G3), C(G2, F1, A3), C(A2, F1, G3), C(G2, E1, G3), C(G2, F1, G3)])
+
+
 class ODEfunc(nn.Module):
     """The augmented dynamics of cnf.py:13-99: d/dt (x, a) = (f(t, x), -div f), with a kept per feature."""
 
@@ -94,6 +121,12 @@ class ODEfunc(nn.Module):
     def exact_trace(self) -> bool:
         """Does this setting evaluate the exact divergence of a row-wise net (cnf.py:91-95)?"""
         return not self.set_data and (self.divergence == 'compute' or (self.divergence == 'approximate' and not self.training))
+
+    def exact_set_trace(self) -> bool:
+        """Does this setting evaluate the exact divergence of a set net (cnf.py:91-93: divergence_exact_for_sets)?"""
+        if self.divergence == 'compute_set':
+            return True
+        return self.set_data and (self.divergence == 'compute' or (self.divergence == 'approximate' and not self.training))
 
     def forward(self, t, states):
         """states = (x, a[, latent][, mask]) -> their time derivatives (zeros for latent and mask)."""
@@ -262,6 +295,74 @@ class ContinuousTransform(Transform):
                 return tc.to(torch.float32).contiguous()
         return self._trace.get(('trace', str(device)), build, guards=list(weights))
 
+    def _set_kernel_net(self, set_size: int, latent_dim: int, device):
+        """(sx_cnf_set_net, keep-alive list) for sx_cnf_set_flow over sets of `set_size` elements, or None outside its coverage."""
+        diffeq = self.odefunc.diffeq
+        if type(diffeq) is not DiffeqDeepset or type(diffeq.net) is not EquivariantNet:
+            return None
+        net = diffeq.net
+        act = type(net.activation).__name__
+        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
+        if type(net.final_activation) is not nn.Identity or type(net.activation) is not getattr(nn, act, None) \
+                or _hip.ACT_CODES.get(act, 99) > 6 or _ACT_DEFAULTS.get(type(net.activation), lambda m: True)(net.activation) is not True:
+            return None
+        layers = list(net.layers)
+        if len(layers) not in (2, 3) or any(type(l) is not EquivariantLayer or type(l.l1) is not nn.Linear or type(l.l2) is not nn.Linear
+                                            for l in layers):
+            return None
+        if not 1 <= set_size <= _hip.CNF_SET_MAX_SIZE or not 1 <= self.dim <= _hip.CNF_SET_MAX_DIM:
+            return None
+        widths = [1 + self.dim + latent_dim] + [l.l1.out_features for l in layers]
+        if widths[0] > _hip.CNF_SET_MAX_IN or widths[-1] != self.dim or any(w > _hip.CNF_SET_MAX_HIDDEN for w in widths[1:-1]):
+            return None
+        if any(l.l1.in_features != w or l.l2.in_features != w or l.l2.out_features != l.l1.out_features for l, w in zip(layers, widths)):
+            return None
+        tensors = [t for l in layers for t in (l.l1.weight, l.l2.weight, l.l1.bias, l.l2.bias)]
+        if any(t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device for t in tensors):
+            return None
+        image, offsets = self._set_constants(layers, set_size, device)
+        d = _hip.sx_cnf_set_net()
+        base = image.data_ptr()
+        for i, l in enumerate(layers):
+            d.A[i], d.G[i], d.bias[i] = l.l1.weight.data_ptr(), base + 4 * offsets[f'G{i}'], base + 4 * offsets[f'b{i}']
+            d.out_dim[i] = l.l1.out_features
+        d.w0, d.trace = base + 4 * offsets['w0'], base + 4 * offsets['trace']
+        d.n_layers, d.dim, d.latent_dim, d.act, d.set_size = len(layers), self.dim, latent_dim, _hip.ACT_CODES[act], set_size
+        if _hip.lib().sx_cnf_set_lds_bytes(d, 1) == 0:
+            return None
+        return d, [image] + [t.detach() for t in tensors]
+
+    def _set_constants(self, layers, set_size: int, device):
+        """What sx_cnf_set_flow reads beside the l1 weights, as one fp32 device buffer and float offsets into it: per layer G = l2.weight
+        / N and bias = l1.bias + l2.bias / N, the time column w0 and `set_trace_constants` (two hidden layers: zero-padded to squares of
+        whole tiles).  Derived in fp64; cached per N until a weight changes (ProgramCache guards and the structure epoch)."""
+        guards = [t for l in layers for t in (l.l1.weight, l.l2.weight, l.l1.bias, l.l2.bias)]
+
+        def build():
+            with torch.no_grad():
+                f64 = lambda t: t.detach().to(torch.float64)
+                parts = {}
+                for i, l in enumerate(layers):
+                    parts[f'G{i}'] = f64(l.l2.weight) / set_size
+                    parts[f'b{i}'] = f64(l.l1.bias) + f64(l.l2.bias) / set_size
+                parts['w0'] = f64(layers[0].l1.weight)[:, 0] + f64(layers[0].l2.weight)[:, 0]
+                tc = set_trace_constants([(f64(l.l1.weight), f64(l.l2.weight)) for l in layers], self.dim, set_size)
+                if tc.dim() == 3:
+                    P = 32 * max((tc.shape[1] + 31) // 32, (tc.shape[2] + 31) // 32)
+                    full = torch.zeros(5, P, P, dtype=torch.float64, device=device)
+                    full[:, :tc.shape[1], :tc.shape[2]] = tc
+                    tc = full
+                parts['trace'] = tc
+                offsets, off = {}, 0
+                for k, v in parts.items():
+                    offsets[k] = off
+                    off += (v.numel() + 3) // 4 * 4                   # (every part 16-byte aligned)
+                image = torch.zeros(off, dtype=torch.float32, device=device)
+                for k, v in parts.items():
+                    image[offsets[k]:offsets[k] + v.numel()] = v.reshape(-1).to(torch.float32)
+                return image, offsets
+        return self._trace.get(('set', set_size, str(device)), build, guards=guards)
+
     def _exact_kernel_net(self, latent_dim: int, device):
         """(sx_cnf_exact_net, keep-alive list) for sx_cnf_exact_flow, or None when the ODE function is outside its coverage."""
         s = exact_trace.kernel_coverage(self.odefunc.diffeq, self.dim, latent_dim)
@@ -341,6 +442,9 @@ class ContinuousTransform(Transform):
         elif not graph and mask is None and func.divergence == 'exact' and not func.set_data:
             trace, entry = want_ldj, 'sx_cnf_exact_flow'
             plan = self._exact_kernel_net(0 if latent is None else latent.shape[-1], x.device)
+        if plan is None and not graph and mask is None and x.dim() >= 2 and (func.divergence == 'none' or func.exact_set_trace()):
+            trace, entry = want_ldj and func.divergence != 'none', 'sx_cnf_set_flow'
+            plan = self._set_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
         if plan is not None:
             x2, lead = flatten_rows(x)
             lat2 = None if latent is None else flatten_rows(latent)[0]
@@ -393,3 +497,13 @@ class ContinuousTransform(Transform):
     def _autograd_inverse(self, y2, lat2=None, pre=None):
         x, ldj = self._solve(y2, lat2, None, True, True)
         return x, ldj.reshape(-1)
+
+    @property
+    def set_data(self) -> bool:
+        """Does the ODE function read its input as sets (..., N, dim)?  (NormalizingFlow keeps the set axis for such layers.)"""
+        return bool(self.odefunc.set_data or self.odefunc.divergence == 'compute_set')
+
+    def _autograd_set(self, x2, lat2, set_size: int, reverse: bool):
+        lat = None if lat2 is None else lat2.reshape(-1, set_size, lat2.shape[-1])
+        y, ldj = self._solve(x2.reshape(-1, set_size, x2.shape[-1]), lat, None, reverse, True)
+        return y.reshape(x2.shape), ldj.reshape(-1)

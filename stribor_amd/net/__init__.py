@@ -1,7 +1,8 @@
 from .mlp import MLP
 from .time_net import TimeFourier, TimeFourierBounded, TimeIdentity, TimeLinear, TimeLog, TimeTanh
 from .attention import Attention, InducedSelfAttention, SelfAttention, attention
-from .diffeq import DiffeqConcat, DiffeqMLP, DiffeqNet
+from .equivariant import EquivariantLayer, EquivariantNet
+from .diffeq import DiffeqConcat, DiffeqDeepset, DiffeqMLP, DiffeqNet
 from .made import MADE
 from .diffeq_zero_trace import DiffeqZeroTraceMLP
 from .diagjac import FuncAndDiagJac

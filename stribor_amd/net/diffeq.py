@@ -1,8 +1,10 @@
-"""Differential-equation nets of the continuous normalizing flow (reference: stribor/net/diffeq.py:13-75).
+"""Differential-equation nets of the continuous normalizing flow (reference: stribor/net/diffeq.py:13-94).
 
 Same constructors and ``state_dict`` keys (``net.net.0.weight``, ...); ``DiffeqMLP`` builds the product ``net.MLP``, so its
 construction order and RNG draws are the MLP's.  The input columns are [t, x, latent] in this order (diffeq.py:44-47).
 ``ContinuousTransform`` does not call a ``DiffeqMLP`` on its kernel path at all: ``sx_cnf_flow`` consumes the weights directly.
+``DiffeqDeepset`` is the same wrapper around ``net.EquivariantNet`` for sets of shape (..., N, dim) (keys
+``net.layers.<i>.l1.weight``, ...); its kernel is ``sx_cnf_set_flow``.
 """
 from abc import ABCMeta, abstractmethod
 from typing import List
@@ -10,9 +12,10 @@ from typing import List
 import torch
 import torch.nn as nn
 
+from .equivariant import EquivariantNet
 from .mlp import MLP
 
-__all__ = ['DiffeqNet', 'DiffeqConcat', 'DiffeqMLP']
+__all__ = ['DiffeqNet', 'DiffeqConcat', 'DiffeqMLP', 'DiffeqDeepset']
 
 
 class DiffeqNet(nn.Module, metaclass=ABCMeta):
@@ -45,3 +48,12 @@ class DiffeqMLP(DiffeqConcat):
     def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, activation: str = 'Tanh',
                  final_activation: str = None, **kwargs):
         super().__init__(MLP(in_dim, hidden_dims, out_dim, activation, final_activation))
+
+
+class DiffeqDeepset(DiffeqConcat):
+    """``DiffeqDeepset(dim + 1 (+ latent), hidden_dims, dim)`` over sets (..., N, dim) (diffeq.py:78-94); ``mask`` reaches the
+    equivariant layers through ``DiffeqConcat.forward``'s keyword arguments."""
+
+    def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, activation: str = 'Tanh',
+                 final_activation: str = None, **kwargs):
+        super().__init__(EquivariantNet(in_dim, hidden_dims, out_dim, activation, final_activation))

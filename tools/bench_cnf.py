@@ -11,6 +11,11 @@ count, against its composition path (FuncAndDiagJac: one autograd.grad with a gr
 the two MADEs 2 x 2 (D H1 + H1 H2 + H2 d_h D), and per dimension the dimwise net 2 (1 + d_h) H1 + 2 H1 H2 + 2 H2 for the value and
 2 H1 H2 + 2 H2 for the tangent (the latent-free case; padding to tiles of 32 is not counted).
 
+The set line: set_data=True over DiffeqDeepset(3, [64, 64], 2) on sx_cnf_set_flow, (B, N, dim) = (8192, 32, 2), the same grid, against
+its composition path (divergence_exact_for_sets: N x dim reverse passes with a graph per evaluation) timed at --set-fallback-sets sets
+and scaled.  FLOPs per element and evaluation: every equivariant layer is two GEMMs (the l1 and l2 branches), 2 x 2 (dim H1 + H1 H2 +
+H2 dim), plus five H2 x H1 trace GEMMs, 5 x 2 H2 H1 (padding and the set sums are not counted).
+
     python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json]
 """
 import argparse
@@ -43,6 +48,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=1 << 18)
     ap.add_argument('--fallback-rows', type=int, default=1 << 14, help='rows of the composition-path timing (scaled to --rows)')
+    ap.add_argument('--sets', type=int, default=8192, help='B of the set line (N = 32, dim = 2)')
+    ap.add_argument('--set-fallback-sets', type=int, default=64, help="sets of the set line's composition-path timing (scaled to --sets)")
     ap.add_argument('--steps', type=int, default=16)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--json', default=None)
@@ -99,6 +106,31 @@ def main():
     print(f'exact trace dim {D} d_h {d_h} {hidden} N={a.rows} rk4 x {a.steps}: solve + log-det {ms:.2f} ms ({r["rows_per_s"]:.3g} rows/s, '
           f'{r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path '
           f'{fb:.0f} ms (timed at {ys.shape[0]} rows, scaled) = {r["composed_over_kernel"]:.1f} x; kernel vs composition max abs '
+          f'x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
+    # the set net
+    torch.manual_seed(0)
+    B, N, D, hidden = a.sets, 32, 2, [64, 64]
+    f = st.ContinuousTransform(D, net=st.net.DiffeqDeepset(D + 1, hidden, D), divergence='compute', solver='rk4',
+                               solver_options={'step_size': 1.0 / a.steps}, set_data=True).eval().to('cuda')
+    y = torch.randn(B, N, D, device='cuda')
+    ys = y[:a.set_fallback_sets]
+    H1, H2 = hidden
+    flop_eval = 4 * (D * H1 + H1 * H2 + H2 * D) + 10 * H2 * H1
+    with torch.no_grad():
+        ms = timed(lambda: f.inverse_and_log_det_jacobian(y), a.reps)
+        assert f._last_path == 'kernel'
+        ms_x = timed(lambda: f.inverse(y), a.reps)
+        fb = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=0) * (B / ys.shape[0])
+        xk, lk = f.inverse_and_log_det_jacobian(ys)
+        xc, lc = f._composed_reference(ys, reverse=True)
+    fl = B * N * 4 * a.steps * flop_eval
+    r = results[f'set_b{B}_n{N}_dim{D}_h{"x".join(map(str, hidden))}'] = {
+        'solve_ldj_ms': ms, 'solve_only_ms': ms_x, 'composed_ms_scaled': fb, 'rows_per_s': B * N / ms * 1e3, 'tflops': fl / ms / 1e9,
+        'frac_of_peak': fl / (ms * 1e-3) / PEAK_F32_MFMA, 'composed_over_kernel': fb / ms,
+        'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item()}
+    print(f'sets (B, N, dim) = ({B}, {N}, {D}) {hidden} rk4 x {a.steps}: solve + log-det {ms:.2f} ms ({r["rows_per_s"]:.3g} elements/s, '
+          f'{r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path '
+          f'{fb:.0f} ms (timed at {ys.shape[0]} sets, scaled) = {r["composed_over_kernel"]:.0f} x; kernel vs composition max abs '
           f'x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
     results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows}
     if a.json:
