@@ -765,6 +765,51 @@ size_t sx_cnf_exact_lds_bytes(const sx_cnf_exact_net *net_host);
 int sx_cnf_exact_flow(const sx_cnf_exact_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                       int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- exact-trace continuous normalizing flow over sets (ContinuousTransform with divergence='exact' over DiffeqExactTraceDeepSet:
+ * stribor/net/diffeq_exact_trace.py:75-101, diffeq_zero_trace.py:59-176) ----
+ * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  For element i, dimension d:
+ * h_i[d, :] = MADE(x_i)[d, :] + p_i with p_i the pooling over the OTHER elements j of e_j = set_emb([t, x_j]) (an MLP with d_h
+ * outputs); f_i[d] = g(t, x_i[d], h_i[d, :], latent_i), jac_i[d] = dg/dx at fixed h, as sx_cnf_exact_flow.  Pooling: sum = (sum_j e_j)
+ * - e_i with the sum taken in element order; mean = that / max(N - 1, 1); max = per column e_i == first ? second : first with first >=
+ * second the two largest values over the set, duplicates counted; N == 1 pools to 0.
+ * The image is sx_cnf_exact_net's in tiles, positions and vectors, with these parts, in this order (sizes in floats):
+ *   MADE:      W1 [HT x 1 tiles], b1 [32 HT], (two hidden layers: W2 [HT x HT tiles], b2 [32 HT],) W_last [OT x HT tiles], b_last [32 OT]
+ *   set_emb:   W1[:, 1:] [HT x 1 tiles] (inputs at the state's positions), b1 [32 HT], W1[:, 0] (time) [32 HT], (W2 [HT x HT tiles],
+ *              b2 [32 HT],) W_last [1 x HT tiles], b_last [32]: output slot kk at position kmap(kk >> 1, kk & 1)
+ *   dimwise:   as sx_cnf_exact_net's
+ * The kernel keeps an exchange scratch of 128 x 16 floats behind the image in LDS. */
+#define SX_CNF_EXACT_SET_MAX_DIM    16
+#define SX_CNF_EXACT_SET_MAX_DH     8
+#define SX_CNF_EXACT_SET_MAX_LATENT 64
+#define SX_CNF_EXACT_SET_MAX_HIDDEN 64
+#define SX_CNF_EXACT_SET_MAX_SIZE   128
+#define SX_POOL_SUM  0
+#define SX_POOL_MEAN 1
+#define SX_POOL_MAX  2
+typedef struct {
+    const float *image;     /* device, 16-byte aligned: the LDS image above                                             */
+    const float *w_latent;  /* device, 16-byte aligned: the dimwise W1[:, 2 + d_h ..], row-major [32 HT][32 ceil(latent_dim / 32)],
+                               zero-padded; NULL iff latent_dim == 0                                                     */
+    int32_t image_floats;   /* must equal sx_cnf_exact_set_lds_bytes / 4 - 128 * 16                                     */
+    int32_t dim;            /* 1..SX_CNF_EXACT_SET_MAX_DIM                                                              */
+    int32_t d_h;            /* 1..SX_CNF_EXACT_SET_MAX_DH                                                               */
+    int32_t latent_dim;     /* 0..SX_CNF_EXACT_SET_MAX_LATENT                                                           */
+    int32_t n_hidden;       /* 1 or 2 hidden layers, the same widths in the MADE, the set embedding and the dimwise net */
+    int32_t hidden[2];      /* 1..SX_CNF_EXACT_SET_MAX_HIDDEN each                                                      */
+    int32_t act;            /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU, the same in the three nets                          */
+    int32_t set_size;       /* 1..SX_CNF_EXACT_SET_MAX_SIZE                                                             */
+    int32_t pooling;        /* SX_POOL_SUM, SX_POOL_MEAN or SX_POOL_MAX                                                 */
+} sx_cnf_exact_set_net;
+
+/* Bytes of LDS of a launch for this network: the image plus the exchange scratch; 0 for a network outside the coverage or one that
+ * does not fit SX_CNF_LDS_BYTES.  Reads the integer fields only. */
+size_t sx_cnf_exact_set_lds_bytes(const sx_cnf_exact_set_net *net_host);
+
+/* The arguments of sx_cnf_exact_flow; n_rows must be a multiple of set_size.  A workgroup takes floor(128 / set_size) whole sets at a
+ * time; a set's result does not depend on its position in the batch or on the other sets. */
+int sx_cnf_exact_set_flow(const sx_cnf_exact_set_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                          int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
+
 /* ---- continuous normalizing flow over sets (ContinuousTransform with set_data=True or divergence='compute_set' over DiffeqDeepset:
  * stribor/net/diffeq.py:78-94 around net/equivariant.py's EquivariantNet) ----
  * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  Equivariant layer l is

@@ -3,7 +3,8 @@
 Same names and constructor signatures as ``stribor`` for the classes on the path
 (``NormalizingFlow``, ``Coupling``, ``Affine``, ``Spline``, ``AffineLU``, ``MatrixExponential``,
 ``Permute``/``Flip``, ``Sigmoid``/``Logit``, ``ELU``, ``LeakyReLU``, ``Cumsum``/``Diff``, ``Identity``,
-``IResNet``/``ContinuousIResNet``, ``ContinuousTransform`` (with ``net.DiffeqMLP``), ``UnitNormal``, ``net.MLP``, ``net.attention``/``net.Attention``/``net.SelfAttention``/
+``IResNet``/``ContinuousIResNet``, ``ContinuousTransform`` (with ``net.DiffeqMLP``, ``net.DiffeqDeepset``, ``net.DiffeqExactTraceMLP``,
+``net.DiffeqExactTraceDeepSet``), ``UnitNormal``, ``net.MLP``, ``net.attention``/``net.Attention``/``net.SelfAttention``/
 ``net.InducedSelfAttention``, ``util.get_mask``, ``util.safe_softmax``); the arithmetic is hand-written
 HIP for gfx950 behind the C ABI in ``include/stribor_hip.h``.  There is no CPU fallback.
 """

@@ -60,7 +60,8 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
-           'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow']
+           'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
+           'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
@@ -134,6 +135,12 @@ class sx_cnf_set_net(C.Structure):
 class sx_cnf_exact_net(C.Structure):
     _fields_ = [('image', C.c_void_p), ('w_latent', C.c_void_p), ('image_floats', C.c_int32), ('dim', C.c_int32), ('d_h', C.c_int32),
                 ('latent_dim', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 2), ('act', C.c_int32)]
+
+
+class sx_cnf_exact_set_net(C.Structure):
+    _fields_ = [('image', C.c_void_p), ('w_latent', C.c_void_p), ('image_floats', C.c_int32), ('dim', C.c_int32), ('d_h', C.c_int32),
+                ('latent_dim', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 2), ('act', C.c_int32),
+                ('set_size', C.c_int32), ('pooling', C.c_int32)]
 
 
 class sx_attention_args(C.Structure):
@@ -269,6 +276,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_exact_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_net)]
     lib.sx_cnf_exact_flow.restype = i32
     lib.sx_cnf_exact_flow.argtypes = [C.POINTER(sx_cnf_exact_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_exact_set_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_exact_set_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_set_net)]
+    lib.sx_cnf_exact_set_flow.restype = i32
+    lib.sx_cnf_exact_set_flow.argtypes = [C.POINTER(sx_cnf_exact_set_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
     lib.sx_cnf_set_lds_bytes.restype = C.c_size_t
     lib.sx_cnf_set_lds_bytes.argtypes = [C.POINTER(sx_cnf_set_net), i32]
     lib.sx_cnf_set_flow.restype = i32

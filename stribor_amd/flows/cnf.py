@@ -20,7 +20,9 @@ weight-only constants (``set_trace_constants``; they depend on N) are derived on
 ``divergence='exact'`` over a ``net.DiffeqExactTraceMLP`` (two MADEs + a dimwise MLP, one or two hidden layers of <= 64 units,
 dim <= 16, d_h <= 8, latent <= 64) is ONE launch of ``sx_cnf_exact_flow`` under the same conditions: the masked weights are staged
 into the kernel's LDS image once (cached, guarded on weights and masks) and the Jacobian diagonal is a forward-mode tangent beside the
-value.  Any other net under 'exact' runs the composition path over ``net.FuncAndDiagJac``.
+value.  Over a ``net.DiffeqExactTraceDeepSet`` on sets (..., N, dim) (N <= 128, the same widths, sum / mean / max pooling) it is ONE
+launch of ``sx_cnf_exact_set_flow``: the same image scheme plus one ordered exchange through LDS per evaluation for the exclusive
+pooling.  Any other net under 'exact' runs the composition path over ``net.FuncAndDiagJac``.
 """
 import ctypes
 from typing import Dict, Optional
@@ -34,6 +36,7 @@ from ..flow import Transform, flatten_rows, graph_wanted
 from ..fused import ProgramCache
 from ..net import diffeq_exact_trace as exact_trace
 from ..net.diffeq import DiffeqDeepset, DiffeqMLP
+from ..net.diffeq_zero_trace import DiffeqZeroTraceDeepSet
 from ..net.equivariant import EquivariantLayer, EquivariantNet
 from ..net.mlp import MLP
 from ..util.divergence import divergence_approx, divergence_exact, divergence_exact_for_sets
@@ -390,6 +393,35 @@ class ContinuousTransform(Transform):
             return None
         return d, [image, w_latent]
 
+    def _exact_set_kernel_net(self, set_size: int, latent_dim: int, device):
+        """(sx_cnf_exact_set_net, keep-alive list) for sx_cnf_exact_set_flow over sets of `set_size` elements, or None when the ODE
+        function is outside its coverage."""
+        s = exact_trace.kernel_coverage_set(self.odefunc.diffeq, self.dim, latent_dim, set_size)
+        if s is None:
+            return None
+        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
+        if any(_ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True for m in s['activations']):
+            return None
+        guards = exact_trace.kernel_tensors_set(s)
+        if any(g.dtype != torch.float32 or not g.is_contiguous() or g.device != device for g in guards):
+            return None
+
+        def build():
+            image, w_latent = exact_trace.kernel_image_set(s)
+            image = torch.from_numpy(image).to(device)
+            return image, (None if w_latent is None else torch.from_numpy(w_latent).contiguous().to(device))
+        image, w_latent = self._trace.get(('exact_set', str(device)), build, guards=guards)
+        d = _hip.sx_cnf_exact_set_net()
+        d.image, d.w_latent, d.image_floats = image.data_ptr(), (0 if w_latent is None else w_latent.data_ptr()), image.numel()
+        d.dim, d.d_h, d.latent_dim, d.n_hidden, d.act = self.dim, s['d_h'], latent_dim, len(s['hidden']), _hip.ACT_CODES[s['act']]
+        d.set_size, d.pooling = set_size, exact_trace.POOLINGS[s['pooling']]
+        for i, w in enumerate(s['hidden']):
+            d.hidden[i] = w
+        lds = _hip.lib().sx_cnf_exact_set_lds_bytes(d)
+        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * (image.numel() + exact_trace.SET_EXCHANGE_FLOATS):
+            return None
+        return d, [image, w_latent]
+
     # ---- the two paths ----------------------------------------------------------------------------------------------------------
     def _solve_kernel(self, plan, x2, lat2, name, step, grid, want_ldj, entry='sx_cnf_flow'):
         d, keep = plan
@@ -439,6 +471,10 @@ class ContinuousTransform(Transform):
             ld = 0 if latent is None else latent.shape[-1]
             trace = want_ldj and func.divergence != 'none'
             plan = self._kernel_net(ld, trace, x.device)
+        elif not graph and mask is None and func.divergence == 'exact' and type(func.diffeq) is exact_trace.DiffeqExactTraceDeepSet:
+            if x.dim() >= 2:                                          # (the choice does not depend on set_data: ODEfunc ignores it here)
+                trace, entry = want_ldj, 'sx_cnf_exact_set_flow'
+                plan = self._exact_set_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
         elif not graph and mask is None and func.divergence == 'exact' and not func.set_data:
             trace, entry = want_ldj, 'sx_cnf_exact_flow'
             plan = self._exact_kernel_net(0 if latent is None else latent.shape[-1], x.device)
@@ -501,7 +537,8 @@ class ContinuousTransform(Transform):
     @property
     def set_data(self) -> bool:
         """Does the ODE function read its input as sets (..., N, dim)?  (NormalizingFlow keeps the set axis for such layers.)"""
-        return bool(self.odefunc.set_data or self.odefunc.divergence == 'compute_set')
+        return bool(self.odefunc.set_data or self.odefunc.divergence == 'compute_set'
+                    or type(self.odefunc.diffeq) in (DiffeqZeroTraceDeepSet, exact_trace.DiffeqExactTraceDeepSet))
 
     def _autograd_set(self, x2, lat2, set_size: int, reverse: bool):
         lat = None if lat2 is None else lat2.reshape(-1, set_size, lat2.shape[-1])

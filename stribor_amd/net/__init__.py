@@ -4,6 +4,6 @@ from .attention import Attention, InducedSelfAttention, SelfAttention, attention
 from .equivariant import EquivariantLayer, EquivariantNet
 from .diffeq import DiffeqConcat, DiffeqDeepset, DiffeqMLP, DiffeqNet
 from .made import MADE
-from .diffeq_zero_trace import DiffeqZeroTraceMLP
+from .diffeq_zero_trace import DiffeqZeroTraceDeepSet, DiffeqZeroTraceMLP
 from .diagjac import FuncAndDiagJac
-from .diffeq_exact_trace import DiffeqExactTrace, DiffeqExactTraceMLP
+from .diffeq_exact_trace import DiffeqExactTrace, DiffeqExactTraceDeepSet, DiffeqExactTraceMLP

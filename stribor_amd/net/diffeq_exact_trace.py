@@ -7,6 +7,11 @@ general evaluation is ``net.FuncAndDiagJac`` (any two modules, any device, a gra
 (two MADEs + a ``DiffeqMLP``); same constructors and ``state_dict`` keys as the reference (``exclusive_net.net1.net.0.{weight,bias,
 mask}``, ``dimwise_net.net.net.0.weight``), construction order net1, net2, dimwise net.
 
+``DiffeqExactTraceDeepSet`` is the set instance over (..., N, dim) (diffeq_exact_trace.py:75-101): exclusive net
+``DiffeqZeroTraceDeepSet`` (keys ``exclusive_net.elementwise.net.<i>.{weight,bias,mask}``,
+``exclusive_net.interaction.set_emb.net.net.<i>.{weight,bias}``), the same dimwise net; construction order MADE, set embedding,
+dimwise net.  ``closed_form_set`` / ``kernel_image_set`` are its counterparts of the functions below, for ``sx_cnf_exact_set_flow``.
+
 For the MLP instance this module also holds what ``sx_cnf_exact_flow`` consumes: ``kernel_image`` stages ``mask * weight`` and the
 dimwise weights into the kernel's LDS image (include/stribor_hip.h), and ``closed_form`` is the same arithmetic as torch ops --
 value and forward-mode tangent side by side, no autograd -- in any dtype (tests hold it to ``autograd.functional.jacobian``).
@@ -20,13 +25,16 @@ import torch.nn as nn
 from ..util.flatten_params import flatten_params
 from .diagjac import FuncAndDiagJac
 from .diffeq import DiffeqMLP
-from .diffeq_zero_trace import DiffeqZeroTraceMLP
+from .diffeq_zero_trace import DiffeqZeroTraceDeepSet, DiffeqZeroTraceMLP, ZeroTraceEquivariantEncoder
 from .made import MADE, MaskedLinear
 from .mlp import MLP
 
-__all__ = ['DiffeqExactTrace', 'DiffeqExactTraceMLP']
+__all__ = ['DiffeqExactTrace', 'DiffeqExactTraceMLP', 'DiffeqExactTraceDeepSet']
 
 MAX_DIM, MAX_DH, MAX_LATENT, MAX_HIDDEN = 16, 8, 64, 64          # sx_cnf_exact_flow's coverage (SX_CNF_EXACT_MAX_*)
+MAX_SET_SIZE = 128                                               # sx_cnf_exact_set_flow's (SX_CNF_EXACT_SET_MAX_*: the four above too)
+POOLINGS = {'sum': 0, 'mean': 1, 'max': 2}                       # SX_POOL_*
+SET_EXCHANGE_FLOATS = 128 * 16                                   # the kernel's LDS exchange buffer, after the image
 
 
 class DiffeqExactTrace(nn.Module):
@@ -51,6 +59,20 @@ class DiffeqExactTraceMLP(DiffeqExactTrace):
     def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, d_h: int, latent_dim: int = 0, return_log_det_jac: bool = True,
                  **kwargs):
         exclusive_net = DiffeqZeroTraceMLP(in_dim, hidden_dims, d_h * out_dim, return_log_det_jac=False, return_per_dim=True)
+        dimwise_net = DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1)
+        super().__init__(exclusive_net, dimwise_net, return_log_det_jac)
+
+
+class DiffeqExactTraceDeepSet(DiffeqExactTrace):
+    """``DiffeqExactTraceDeepSet(dim, hidden_dims, dim, d_h, latent_dim, pooling)`` over sets (..., N, dim): exclusive net
+    DiffeqZeroTraceDeepSet(dim, hidden_dims, d_h * dim, pooling), dimwise net DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1) over
+    the columns [t, x_i[d], h_i[d], latent_i].  `mask` is not passed on (``DiffeqExactTrace.forward``), so every element counts.
+
+    `pooling` reaches the exclusive net (the reference's constructor drops it and always pools by 'max': DESIGN.md 4.11)."""
+
+    def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, d_h: int, latent_dim: int = 0, pooling: str = 'max',
+                 return_log_det_jac: bool = True, **kwargs):
+        exclusive_net = DiffeqZeroTraceDeepSet(in_dim, hidden_dims, d_h * out_dim, pooling=pooling, return_log_det_jac=False)
         dimwise_net = DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1)
         super().__init__(exclusive_net, dimwise_net, return_log_det_jac)
 
@@ -101,6 +123,32 @@ def _structure(net):
             'activations': [a for stack in stacks for a in stack[1::2]]}
 
 
+def _dimwise(s, t, x2, h, lat2, want_jac, cast, dtype):
+    """The dimwise net of a structure dict on rows x2 [R, D] with h [R, D, d_h] and lat2 [R, L] | None -> (f [R, D], jac [R, D] | None):
+    value and tangent d/dx_i side by side."""
+    act, dact = _ACTS[s['act']]
+    d_h = s['d_h']
+    dw = s['dimwise']
+    W1, b1 = cast(dw[0].weight), cast(dw[0].bias)
+    tt = (t.detach() if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).to(device=x2.device, dtype=dtype).reshape(())
+    z = x2.unsqueeze(-1) * W1[:, 1] + h @ W1[:, 2:2 + d_h].t() + tt * W1[:, 0]
+    if b1 is not None:
+        z = z + b1
+    if lat2 is not None:
+        z = z + (lat2 @ W1[:, 2 + d_h:].t()).unsqueeze(-2)
+    a = act(z)
+    tau = dact(a) * W1[:, 1] if want_jac else None
+    for l in dw[1:-1]:
+        W, b = cast(l.weight), cast(l.bias)
+        a_next = act(nn.functional.linear(a, W, b))
+        if want_jac:
+            tau = dact(a_next) * (tau @ W.t())
+        a = a_next
+    wl, bl = cast(dw[-1].weight)[0], cast(dw[-1].bias)
+    f = a @ wl + (0 if bl is None else bl[0])
+    return f, ((tau @ wl) if want_jac else None)
+
+
 def closed_form(net, t, x, latent=None, want_jac: bool = True, dtype=None):
     """(f, jac) of a plain DiffeqExactTraceMLP by its closed form, as torch ops without autograd, in `dtype` (default: x's):
         h     = MADE_1(x) + MADE_2(x)                           (mask * weight)
@@ -127,27 +175,9 @@ def closed_form(net, t, x, latent=None, want_jac: bool = True, dtype=None):
                 a = act(a)
         raw = raw + a
     h = raw.reshape(-1, d_h, D).transpose(-1, -2)                     # [N, D, d_h]: column kk * D + i -> [i, kk]
-    dw = s['dimwise']
-    W1, b1 = cast(dw[0].weight), cast(dw[0].bias)
-    tt = (t.detach() if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).to(device=x.device, dtype=dtype).reshape(())
-    z = x2.unsqueeze(-1) * W1[:, 1] + h @ W1[:, 2:2 + d_h].t() + tt * W1[:, 0]
-    if b1 is not None:
-        z = z + b1
-    if latent is not None:
-        lat2 = latent.detach().to(dtype).reshape(-1, latent.shape[-1])
-        z = z + (lat2 @ W1[:, 2 + d_h:].t()).unsqueeze(-2)
-    a = act(z)
-    tau = dact(a) * W1[:, 1] if want_jac else None
-    for l in dw[1:-1]:
-        W, b = cast(l.weight), cast(l.bias)
-        a_next = act(nn.functional.linear(a, W, b))
-        if want_jac:
-            tau = dact(a_next) * (tau @ W.t())
-        a = a_next
-    wl, bl = cast(dw[-1].weight)[0], cast(dw[-1].bias)
-    f = a @ wl + (0 if bl is None else bl[0])
-    jac = (tau @ wl).reshape(*lead, D) if want_jac else None
-    return f.reshape(*lead, D), jac
+    lat2 = None if latent is None else latent.detach().to(dtype).reshape(-1, latent.shape[-1])
+    f, jac = _dimwise(s, t, x2, h, lat2, want_jac, cast, dtype)
+    return f.reshape(*lead, D), (jac.reshape(*lead, D) if want_jac else None)
 
 
 # ---- the kernel's LDS image -------------------------------------------------------------------------------------------------------
@@ -238,6 +268,191 @@ def kernel_image(s):
             mat(OT if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W)
             vec(OT if last else HT, out_pos, None if l.bias is None else npy(l.bias))
             in_pos = out_pos
+    dw = s['dimwise']
+    W1 = npy(dw[0].weight)
+    h1 = np.arange(W1.shape[0])
+    mat(HT, 1, h1, np.concatenate([[0], pos_in]), W1[:, 1:2 + d_h])
+    vec(HT, h1, None if dw[0].bias is None else npy(dw[0].bias))
+    vec(HT, h1, W1[:, 0])
+    vec(HT, h1, W1[:, 1])
+    if NH == 2:
+        W2 = npy(dw[1].weight)
+        mat(HT, HT, np.arange(W2.shape[0]), h1, W2)
+        vec(HT, np.arange(W2.shape[0]), None if dw[1].bias is None else npy(dw[1].bias))
+    wl = npy(dw[-1].weight)
+    vec(HT, np.arange(wl.shape[1]), wl[0])
+    vec(1, np.arange(1), None if dw[-1].bias is None else npy(dw[-1].bias))
+    w_latent = None
+    if L:
+        w_latent = np.zeros((32 * HT, 32 * ((L + 31) // 32)), np.float32)
+        w_latent[:W1.shape[0], :L] = W1[:, 2 + d_h:]
+    return np.concatenate(parts), w_latent
+
+
+# ---- the set instance -------------------------------------------------------------------------------------------------------------
+def _structure_set(net):
+    """The layers of a DiffeqExactTraceDeepSet-shaped module -> dict, or None when it is not the plain instance: one MADE and two
+    DiffeqMLPs over plain MLPs, none with a final activation, one activation name and the same hidden widths in all three."""
+    ex = net.exclusive_net
+    if type(ex) is not DiffeqZeroTraceDeepSet or type(ex.interaction) is not ZeroTraceEquivariantEncoder:
+        return None
+    made, emb, dim_net = ex.elementwise, ex.interaction.set_emb, net.dimwise_net
+    if type(made) is not MADE or made.final_activation is not None or not made.return_per_dim:
+        return None
+    if any(type(m) is not DiffeqMLP or type(m.net) is not MLP or m.net._wrapped or m.net.final_activation_name is not None
+           for m in (emb, dim_net)):
+        return None
+    act = dim_net.net.activation_name
+    if made.activation != act or emb.net.activation_name != act or ex.interaction.pooling not in POOLINGS:
+        return None
+    stacks = [list(made.net), list(emb.net.net), list(dim_net.net.net)]
+    for stack, kind in zip(stacks, (MaskedLinear, nn.Linear, nn.Linear)):
+        if len(stack) % 2 != 1 or any(not isinstance(l, kind) for l in stack[0::2]):
+            return None
+        if any(type(a) is not getattr(nn, act, None) for a in stack[1::2]):
+            return None
+    lins = [stack[0::2] for stack in stacks]
+    hidden = [l.out_features for l in lins[2][:-1]]
+    if any([l.out_features for l in ls[:-1]] != hidden for ls in lins[:2]):
+        return None
+    D = lins[0][0].in_features
+    out = lins[0][-1].out_features
+    if out % D or lins[2][-1].out_features != 1 or ex.interaction.in_dim != D:
+        return None
+    d_h = out // D
+    if lins[1][0].in_features != D + 1 or lins[1][-1].out_features != d_h:
+        return None
+    L = lins[2][0].in_features - 2 - d_h
+    if L < 0:
+        return None
+    return {'D': D, 'd_h': d_h, 'L': L, 'hidden': hidden, 'act': act, 'pooling': ex.interaction.pooling, 'made': lins[0], 'emb': lins[1],
+            'dimwise': lins[2], 'activations': [a for stack in stacks for a in stack[1::2]]}
+
+
+def closed_form_set(net, t, x, latent=None, want_jac: bool = True, dtype=None):
+    """(f, jac) of a plain DiffeqExactTraceDeepSet over sets x [..., N, D] (a 2-D x is one set) by its closed form, as torch ops
+    without autograd, in `dtype` (default: x's):
+        e_j   = set_emb([t, x_j])                               an MLP, d_h columns
+        p_i   = pool over j != i of e_j                         'sum': (sum_j e_j) - e_i, the sum taken in element order;
+                                                                'mean': that / max(N - 1, 1);  'max': N == 1 -> 0, else per column
+                                                                e_i == first ? second : first (the two largest, duplicates count)
+        h_i[d, :] = MADE(x_i)[d, :] + p_i                       (mask * weight)
+    then the dimwise net with its tangent, as `closed_form`.  This is what sx_cnf_exact_set_flow evaluates per stage."""
+    s = _structure_set(net)
+    if s is None or s['act'] not in _ACTS or not s['hidden']:
+        raise NotImplementedError('closed_form_set: a plain DiffeqExactTraceDeepSet with hidden layers and an activation of the kernel\'s set')
+    act, _ = _ACTS[s['act']]
+    dtype = dtype or x.dtype
+    D, d_h = s['D'], s['d_h']
+    cast = lambda p: None if p is None else p.detach().to(device=x.device, dtype=dtype)
+    x = x.detach().to(dtype)
+    lead, N = x.shape[:-1], x.shape[-2]
+    x2 = x.reshape(-1, D)
+    a = x2
+    for i, l in enumerate(s['made']):
+        a = nn.functional.linear(a, cast(l.mask) * cast(l.weight), cast(l.bias))
+        if i + 1 < len(s['made']):
+            a = act(a)
+    h = a.reshape(-1, d_h, D).transpose(-1, -2)                       # [R, D, d_h]: column kk * D + i -> [i, kk]
+    tt = (t.detach() if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).to(device=x.device, dtype=dtype).reshape(())
+    emb = s['emb']
+    W1 = cast(emb[0].weight)
+    e = x2 @ W1[:, 1:].t() + tt * W1[:, 0]
+    if emb[0].bias is not None:
+        e = e + cast(emb[0].bias)
+    for l in emb[1:]:
+        e = nn.functional.linear(act(e), cast(l.weight), cast(l.bias))
+    e = e.reshape(-1, N, d_h)
+    if N == 1:
+        p = torch.zeros_like(e)
+    elif s['pooling'] == 'max':
+        first, second = torch.topk(e, 2, dim=-2).values.chunk(2, dim=-2)
+        p = torch.where(e == first, second, first)
+    else:
+        tot = e[:, 0]
+        for j in range(1, N):
+            tot = tot + e[:, j]
+        p = tot.unsqueeze(-2) - e
+        if s['pooling'] == 'mean':
+            p = p / max(N - 1, 1)
+    h = h + p.reshape(-1, 1, d_h)
+    lat2 = None if latent is None else latent.detach().to(dtype).expand(*lead, latent.shape[-1]).reshape(-1, latent.shape[-1])
+    f, jac = _dimwise(s, t, x2, h, lat2, want_jac, cast, dtype)
+    return f.reshape(*lead, D), (jac.reshape(*lead, D) if want_jac else None)
+
+
+def kernel_coverage_set(net, dim: int, latent_dim: int, set_size: int):
+    """The structure dict of `net` when sx_cnf_exact_set_flow covers it for sets of `set_size` elements of `dim` features and
+    `latent_dim` latent columns, else None."""
+    from .. import _hip
+    if type(net) is not DiffeqExactTraceDeepSet or not net.return_log_det_jac:
+        return None
+    s = _structure_set(net)
+    if s is None or s['D'] != dim or s['L'] != latent_dim:
+        return None
+    if not 1 <= dim <= MAX_DIM or not 1 <= s['d_h'] <= MAX_DH or latent_dim > MAX_LATENT or not 1 <= set_size <= MAX_SET_SIZE:
+        return None
+    if len(s['hidden']) not in (1, 2) or any(not 1 <= w <= MAX_HIDDEN for w in s['hidden']):
+        return None
+    if _hip.ACT_CODES.get(s['act'], 99) > 6:
+        return None
+    return s
+
+
+def kernel_tensors_set(s):
+    """Every tensor the image is made of: the cache guards (weights, biases AND the MADE's masks)."""
+    ts = []
+    for l in s['made']:
+        ts += [l.weight, l.mask] + ([] if l.bias is None else [l.bias])
+    for l in s['emb'] + s['dimwise']:
+        ts += [l.weight] + ([] if l.bias is None else [l.bias])
+    return ts
+
+
+def kernel_image_set(s):
+    """-> (image [floats] fp32 numpy, w_latent [32 HT, 32 LT] fp32 numpy | None): the layout of include/stribor_hip.h
+    (sx_cnf_exact_set_net).  The masks are multiplied in HERE: a weight entry under a zero mask never reaches the kernel."""
+    D, d_h, L, hidden = s['D'], s['d_h'], s['L'], s['hidden']
+    HT, OT, NH = max(_tiles(w) for w in hidden), _out_tiles(d_h), len(hidden)
+    npy = lambda p: p.detach().cpu().numpy().astype(np.float32)
+    pos_x = _kmap(np.arange(D), 0)
+    cols = np.arange(d_h * D)
+    pos_raw = 32 * ((cols // D) >> 1) + _kmap(cols % D, (cols // D) & 1)
+    kk = np.arange(d_h)
+    pos_e = _kmap(kk >> 1, kk & 1)                                    # slot kk of the embedding: register kk >> 1, lane half kk & 1
+    pos_in = _kmap(1 + (kk >> 1), kk & 1)
+    parts = []
+
+    def vec(n_tiles, pos, values):
+        v = np.zeros(32 * n_tiles, np.float32)
+        if values is not None:
+            v[pos] = values
+        parts.append(v)
+
+    def mat(mt, kt, rpos, cpos, W):
+        Wp = np.zeros((32 * mt, 32 * kt), np.float32)
+        Wp[np.ix_(rpos, cpos)] = W
+        parts.append(_fragment_image(Wp))
+
+    in_pos = pos_x
+    for i, l in enumerate(s['made']):
+        last = i + 1 == len(s['made'])
+        out_pos = pos_raw if last else np.arange(l.out_features)
+        with np.errstate(invalid='ignore'):
+            W = np.where(npy(l.mask) != 0, npy(l.mask) * npy(l.weight), np.float32(0))          # (0 * inf is not 0)
+        mat(OT if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W)
+        vec(OT if last else HT, out_pos, None if l.bias is None else npy(l.bias))
+        in_pos = out_pos
+    in_pos = pos_x
+    for i, l in enumerate(s['emb']):
+        last = i + 1 == len(s['emb'])
+        out_pos = pos_e if last else np.arange(l.out_features)
+        W = npy(l.weight)
+        mat(1 if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W[:, 1:] if i == 0 else W)
+        vec(1 if last else HT, out_pos, None if l.bias is None else npy(l.bias))
+        if i == 0:
+            vec(HT, out_pos, W[:, 0])
+        in_pos = out_pos
     dw = s['dimwise']
     W1 = npy(dw[0].weight)
     h1 = np.arange(W1.shape[0])

@@ -16,6 +16,11 @@ its composition path (divergence_exact_for_sets: N x dim reverse passes with a g
 and scaled.  FLOPs per element and evaluation: every equivariant layer is two GEMMs (the l1 and l2 branches), 2 x 2 (dim H1 + H1 H2 +
 H2 dim), plus five H2 x H1 trace GEMMs, 5 x 2 H2 H1 (padding and the set sums are not counted).
 
+The exact-set line: divergence='exact' over DiffeqExactTraceDeepSet(2, [64, 64], 2, d_h = 4) on sx_cnf_exact_set_flow, the set line's
+(B, N, dim) and grid, against its composition path (FuncAndDiagJac) timed at --set-fallback-sets sets and scaled.  FLOPs per element and
+evaluation: the MADE and the set embedding 2 (D H1 + H1 H2 + H2 d_h D) + 2 (D H1 + H1 H2 + H2 d_h), and per dimension the dimwise net
+as in the exact-trace line (padding and the exchange are not counted).
+
     python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json]
 """
 import argparse
@@ -132,6 +137,28 @@ def main():
           f'{r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path '
           f'{fb:.0f} ms (timed at {ys.shape[0]} sets, scaled) = {r["composed_over_kernel"]:.0f} x; kernel vs composition max abs '
           f'x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
+    # the exact-trace set net
+    torch.manual_seed(0)
+    d_h = 4
+    f = st.ContinuousTransform(D, net=st.net.DiffeqExactTraceDeepSet(D, hidden, D, d_h), divergence='exact', solver='rk4',
+                               solver_options={'step_size': 1.0 / a.steps}).eval().to('cuda')
+    flop_eval = 2 * (D * H1 + H1 * H2 + H2 * d_h * D) + 2 * (D * H1 + H1 * H2 + H2 * d_h) + D * (2 * (1 + d_h) * H1 + 4 * H1 * H2 + 4 * H2)
+    with torch.no_grad():
+        ms = timed(lambda: f.inverse_and_log_det_jacobian(y), a.reps)
+        assert f._last_path == 'kernel'
+        ms_x = timed(lambda: f.inverse(y), a.reps)
+        fb = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=1) * (B / ys.shape[0])
+        xk, lk = f.inverse_and_log_det_jacobian(ys)
+        xc, lc = f._composed_reference(ys, reverse=True)
+    fl = B * N * 4 * a.steps * flop_eval
+    r = results[f'exact_set_b{B}_n{N}_dim{D}_dh{d_h}_h{"x".join(map(str, hidden))}'] = {
+        'solve_ldj_ms': ms, 'solve_only_ms': ms_x, 'composed_ms_scaled': fb, 'rows_per_s': B * N / ms * 1e3, 'tflops': fl / ms / 1e9,
+        'frac_of_peak': fl / (ms * 1e-3) / PEAK_F32_MFMA, 'composed_over_kernel': fb / ms,
+        'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item()}
+    print(f'exact-trace sets (B, N, dim) = ({B}, {N}, {D}) d_h {d_h} {hidden} rk4 x {a.steps}: solve + log-det {ms:.2f} ms '
+          f'({r["rows_per_s"]:.3g} elements/s, {r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone '
+          f'{ms_x:.2f} ms; composition path {fb:.0f} ms (timed at {ys.shape[0]} sets, scaled) = {r["composed_over_kernel"]:.1f} x; kernel '
+          f'vs composition max abs x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
     results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows}
     if a.json:
         with open(a.json, 'w') as fh:
