@@ -24,126 +24,35 @@
 // Coverage: dim <= 64 (<= 32 with two hidden layers wider than 64 units: that kernel would spill), 1 + dim + latent_dim <= 128,
 // one or two hidden layers of <= 128 units, activations Identity / Tanh /
 // ReLU / Sigmoid / ELU / Softplus / LeakyReLU (the ones whose derivative is a function of the activation's OUTPUT).
-#include "sx_common.h"
-
-#define SX_CNF_WAVES 4
-#define SX_CNF_THREADS (SX_CNF_WAVES * 64)
+#include "sx_cnf_common.h"
 
 namespace {
-
-__host__ __device__ inline int cn_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-extern __shared__ __attribute__((aligned(16))) float cn_smem[];
-
-__device__ __forceinline__ float cn_act(float v, int act) {
-    switch (act) {
-        case SX_ACT_TANH: return tanhf(v);
-        case SX_ACT_RELU: return fmaxf(v, 0.f);
-        case SX_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        case SX_ACT_ELU: return v > 0.f ? v : expm1f(v);
-        case SX_ACT_SOFTPLUS: return v > 20.f ? v : log1pf(expf(v));
-        case SX_ACT_LEAKYRELU: return v > 0.f ? v : 0.01f * v;
-        default: return v;
-    }
-}
-
-// act'(v) from a = act(v)
-__device__ __forceinline__ float cn_dact(float a, int act) {
-    switch (act) {
-        case SX_ACT_TANH: return 1.f - a * a;
-        case SX_ACT_RELU: return a > 0.f ? 1.f : 0.f;
-        case SX_ACT_SIGMOID: return a * (1.f - a);
-        case SX_ACT_ELU: return a > 0.f ? 1.f : a + 1.f;
-        case SX_ACT_SOFTPLUS: return 1.f - expf(-a);            // sigmoid(v) = 1 - exp(-softplus(v))
-        case SX_ACT_LEAKYRELU: return a > 0.f ? 1.f : 0.01f;
-        default: return 1.f;
-    }
-}
 
 // (inlined on purpose: an out-of-line call would spill the live stage vectors around it)
 __device__ __forceinline__ void cn_act_tile(f32x16 *v, int act) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) (*v)[r] = cn_act((*v)[r], act);
+    for (int r = 0; r < 16; ++r) (*v)[r] = cnf_act((*v)[r], act);
 }
 
 __device__ __forceinline__ void cn_dact_tile(f32x16 *v, int act) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) (*v)[r] = cn_dact((*v)[r], act);
-}
-
-template <int T>
-struct ctile {
-    f32x16 v[T];
-};
-
-// LDS image of a matrix block: MT x KT A-operand tiles of 1024 floats (tile (m, c), float g*256 + lane*4 + j holds
-// W[32m + (lane & 31)][col0 + 32c + kmap(4g + j, lane >> 5)]), W row-major with row stride ld
-__device__ __forceinline__ void cn_stage(const float *__restrict__ W, int out_dim, int in_dim, int ld, int col0, int MT, int KT, int base) {
-    const int n_w = MT * KT * 1024;
-    for (int e = threadIdx.x; e < n_w; e += SX_CNF_THREADS) {
-        const int tile = e >> 10, rem = e & 1023;
-        const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
-        const int m = tile / KT, c = tile - m * KT;
-        const int row = 32 * m + (lane & 31), col = 32 * c + cn_kmap(4 * g + j, lane >> 5);
-        cn_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * ld + col0 + col] : 0.f;
-    }
-}
-
-// a vector of n_pad floats (entries beyond n: 0), element i at stride `stride` of src (NULL: zeros)
-__device__ __forceinline__ void cn_stage_vec(const float *__restrict__ src, int n, int stride, int n_pad, int base) {
-    for (int i = threadIdx.x; i < n_pad; i += SX_CNF_THREADS)
-        cn_smem[base + i] = (src != nullptr && i < n) ? src[(int64_t)i * stride] : 0.f;
+    for (int r = 0; r < 16; ++r) (*v)[r] = cnf_dact((*v)[r], act);
 }
 
 // out[m] = (W . in)[m], m < MT; W: an image at `wb` (already offset by lane * 4), KT input tiles
 template <int KT, int MT>
-__device__ __forceinline__ void cn_gemm(const ctile<KT> &in, ctile<MT> &out, const float *wb) {
+__device__ __forceinline__ void cn_gemm(const cnf_tile<KT> &in, cnf_tile<MT> &out, const float *wb) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         f32x16 acc = {};
-#pragma unroll
-        for (int c = 0; c < KT; ++c) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(wb + (m * KT + c) * 1024 + g * 256);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in.v[c][4 * g + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in.v[c][4 * g + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in.v[c][4 * g + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in.v[c][4 * g + 3], acc, 0, 0, 0);
-            }
-        }
+        cnf_mma<KT>(acc, in, wb + m * KT * 1024);
         out.v[m] = acc;
     }
 }
 
-// the same product with the matrix read from global memory: row-major [MT * 32][KT * 32], zero-padded (a lane's four A values
-// of k-group g are the contiguous columns 32c + 8g + 4h .. + 3 of row 32m + (lane & 31))
-template <int KT, int MT>
-__device__ __forceinline__ void cn_gemm_global(const ctile<KT> &in, ctile<MT> &out, const float *__restrict__ W, int lane) {
-    const float *wl = W + (int64_t)(lane & 31) * (KT * 32) + 4 * (lane >> 5);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        f32x16 acc = {};
-#pragma unroll
-        for (int c = 0; c < KT; ++c) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(wl + (int64_t)m * 32 * (KT * 32) + 32 * c + 8 * g);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in.v[c][4 * g + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in.v[c][4 * g + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in.v[c][4 * g + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in.v[c][4 * g + 3], acc, 0, 0, 0);
-            }
-        }
-        out.v[m] = acc;
-    }
-}
-
-// feature 32m + kmap(r, h) of a padded vector at `vb` (already offset by 4 * h)
-__device__ __forceinline__ float cn_vec(const float *vb, int m, int r) { return vb[32 * m + 8 * (r >> 2) + (r & 3)]; }
-
+// this file's own sweep, not cnf_act_all: with that one the (1, 4, 2)-tile kernel spills (30 VGPRs, 124 bytes of scratch per lane)
 template <int T>
-__device__ __forceinline__ void cn_act_all(ctile<T> &v, int act) {
+__device__ __forceinline__ void cn_act_all(cnf_tile<T> &v, int act) {
 #pragma unroll
     for (int m = 0; m < T; ++m) {
         if (act == SX_ACT_RELU) {
@@ -172,47 +81,47 @@ struct cn_args {
 
 // f(t, x) and -- when `want` -- tr = tr df/dx for the wave's 32 rows
 template <int DT, int HT, int NH>
-__device__ __forceinline__ void cn_eval(const cn_args &a, const ctile<DT> &xin, float t, const ctile<HT> &lat, ctile<DT> &k, bool want, float &tr,
+__device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xin, float t, const cnf_tile<HT> &lat, cnf_tile<DT> &k, bool want, float &tr,
                                         int lane) {
     const int h = lane >> 5, act = a.net.act;
     // the weights in LDS never change, so their loads are loop-invariant: without this the compiler hoists them out of the step
     // loop and holds whole matrices in registers
     asm volatile("" ::: "memory");
-    const float *b1 = cn_smem + a.base_b[0] + 4 * h, *w0 = cn_smem + a.base_w0 + 4 * h;
-    ctile<HT> h1;
-    cn_gemm<DT, HT>(xin, h1, cn_smem + a.base_w[0] + lane * 4);
+    const float *b1 = cnf_smem + a.base_b[0] + 4 * h, *w0 = cnf_smem + a.base_w0 + 4 * h;
+    cnf_tile<HT> h1;
+    cn_gemm<DT, HT>(xin, h1, cnf_smem + a.base_w[0] + lane * 4);
 #pragma unroll
     for (int m = 0; m < HT; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) h1.v[m][r] = (h1.v[m][r] + lat.v[m][r]) + (cn_vec(b1, m, r) + t * cn_vec(w0, m, r));
+        for (int r = 0; r < 16; ++r) h1.v[m][r] = (h1.v[m][r] + lat.v[m][r]) + (cnf_vec(b1, m, r) + t * cnf_vec(w0, m, r));
     cn_act_all<HT>(h1, act);
     float s = 0.f;
     if (NH == 1) {
         if (want) {
-            const float *cv = cn_smem + a.base_tr + 4 * h;
+            const float *cv = cnf_smem + a.base_tr + 4 * h;
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
                 f32x16 d = h1.v[m];
                 if (act != SX_ACT_IDENTITY) cn_dact_tile(&d, act);
                 else d = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
 #pragma unroll
-                for (int r = 0; r < 16; ++r) s += d[r] * cn_vec(cv, m, r);
+                for (int r = 0; r < 16; ++r) s += d[r] * cnf_vec(cv, m, r);
             }
         }
-        cn_gemm<HT, DT>(h1, k, cn_smem + a.base_w[1] + lane * 4);
-        const float *b2 = cn_smem + a.base_b[1] + 4 * h;
+        cn_gemm<HT, DT>(h1, k, cnf_smem + a.base_w[1] + lane * 4);
+        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
 #pragma unroll
         for (int m = 0; m < DT; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) k.v[m][r] += cn_vec(b2, m, r);
+            for (int r = 0; r < 16; ++r) k.v[m][r] += cnf_vec(b2, m, r);
     } else {
-        ctile<HT> h2;
-        cn_gemm<HT, HT>(h1, h2, cn_smem + a.base_w[1] + lane * 4);
-        const float *b2 = cn_smem + a.base_b[1] + 4 * h;
+        cnf_tile<HT> h2;
+        cn_gemm<HT, HT>(h1, h2, cnf_smem + a.base_w[1] + lane * 4);
+        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
 #pragma unroll
         for (int m = 0; m < HT; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) h2.v[m][r] += cn_vec(b2, m, r);
+            for (int r = 0; r < 16; ++r) h2.v[m][r] += cnf_vec(b2, m, r);
         cn_act_all<HT>(h2, act);
         if (want) {
             // h1 <- d1, v = C d1, s = d2 . v
@@ -224,23 +133,23 @@ __device__ __forceinline__ void cn_eval(const cn_args &a, const ctile<DT> &xin, 
             // v = C d1 one 32-row tile at a time, consumed at once: s += d2 . v
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
-                ctile<1> v;
-                if (a.c_in_lds) cn_gemm<HT, 1>(h1, v, cn_smem + a.base_tr + m * HT * 1024 + lane * 4);
-                else cn_gemm_global<HT, 1>(h1, v, a.net.trace + (int64_t)m * 32 * (HT * 32), lane);
+                f32x16 v = {};
+                if (a.c_in_lds) cnf_mma<HT>(v, h1, cnf_smem + a.base_tr + m * HT * 1024 + lane * 4);
+                else cnf_mma_global<HT>(v, h1, a.net.trace + (int64_t)m * 32 * (HT * 32), lane);
                 f32x16 d = h2.v[m];
                 if (act != SX_ACT_IDENTITY) cn_dact_tile(&d, act);
                 else d = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
 #pragma unroll
-                for (int r = 0; r < 16; ++r) s += d[r] * v.v[0][r];
+                for (int r = 0; r < 16; ++r) s += d[r] * v[r];
             }
         }
         asm volatile("" ::: "memory");
-        cn_gemm<HT, DT>(h2, k, cn_smem + a.base_w[2] + lane * 4);
-        const float *b3 = cn_smem + a.base_b[2] + 4 * h;
+        cn_gemm<HT, DT>(h2, k, cnf_smem + a.base_w[2] + lane * 4);
+        const float *b3 = cnf_smem + a.base_b[2] + 4 * h;
 #pragma unroll
         for (int m = 0; m < DT; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) k.v[m][r] += cn_vec(b3, m, r);
+            for (int r = 0; r < 16; ++r) k.v[m][r] += cnf_vec(b3, m, r);
     }
     if (want) tr = s + __shfl_xor(s, 32, 64);          // the two lane halves hold the two feature halves of a row
 }
@@ -249,20 +158,20 @@ template <int DT, int HT, int NH>
 __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args a) {
     const sx_cnf_net &net = a.net;
     const int D = net.dim, L = net.latent_dim, in_dim = 1 + D + L, H1 = net.layer[0].out_dim;
-    cn_stage(net.layer[0].W, H1, D, in_dim, 1, HT, DT, a.base_w[0]);
-    cn_stage_vec(net.layer[0].b, H1, 1, HT * 32, a.base_b[0]);
-    cn_stage_vec(net.layer[0].W, H1, in_dim, HT * 32, a.base_w0);
+    cnf_stage(net.layer[0].W, H1, D, in_dim, 1, HT, DT, a.base_w[0]);
+    cnf_stage_vec(net.layer[0].b, H1, 1, HT * 32, a.base_b[0]);
+    cnf_stage_vec(net.layer[0].W, H1, in_dim, HT * 32, a.base_w0);
     if (NH == 1) {
-        cn_stage(net.layer[1].W, D, H1, H1, 0, DT, HT, a.base_w[1]);
-        cn_stage_vec(net.layer[1].b, D, 1, DT * 32, a.base_b[1]);
-        cn_stage_vec(a.want_ldj ? net.trace : nullptr, H1, 1, HT * 32, a.base_tr);
+        cnf_stage(net.layer[1].W, D, H1, H1, 0, DT, HT, a.base_w[1]);
+        cnf_stage_vec(net.layer[1].b, D, 1, DT * 32, a.base_b[1]);
+        cnf_stage_vec(a.want_ldj ? net.trace : nullptr, H1, 1, HT * 32, a.base_tr);
     } else {
         const int H2 = net.layer[1].out_dim;
-        cn_stage(net.layer[1].W, H2, H1, H1, 0, HT, HT, a.base_w[1]);
-        cn_stage_vec(net.layer[1].b, H2, 1, HT * 32, a.base_b[1]);
-        cn_stage(net.layer[2].W, D, H2, H2, 0, DT, HT, a.base_w[2]);
-        cn_stage_vec(net.layer[2].b, D, 1, DT * 32, a.base_b[2]);
-        if (a.want_ldj && a.c_in_lds) cn_stage(net.trace, HT * 32, HT * 32, HT * 32, 0, HT, HT, a.base_tr);
+        cnf_stage(net.layer[1].W, H2, H1, H1, 0, HT, HT, a.base_w[1]);
+        cnf_stage_vec(net.layer[1].b, H2, 1, HT * 32, a.base_b[1]);
+        cnf_stage(net.layer[2].W, D, H2, H2, 0, DT, HT, a.base_w[2]);
+        cnf_stage_vec(net.layer[2].b, D, 1, DT * 32, a.base_b[2]);
+        if (a.want_ldj && a.c_in_lds) cnf_stage(net.trace, HT * 32, HT * 32, HT * 32, 0, HT, HT, a.base_tr);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, h = lane >> 5;
@@ -273,16 +182,16 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
          grp += (int64_t)gridDim.x * SX_CNF_WAVES) {
         const int64_t row = grp * 32 + (lane & 31);
         const bool live = row < a.n_rows;
-        ctile<DT> y;
+        cnf_tile<DT> y;
 #pragma unroll
         for (int c = 0; c < DT; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + cn_kmap(r, h);
+                const int f = 32 * c + cnf_kmap(r, h);
                 y.v[c][r] = (live && f < D) ? a.x[row * D + f] : 0.f;
             }
         // the latent share of the first layer: W1[:, 1 + D ..] . latent_row, once per row
-        ctile<HT> lat;
+        cnf_tile<HT> lat;
 #pragma unroll
         for (int m = 0; m < HT; ++m) lat.v[m] = f32x16{};
         if (L > 0) {
@@ -291,7 +200,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
                 f32x16 lb;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * c + cn_kmap(r, h);
+                    const int f = 32 * c + cnf_kmap(r, h);
                     lb[r] = (live && f < L) ? a.latent[row * L + f] : 0.f;
                 }
 #pragma unroll
@@ -299,7 +208,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
                     const int wr = 32 * m + (lane & 31);
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const int f = 32 * c + cn_kmap(q, h);
+                        const int f = 32 * c + cnf_kmap(q, h);
                         const float av = (wr < H1 && f < L) ? W1[(int64_t)wr * in_dim + 1 + D + f] : 0.f;
                         lat.v[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, lb[q], lat.v[m], 0, 0, 0);
                     }
@@ -307,72 +216,20 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
             }
         }
         float l = 0.f;
-        const int n_stages = a.solver == SX_CNF_EULER ? 1 : a.solver == SX_CNF_MIDPOINT ? 2 : 4;
+        const int n_stages = cnf_stages(a.solver);
         const float third = 1.f / 3.f, two_thirds = 2.f / 3.f;
         for (int i = 0; i < a.n_steps; ++i) {
-            // the grid: t_i = t0 +- i * step_size, the last point replaced by t1
-            const float ta = i == 0 ? a.t0 : a.t0 + sgn * ((float)i * a.step_size);
-            const float tb = i + 1 == a.n_steps ? a.t1 : a.t0 + sgn * ((float)(i + 1) * a.step_size);
+            float ta, tb;
+            cnf_grid(a, sgn, i, ta, tb);
             const float dt = tb - ta, half = 0.5f * dt;
-            ctile<DT> k1, k2, xs = y;          // (rk4: after stage 3, k1 holds k1 + 3 (k2 + k3))
+            cnf_tile<DT> k1, k2, xs = y;          // (rk4: after stage 3, k1 holds k1 + 3 (k2 + k3))
             float q1 = 0.f, q2 = 0.f, ts = ta;
             // one copy of the network's code serves every stage: the stage index is wave-uniform
             for (int st = 0; st < n_stages; ++st) {
-                ctile<DT> k;
+                cnf_tile<DT> k;
                 float q = 0.f;
                 cn_eval<DT, HT, NH>(a, xs, ts, lat, k, want, q, lane);
-                if (a.solver == SX_CNF_EULER) {                       // y += dt f(t, y)
-#pragma unroll
-                    for (int c = 0; c < DT; ++c)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) y.v[c][r] = y.v[c][r] + dt * k.v[c][r];
-                    l = l + dt * q;
-                } else if (a.solver == SX_CNF_MIDPOINT) {             // y += dt f(t + dt/2, y + f(t, y) dt/2)
-                    if (st == 0) {
-#pragma unroll
-                        for (int c = 0; c < DT; ++c)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + k.v[c][r] * half;
-                        ts = ta + half;
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < DT; ++c)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) y.v[c][r] = y.v[c][r] + dt * k.v[c][r];
-                        l = l + dt * q;
-                    }
-                } else if (st == 0) {                                 // rk4, the 3/8 rule
-                    k1 = k; q1 = q;
-#pragma unroll
-                    for (int c = 0; c < DT; ++c)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + (dt * k1.v[c][r]) * third;
-                    ts = ta + dt * third;
-                } else if (st == 1) {
-                    k2 = k; q2 = q;
-#pragma unroll
-                    for (int c = 0; c < DT; ++c)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + dt * (k2.v[c][r] - k1.v[c][r] * third);
-                    ts = ta + dt * two_thirds;
-                } else if (st == 2) {
-#pragma unroll
-                    for (int c = 0; c < DT; ++c)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            xs.v[c][r] = y.v[c][r] + dt * ((k1.v[c][r] - k2.v[c][r]) + k.v[c][r]);
-                            k1.v[c][r] = k1.v[c][r] + 3.f * (k2.v[c][r] + k.v[c][r]);
-                        }
-                    q1 = q1 + 3.f * (q2 + q);
-                    ts = tb;
-                } else {
-#pragma unroll
-                    for (int c = 0; c < DT; ++c)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            y.v[c][r] = y.v[c][r] + ((k1.v[c][r] + k.v[c][r]) * dt) * 0.125f;
-                    l = l + ((q1 + q) * dt) * 0.125f;
-                }
+                cnf_tableau<DT>(a.solver, st, ta, tb, dt, half, third, two_thirds, k, q, k1, k2, q1, q2, xs, ts, y, l);
             }
         }
         if (live) {
@@ -380,7 +237,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * c + cn_kmap(r, h);
+                    const int f = 32 * c + cnf_kmap(r, h);
                     if (f < D) a.y[row * D + f] = y.v[c][r];
                 }
             if (want && h == 0) a.ldj[row] = l;
@@ -388,13 +245,11 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
     }
 }
 
-inline int cn_tiles(int n) { return n <= 32 ? 1 : n <= 64 ? 2 : 4; }
-
 // the LDS plan: float offsets into `a` (may be null), -> floats used.  C goes into LDS when it fits beside the rest.
 size_t cn_plan(const sx_cnf_net &net, int want_ldj, cn_args *a) {
-    const int DT = cn_tiles(net.dim), NH = net.n_layers - 1;
+    const int DT = cnf_tiles(net.dim), NH = net.n_layers - 1;
     int HT = 1;
-    for (int l = 0; l < NH; ++l) HT = cn_tiles(net.layer[l].out_dim) > HT ? cn_tiles(net.layer[l].out_dim) : HT;
+    for (int l = 0; l < NH; ++l) HT = cnf_tiles(net.layer[l].out_dim) > HT ? cnf_tiles(net.layer[l].out_dim) : HT;
     size_t off = 0;
     int bw[3] = {0, 0, 0}, bb[3] = {0, 0, 0};
     for (int l = 0; l <= NH; ++l) {
@@ -438,31 +293,6 @@ int cn_check_net(const sx_cnf_net *net_host) {
     return SX_OK;
 }
 
-template <int DT, int HT, int NH>
-int cn_launch(const cn_args &a, size_t lds, void *stream) {
-    auto kern = cnf_flow_kernel<DT, HT, NH>;
-    static bool raised_on[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!raised_on[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SX_CNF_LDS_BYTES);
-        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        raised_on[dev & 63] = true;
-    }
-    int cus = 0, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, SX_CNF_THREADS, lds);
-    if (cus < 1) cus = 1;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t n_groups = (a.n_rows + 31) / 32;
-    const int64_t want = (n_groups + SX_CNF_WAVES - 1) / SX_CNF_WAVES;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const int grid = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SX_CNF_THREADS), lds, sx_stream(stream), a);
-    SX_LAUNCH_CHECK();
-    return SX_OK;
-}
-
 }  // namespace
 
 extern "C" size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj) {
@@ -475,10 +305,8 @@ extern "C" int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const flo
     const int rc = cn_check_net(net_host);
     if (rc != SX_OK) return rc;
     const sx_cnf_net &net = *net_host;
-    SX_REQUIRE(solver >= SX_CNF_EULER && solver <= SX_CNF_RK4, "sx_cnf_flow: solver must be euler (0), midpoint (1) or rk4 (2), got %d", solver);
-    SX_REQUIRE(n_rows >= 0 && n_steps >= 0, "sx_cnf_flow: negative n_rows / n_steps");
-    SX_REQUIRE(n_steps <= 1 || step_size > 0.f, "sx_cnf_flow: a grid of %d steps needs step_size > 0", n_steps);
-    SX_REQUIRE(x != nullptr && y != nullptr, "sx_cnf_flow: null input / output");
+    const int rc_call = cnf_check_call("sx_cnf_flow", solver, n_rows, 1, n_steps, step_size, x, y);
+    if (rc_call != SX_OK) return rc_call;
     SX_REQUIRE(net.latent_dim == 0 || latent != nullptr, "sx_cnf_flow: latent rows missing");
     SX_REQUIRE(!want_ldj || (ldj != nullptr && net.trace != nullptr), "sx_cnf_flow: want_ldj needs ldj and the trace constants");
     cn_args a{};
@@ -489,14 +317,17 @@ extern "C" int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const flo
     a.x = x; a.latent = latent; a.y = y; a.ldj = ldj; a.n_rows = n_rows;
     a.solver = solver; a.n_steps = n_steps; a.want_ldj = want_ldj ? 1 : 0;
     a.t0 = t0; a.t1 = t1; a.step_size = step_size;
-    const int DT = cn_tiles(net.dim), NH = net.n_layers - 1;
+    const int DT = cnf_tiles(net.dim), NH = net.n_layers - 1;
     int HT = 1;
-    for (int l = 0; l < NH; ++l) HT = cn_tiles(net.layer[l].out_dim) > HT ? cn_tiles(net.layer[l].out_dim) : HT;
-#define CN_CASE(D_, H_) \
-    if (DT == D_ && HT == H_) return NH == 1 ? cn_launch<D_, H_, 1>(a, lds, stream) : cn_launch<D_, H_, 2>(a, lds, stream);
+    for (int l = 0; l < NH; ++l) HT = cnf_tiles(net.layer[l].out_dim) > HT ? cnf_tiles(net.layer[l].out_dim) : HT;
+    const int64_t want = cnf_row_blocks(n_rows);
+#define CN_CASE(D_, H_)                                                                                  \
+    if (DT == D_ && HT == H_)                                                                            \
+        return NH == 1 ? cnf_launch<cnf_flow_kernel<D_, H_, 1>>("sx_cnf_flow", a, lds, want, stream)     \
+                       : cnf_launch<cnf_flow_kernel<D_, H_, 2>>("sx_cnf_flow", a, lds, want, stream);
     CN_CASE(1, 1) CN_CASE(1, 2) CN_CASE(1, 4) CN_CASE(2, 1) CN_CASE(2, 2)
 #undef CN_CASE
-    if (DT == 2 && HT == 4 && NH == 1) return cn_launch<2, 4, 1>(a, lds, stream);
+    if (DT == 2 && HT == 4 && NH == 1) return cnf_launch<cnf_flow_kernel<2, 4, 1>>("sx_cnf_flow", a, lds, want, stream);
     sx_set_error("sx_cnf_flow: no kernel for %d x %d tiles", DT, HT);
     return SX_E_BADARG;
 }

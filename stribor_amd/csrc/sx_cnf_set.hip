@@ -8,7 +8,7 @@
 //     one hidden layer   tr_i = d1_i . c_d + sum_j d1_j . c_s
 //     two hidden layers  tr_i = d2_i^T (C_abd d1_i + C_c s1) + s2^T (C_f d1_i + C_g s1) + sum_j d2_j^T C_e d1_j
 // with weight-only constants passed in (fp32, derived in fp64 by the caller).
-//   * the conventions of sx_cnf.hip: one wave = 32 rows on the MFMA column, features on the C rows, exact fp32
+//   * the conventions of sx_cnf_common.h: one wave = 32 rows on the MFMA column, features on the C rows, exact fp32
 //     (v_mfma_f32_32x32x2_f32), weights in LDS in A-fragment order, state / stage vectors / log-det in registers for the whole grid,
 //     the same solvers, grid, tableau roundings (-ffp-contract=off) and activations;
 //   * a workgroup of 4 waves owns 128 row slots and takes floor(128 / N) WHOLE sets per pass: sets never straddle workgroups, they
@@ -26,127 +26,25 @@
 //     as still fit SX_CNF_LDS_BYTES; the others are read from global memory (row-major, zero-padded: 16 KiB each, L2-resident).
 //
 // Coverage: 1 <= N <= 128, dim <= 32, 1 + dim + latent_dim <= 64, one or two hidden layers of <= 64 units, the seven activations of
-// sx_cnf.hip, no final activation, no mask.
-#include "sx_common.h"
-
-#define SX_CS_WAVES 4
-#define SX_CS_THREADS (SX_CS_WAVES * 64)
-#define SX_CS_ROWS (SX_CS_WAVES * 32)
+// sx_cnf_common.h, no final activation, no mask.
+#include "sx_cnf_common.h"
 
 namespace {
 
-__host__ __device__ inline int cs_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-extern __shared__ __attribute__((aligned(16))) float cs_smem[];
-
-__device__ __forceinline__ float cs_act(float v, int act) {
-    switch (act) {
-        case SX_ACT_TANH: return tanhf(v);
-        case SX_ACT_RELU: return fmaxf(v, 0.f);
-        case SX_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        case SX_ACT_ELU: return v > 0.f ? v : expm1f(v);
-        case SX_ACT_SOFTPLUS: return v > 20.f ? v : log1pf(expf(v));
-        case SX_ACT_LEAKYRELU: return v > 0.f ? v : 0.01f * v;
-        default: return v;
-    }
-}
-
-// act'(v) from a = act(v)
-__device__ __forceinline__ float cs_dact(float a, int act) {
-    switch (act) {
-        case SX_ACT_TANH: return 1.f - a * a;
-        case SX_ACT_RELU: return a > 0.f ? 1.f : 0.f;
-        case SX_ACT_SIGMOID: return a * (1.f - a);
-        case SX_ACT_ELU: return a > 0.f ? 1.f : a + 1.f;
-        case SX_ACT_SOFTPLUS: return 1.f - expf(-a);            // sigmoid(v) = 1 - exp(-softplus(v))
-        case SX_ACT_LEAKYRELU: return a > 0.f ? 1.f : 0.01f;
-        default: return 1.f;
-    }
-}
-
 template <int T>
-struct stile {
-    f32x16 v[T];
-};
-
-template <int T>
-__device__ __forceinline__ void cs_act_all(stile<T> &v, int act) {
-    if (act == SX_ACT_IDENTITY) return;
+__device__ __forceinline__ void cs_dact_all(cnf_tile<T> &v, int act) {
 #pragma unroll
     for (int m = 0; m < T; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v.v[m][r] = cs_act(v.v[m][r], act);
+        for (int r = 0; r < 16; ++r) v.v[m][r] = cnf_dact(v.v[m][r], act);
 }
-
-template <int T>
-__device__ __forceinline__ void cs_dact_all(stile<T> &v, int act) {
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v.v[m][r] = cs_dact(v.v[m][r], act);
-}
-
-// LDS image of a matrix block, as sx_cnf.hip's: MT x KT A-operand tiles of 1024 floats (tile (m, c), float g*256 + lane*4 + j holds
-// W[32m + (lane & 31)][col0 + 32c + kmap(4g + j, lane >> 5)]), W row-major with row stride ld
-__device__ __forceinline__ void cs_stage(const float *__restrict__ W, int out_dim, int in_dim, int ld, int col0, int MT, int KT, int base) {
-    const int n_w = MT * KT * 1024;
-    for (int e = threadIdx.x; e < n_w; e += SX_CS_THREADS) {
-        const int tile = e >> 10, rem = e & 1023;
-        const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
-        const int m = tile / KT, c = tile - m * KT;
-        const int row = 32 * m + (lane & 31), col = 32 * c + cs_kmap(4 * g + j, lane >> 5);
-        cs_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * ld + col0 + col] : 0.f;
-    }
-}
-
-// a vector of n_pad floats (entries beyond n: 0; src NULL: zeros)
-__device__ __forceinline__ void cs_stage_vec(const float *__restrict__ src, int n, int n_pad, int base) {
-    for (int i = threadIdx.x; i < n_pad; i += SX_CS_THREADS) cs_smem[base + i] = (src != nullptr && i < n) ? src[i] : 0.f;
-}
-
-// acc += (tile row of W) . in: the KT A tiles at `wb` (an LDS image's tile (m, 0), already offset by lane * 4)
-template <int KT>
-__device__ __forceinline__ void cs_mma(f32x16 &acc, const stile<KT> &in, const float *wb) {
-#pragma unroll
-    for (int c = 0; c < KT; ++c) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(wb + c * 1024 + g * 256);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in.v[c][4 * g + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in.v[c][4 * g + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in.v[c][4 * g + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in.v[c][4 * g + 3], acc, 0, 0, 0);
-        }
-    }
-}
-
-// the same with the 32 matrix rows read from global memory: `W` = row 32m of a row-major matrix of KT * 32 columns, zero-padded (a
-// lane's four A values of k-group g are the contiguous columns 32c + 8g + 4h .. + 3 of row lane & 31)
-template <int KT>
-__device__ __forceinline__ void cs_mma_global(f32x16 &acc, const stile<KT> &in, const float *__restrict__ W, int lane) {
-    const float *wl = W + (int64_t)(lane & 31) * (KT * 32) + 4 * (lane >> 5);
-#pragma unroll
-    for (int c = 0; c < KT; ++c) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(wl + 32 * c + 8 * g);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in.v[c][4 * g + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in.v[c][4 * g + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in.v[c][4 * g + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in.v[c][4 * g + 3], acc, 0, 0, 0);
-        }
-    }
-}
-
-// feature 32m + kmap(r, h) of a padded vector at `vb` (already offset by 4 * h)
-__device__ __forceinline__ float cs_vec(const float *vb, int m, int r) { return vb[32 * m + 8 * (r >> 2) + (r & 3)]; }
 
 struct cs_args {
     sx_cnf_set_net net;
     int base_a[3], base_g[3], base_b[3];          // LDS float offsets of the A / G images and the biases
     int base_w0;                                  // ... of the time column
     int base_tr;                                  // ... of c_d, c_s (one hidden layer) or the first n_c_lds C images (two)
-    int base_x;                                   // ... of the exchange scratch [SX_CS_ROWS][32 HT + 4]
+    int base_x;                                   // ... of the exchange scratch [SX_CNF_ROWS][32 HT + 4]
     int n_c_lds;
     const float *x;
     const float *latent;
@@ -159,7 +57,7 @@ struct cs_args {
 
 // where a lane stands in its workgroup's pass
 struct cs_pos {
-    int rho;            // row slot 0 .. SX_CS_ROWS - 1
+    int rho;            // row slot 0 .. SX_CNF_ROWS - 1
     int first;          // the first slot of the row's set (a padding slot: itself)
     int n_sets;         // whole sets of this pass
 };
@@ -167,7 +65,7 @@ struct cs_pos {
 // out = the sum of `in` over the rows of the lane's set, e_out = that of the per-row scalar e_in (both lane halves pass the same
 // e_in).  LD = the scratch's row stride (floats).  Uniform over the workgroup: every thread must call it.
 template <int T, int LD>
-__device__ __forceinline__ void cs_setsum(const cs_args &a, const cs_pos &p, const stile<T> &in, stile<T> &out, float e_in, float &e_out,
+__device__ __forceinline__ void cs_setsum(const cs_args &a, const cs_pos &p, const cnf_tile<T> &in, cnf_tile<T> &out, float e_in, float &e_out,
                                           int lane) {
     const int N = a.net.set_size;
     if (N == 1) {
@@ -175,7 +73,7 @@ __device__ __forceinline__ void cs_setsum(const cs_args &a, const cs_pos &p, con
         e_out = e_in;
         return;
     }
-    float *xs = cs_smem + a.base_x;
+    float *xs = cnf_smem + a.base_x;
     const int h = lane >> 5;
     __syncthreads();                    // the reads of the previous exchange are over
     float *mine = xs + p.rho * LD + 4 * h;
@@ -188,7 +86,7 @@ __device__ __forceinline__ void cs_setsum(const cs_args &a, const cs_pos &p, con
     __syncthreads();
     constexpr int COLS = 32 * T + 1;
     const int n_pairs = p.n_sets * COLS;
-    for (int q = threadIdx.x; q < n_pairs; q += SX_CS_THREADS) {
+    for (int q = threadIdx.x; q < n_pairs; q += SX_CNF_THREADS) {
         const int s = q / COLS, f = q - s * COLS;
         float *col = xs + (s * N) * LD + f;
         float acc = col[0];
@@ -209,9 +107,9 @@ __device__ __forceinline__ void cs_setsum(const cs_args &a, const cs_pos &p, con
 
 // acc += (rows 32m .. 32m + 31 of C matrix `ci`) . in
 template <int HT>
-__device__ __forceinline__ void cs_mma_c(f32x16 &acc, const stile<HT> &in, const cs_args &a, int ci, int m, int lane) {
-    if (ci < a.n_c_lds) cs_mma<HT>(acc, in, cs_smem + a.base_tr + (ci * HT + m) * HT * 1024 + lane * 4);
-    else cs_mma_global<HT>(acc, in, a.net.trace + ((int64_t)ci * HT + m) * 32 * (HT * 32), lane);
+__device__ __forceinline__ void cs_mma_c(f32x16 &acc, const cnf_tile<HT> &in, const cs_args &a, int ci, int m, int lane) {
+    if (ci < a.n_c_lds) cnf_mma<HT>(acc, in, cnf_smem + a.base_tr + (ci * HT + m) * HT * 1024 + lane * 4);
+    else cnf_mma_global<HT>(acc, in, a.net.trace + ((int64_t)ci * HT + m) * 32 * (HT * 32), lane);
 }
 
 __device__ __forceinline__ float cs_dot(const f32x16 &p, const f32x16 &q) {
@@ -223,70 +121,70 @@ __device__ __forceinline__ float cs_dot(const f32x16 &p, const f32x16 &q) {
 
 // f(t, x) and -- when `want` -- tr = the row's share of the set's divergence, for the wave's 32 rows
 template <int HT, int NH>
-__device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const f32x16 &xin, float t, const stile<HT> &lat, f32x16 &k, bool want,
+__device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const f32x16 &xin, float t, const cnf_tile<HT> &lat, f32x16 &k, bool want,
                                         float &tr, int lane) {
     constexpr int LD = 32 * HT + 4;
     const int h = lane >> 5, act = a.net.act;
-    // (as in sx_cnf.hip: keeps the loop-invariant LDS weight loads inside the step loop)
+    // (keeps the loop-invariant LDS weight loads inside the step loop: without it the compiler holds whole matrices in registers)
     asm volatile("" ::: "memory");
     float unused;
-    stile<1> xi, mx;
+    cnf_tile<1> xi, mx;
     xi.v[0] = xin;
     cs_setsum<1, LD>(a, p, xi, mx, 0.f, unused, lane);
-    const float *b1 = cs_smem + a.base_b[0] + 4 * h, *w0 = cs_smem + a.base_w0 + 4 * h;
-    stile<HT> h1, m1;
+    const float *b1 = cnf_smem + a.base_b[0] + 4 * h, *w0 = cnf_smem + a.base_w0 + 4 * h;
+    cnf_tile<HT> h1, m1;
 #pragma unroll
     for (int m = 0; m < HT; ++m) {
         f32x16 acc = {};
-        cs_mma<1>(acc, xi, cs_smem + a.base_a[0] + m * 1024 + lane * 4);
-        cs_mma<1>(acc, mx, cs_smem + a.base_g[0] + m * 1024 + lane * 4);
+        cnf_mma<1>(acc, xi, cnf_smem + a.base_a[0] + m * 1024 + lane * 4);
+        cnf_mma<1>(acc, mx, cnf_smem + a.base_g[0] + m * 1024 + lane * 4);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) h1.v[m][r] = (acc[r] + lat.v[m][r]) + (cs_vec(b1, m, r) + t * cs_vec(w0, m, r));
+        for (int r = 0; r < 16; ++r) h1.v[m][r] = (acc[r] + lat.v[m][r]) + (cnf_vec(b1, m, r) + t * cnf_vec(w0, m, r));
     }
-    cs_act_all<HT>(h1, act);
+    cnf_act_all<HT>(h1, act);
     if (NH == 1) {
         float s = 0.f, e = 0.f, e_set = 0.f;
         if (want) {
-            const float *cd = cs_smem + a.base_tr + 4 * h, *cv = cs_smem + a.base_tr + HT * 32 + 4 * h;
+            const float *cd = cnf_smem + a.base_tr + 4 * h, *cv = cnf_smem + a.base_tr + HT * 32 + 4 * h;
 #pragma unroll
             for (int m = 0; m < HT; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float d = cs_dact(h1.v[m][r], act);
-                    s += d * cs_vec(cd, m, r);
-                    e += d * cs_vec(cv, m, r);
+                    const float d = cnf_dact(h1.v[m][r], act);
+                    s += d * cnf_vec(cd, m, r);
+                    e += d * cnf_vec(cv, m, r);
                 }
             e = e + __shfl_xor(e, 32, 64);
         }
         cs_setsum<HT, LD>(a, p, h1, m1, e, e_set, lane);
         f32x16 acc = {};
-        cs_mma<HT>(acc, h1, cs_smem + a.base_a[1] + lane * 4);
-        cs_mma<HT>(acc, m1, cs_smem + a.base_g[1] + lane * 4);
-        const float *b2 = cs_smem + a.base_b[1] + 4 * h;
+        cnf_mma<HT>(acc, h1, cnf_smem + a.base_a[1] + lane * 4);
+        cnf_mma<HT>(acc, m1, cnf_smem + a.base_g[1] + lane * 4);
+        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) k[r] = acc[r] + cs_vec(b2, 0, r);
+        for (int r = 0; r < 16; ++r) k[r] = acc[r] + cnf_vec(b2, 0, r);
         if (want) tr = (s + __shfl_xor(s, 32, 64)) + e_set;
     } else {
-        stile<HT> h2, m2;
+        cnf_tile<HT> h2, m2;
         cs_setsum<HT, LD>(a, p, h1, m1, 0.f, unused, lane);
-        const float *b2 = cs_smem + a.base_b[1] + 4 * h;
+        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
 #pragma unroll
         for (int m = 0; m < HT; ++m) {
             f32x16 acc = {};
-            cs_mma<HT>(acc, h1, cs_smem + a.base_a[1] + m * HT * 1024 + lane * 4);
-            cs_mma<HT>(acc, m1, cs_smem + a.base_g[1] + m * HT * 1024 + lane * 4);
+            cnf_mma<HT>(acc, h1, cnf_smem + a.base_a[1] + m * HT * 1024 + lane * 4);
+            cnf_mma<HT>(acc, m1, cnf_smem + a.base_g[1] + m * HT * 1024 + lane * 4);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) h2.v[m][r] = acc[r] + cs_vec(b2, m, r);
+            for (int r = 0; r < 16; ++r) h2.v[m][r] = acc[r] + cnf_vec(b2, m, r);
         }
-        cs_act_all<HT>(h2, act);
+        cnf_act_all<HT>(h2, act);
         cs_setsum<HT, LD>(a, p, h2, m2, 0.f, unused, lane);
         {
             f32x16 acc = {};
-            cs_mma<HT>(acc, h2, cs_smem + a.base_a[2] + lane * 4);
-            cs_mma<HT>(acc, m2, cs_smem + a.base_g[2] + lane * 4);
-            const float *b3 = cs_smem + a.base_b[2] + 4 * h;
+            cnf_mma<HT>(acc, h2, cnf_smem + a.base_a[2] + lane * 4);
+            cnf_mma<HT>(acc, m2, cnf_smem + a.base_g[2] + lane * 4);
+            const float *b3 = cnf_smem + a.base_b[2] + 4 * h;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) k[r] = acc[r] + cs_vec(b3, 0, r);
+            for (int r = 0; r < 16; ++r) k[r] = acc[r] + cnf_vec(b3, 0, r);
         }
         if (want) {
             // h1 <- d1, m1 <- s1, h2 <- d2, m2 <- s2
@@ -318,37 +216,37 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
 }
 
 template <int HT, int NH>
-__global__ __launch_bounds__(SX_CS_THREADS) void cnf_set_flow_kernel(const cs_args a) {
+__global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_args a) {
     constexpr int LD = 32 * HT + 4;
     const sx_cnf_set_net &net = a.net;
     const int D = net.dim, L = net.latent_dim, in_dim = 1 + D + L, H1 = net.out_dim[0], N = net.set_size;
-    cs_stage(net.A[0], H1, D, in_dim, 1, HT, 1, a.base_a[0]);
-    cs_stage(net.G[0], H1, D, in_dim, 1, HT, 1, a.base_g[0]);
-    cs_stage_vec(net.bias[0], H1, HT * 32, a.base_b[0]);
-    cs_stage_vec(net.w0, H1, HT * 32, a.base_w0);
+    cnf_stage(net.A[0], H1, D, in_dim, 1, HT, 1, a.base_a[0]);
+    cnf_stage(net.G[0], H1, D, in_dim, 1, HT, 1, a.base_g[0]);
+    cnf_stage_vec(net.bias[0], H1, 1, HT * 32, a.base_b[0]);
+    cnf_stage_vec(net.w0, H1, 1, HT * 32, a.base_w0);
     if (NH == 1) {
-        cs_stage(net.A[1], D, H1, H1, 0, 1, HT, a.base_a[1]);
-        cs_stage(net.G[1], D, H1, H1, 0, 1, HT, a.base_g[1]);
-        cs_stage_vec(net.bias[1], D, 32, a.base_b[1]);
-        cs_stage_vec(a.want_ldj ? net.trace : nullptr, H1, HT * 32, a.base_tr);
-        cs_stage_vec(a.want_ldj ? net.trace + H1 : nullptr, H1, HT * 32, a.base_tr + HT * 32);
+        cnf_stage(net.A[1], D, H1, H1, 0, 1, HT, a.base_a[1]);
+        cnf_stage(net.G[1], D, H1, H1, 0, 1, HT, a.base_g[1]);
+        cnf_stage_vec(net.bias[1], D, 1, 32, a.base_b[1]);
+        cnf_stage_vec(a.want_ldj ? net.trace : nullptr, H1, 1, HT * 32, a.base_tr);
+        cnf_stage_vec(a.want_ldj ? net.trace + H1 : nullptr, H1, 1, HT * 32, a.base_tr + HT * 32);
     } else {
         const int H2 = net.out_dim[1];
-        cs_stage(net.A[1], H2, H1, H1, 0, HT, HT, a.base_a[1]);
-        cs_stage(net.G[1], H2, H1, H1, 0, HT, HT, a.base_g[1]);
-        cs_stage_vec(net.bias[1], H2, HT * 32, a.base_b[1]);
-        cs_stage(net.A[2], D, H2, H2, 0, 1, HT, a.base_a[2]);
-        cs_stage(net.G[2], D, H2, H2, 0, 1, HT, a.base_g[2]);
-        cs_stage_vec(net.bias[2], D, 32, a.base_b[2]);
+        cnf_stage(net.A[1], H2, H1, H1, 0, HT, HT, a.base_a[1]);
+        cnf_stage(net.G[1], H2, H1, H1, 0, HT, HT, a.base_g[1]);
+        cnf_stage_vec(net.bias[1], H2, 1, HT * 32, a.base_b[1]);
+        cnf_stage(net.A[2], D, H2, H2, 0, 1, HT, a.base_a[2]);
+        cnf_stage(net.G[2], D, H2, H2, 0, 1, HT, a.base_g[2]);
+        cnf_stage_vec(net.bias[2], D, 1, 32, a.base_b[2]);
         if (a.want_ldj)
             for (int ci = 0; ci < a.n_c_lds; ++ci)
-                cs_stage(net.trace + (int64_t)ci * (HT * 32) * (HT * 32), HT * 32, HT * 32, HT * 32, 0, HT, HT, a.base_tr + ci * HT * HT * 1024);
+                cnf_stage(net.trace + (int64_t)ci * (HT * 32) * (HT * 32), HT * 32, HT * 32, HT * 32, 0, HT, HT, a.base_tr + ci * HT * HT * 1024);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const bool want = a.want_ldj != 0;
     const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
-    const int rows_per_pass = (SX_CS_ROWS / N) * N;
+    const int rows_per_pass = cnf_rows_per_pass(N);
     const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
     cs_pos p;
     p.rho = (threadIdx.x >> 6) * 32 + (lane & 31);
@@ -360,22 +258,22 @@ __global__ __launch_bounds__(SX_CS_THREADS) void cnf_set_flow_kernel(const cs_ar
         const int64_t row = base + p.rho;
         p.first = live ? (p.rho / N) * N : p.rho;
         p.n_sets = n_here / N;
-        f32x16 y;
+        cnf_tile<1> y;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = cs_kmap(r, h);
-            y[r] = (live && f < D) ? a.x[row * D + f] : 0.f;
+            const int f = cnf_kmap(r, h);
+            y.v[0][r] = (live && f < D) ? a.x[row * D + f] : 0.f;
         }
         // the latent share of the first layer: A1[:, latent] . latent_row + G1[:, latent] . (the set's latent sum), once per pass
-        stile<HT> lat;
+        cnf_tile<HT> lat;
 #pragma unroll
         for (int m = 0; m < HT; ++m) lat.v[m] = f32x16{};
         for (int c = 0; c < (L + 31) >> 5; ++c) {
-            stile<1> lb, ml;
+            cnf_tile<1> lb, ml;
             float unused;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + cs_kmap(r, h);
+                const int f = 32 * c + cnf_kmap(r, h);
                 lb.v[0][r] = (live && f < L) ? a.latent[row * L + f] : 0.f;
             }
             cs_setsum<1, LD>(a, p, lb, ml, 0.f, unused, lane);
@@ -384,7 +282,7 @@ __global__ __launch_bounds__(SX_CS_THREADS) void cnf_set_flow_kernel(const cs_ar
                 const int wr = 32 * m + (lane & 31);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const int f = 32 * c + cs_kmap(q, h);
+                    const int f = 32 * c + cnf_kmap(q, h);
                     const bool in = wr < H1 && f < L;
                     const float av = in ? net.A[0][(int64_t)wr * in_dim + 1 + D + f] : 0.f;
                     const float gv = in ? net.G[0][(int64_t)wr * in_dim + 1 + D + f] : 0.f;
@@ -394,74 +292,35 @@ __global__ __launch_bounds__(SX_CS_THREADS) void cnf_set_flow_kernel(const cs_ar
             }
         }
         float l = 0.f;
-        const int n_stages = a.solver == SX_CNF_EULER ? 1 : a.solver == SX_CNF_MIDPOINT ? 2 : 4;
+        const int n_stages = cnf_stages(a.solver);
         const float third = 1.f / 3.f, two_thirds = 2.f / 3.f;
         for (int i = 0; i < a.n_steps; ++i) {
-            // the grid: t_i = t0 +- i * step_size, the last point replaced by t1
-            const float ta = i == 0 ? a.t0 : a.t0 + sgn * ((float)i * a.step_size);
-            const float tb = i + 1 == a.n_steps ? a.t1 : a.t0 + sgn * ((float)(i + 1) * a.step_size);
+            float ta, tb;
+            cnf_grid(a, sgn, i, ta, tb);
             const float dt = tb - ta, half = 0.5f * dt;
-            f32x16 k1 = {}, k2 = {}, xs = y;          // (rk4: after stage 3, k1 holds k1 + 3 (k2 + k3))
+            cnf_tile<1> k1 = {}, k2 = {}, xs = y;
             float q1 = 0.f, q2 = 0.f, ts = ta;
             for (int st = 0; st < n_stages; ++st) {
-                f32x16 k;
+                cnf_tile<1> k;
                 float q = 0.f;
-                cs_eval<HT, NH>(a, p, xs, ts, lat, k, want, q, lane);
-                if (a.solver == SX_CNF_EULER) {                       // y += dt f(t, y)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) y[r] = y[r] + dt * k[r];
-                    l = l + dt * q;
-                } else if (a.solver == SX_CNF_MIDPOINT) {             // y += dt f(t + dt/2, y + f(t, y) dt/2)
-                    if (st == 0) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) xs[r] = y[r] + k[r] * half;
-                        ts = ta + half;
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) y[r] = y[r] + dt * k[r];
-                        l = l + dt * q;
-                    }
-                } else if (st == 0) {                                 // rk4, the 3/8 rule
-                    k1 = k; q1 = q;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) xs[r] = y[r] + (dt * k1[r]) * third;
-                    ts = ta + dt * third;
-                } else if (st == 1) {
-                    k2 = k; q2 = q;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) xs[r] = y[r] + dt * (k2[r] - k1[r] * third);
-                    ts = ta + dt * two_thirds;
-                } else if (st == 2) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        xs[r] = y[r] + dt * ((k1[r] - k2[r]) + k[r]);
-                        k1[r] = k1[r] + 3.f * (k2[r] + k[r]);
-                    }
-                    q1 = q1 + 3.f * (q2 + q);
-                    ts = tb;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) y[r] = y[r] + ((k1[r] + k[r]) * dt) * 0.125f;
-                    l = l + ((q1 + q) * dt) * 0.125f;
-                }
+                cs_eval<HT, NH>(a, p, xs.v[0], ts, lat, k.v[0], want, q, lane);
+                cnf_tableau<1>(a.solver, st, ta, tb, dt, half, third, two_thirds, k, q, k1, k2, q1, q2, xs, ts, y, l);
             }
         }
         if (live) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = cs_kmap(r, h);
-                if (f < D) a.y[row * D + f] = y[r];
+                const int f = cnf_kmap(r, h);
+                if (f < D) a.y[row * D + f] = y.v[0][r];
             }
             if (want && h == 0) a.ldj[row] = l;
         }
     }
 }
 
-inline int cs_tiles(int n) { return n <= 32 ? 1 : 2; }
-
 inline int cs_hidden_tiles(const sx_cnf_set_net &net) {
     int HT = 1;
-    for (int l = 0; l + 1 < net.n_layers; ++l) HT = cs_tiles(net.out_dim[l]) > HT ? cs_tiles(net.out_dim[l]) : HT;
+    for (int l = 0; l + 1 < net.n_layers; ++l) HT = cnf_tiles(net.out_dim[l]) > HT ? cnf_tiles(net.out_dim[l]) : HT;
     return HT;
 }
 
@@ -477,7 +336,7 @@ size_t cs_plan(const sx_cnf_set_net &net, int want_ldj, cs_args *a) {
         bb[l] = (int)off; off += (size_t)MT * 32;
     }
     const int base_w0 = (int)off; off += (size_t)HT * 32;
-    const int base_x = (int)off; off += (size_t)SX_CS_ROWS * (32 * HT + 4);
+    const int base_x = (int)off; off += (size_t)SX_CNF_ROWS * (32 * HT + 4);
     const int base_tr = (int)off;
     int n_c_lds = 0;
     if (NH == 1) off += (size_t)2 * HT * 32;
@@ -510,31 +369,6 @@ int cs_check_shape(const sx_cnf_set_net *net_host) {
     return SX_OK;
 }
 
-template <int HT, int NH>
-int cs_launch(const cs_args &a, size_t lds, void *stream) {
-    auto kern = cnf_set_flow_kernel<HT, NH>;
-    static bool raised_on[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!raised_on[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SX_CNF_LDS_BYTES);
-        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        raised_on[dev & 63] = true;
-    }
-    int cus = 0, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, SX_CS_THREADS, lds);
-    if (cus < 1) cus = 1;
-    if (per_cu < 1) per_cu = 1;
-    const int rows_per_pass = (SX_CS_ROWS / a.net.set_size) * a.net.set_size;
-    const int64_t want = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const int grid = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SX_CS_THREADS), lds, sx_stream(stream), a);
-    SX_LAUNCH_CHECK();
-    return SX_OK;
-}
-
 }  // namespace
 
 extern "C" size_t sx_cnf_set_lds_bytes(const sx_cnf_set_net *net_host, int32_t want_ldj) {
@@ -550,11 +384,8 @@ extern "C" int sx_cnf_set_flow(const sx_cnf_set_net *net_host, const float *x, c
     for (int l = 0; l < net.n_layers; ++l)
         SX_REQUIRE(net.A[l] != nullptr && net.G[l] != nullptr && net.bias[l] != nullptr, "sx_cnf_set_flow: layer %d lacks A, G or bias", l);
     SX_REQUIRE(net.w0 != nullptr, "sx_cnf_set_flow: the time column w0 is missing");
-    SX_REQUIRE(solver >= SX_CNF_EULER && solver <= SX_CNF_RK4, "sx_cnf_set_flow: solver must be euler (0), midpoint (1) or rk4 (2), got %d", solver);
-    SX_REQUIRE(n_rows >= 0 && n_steps >= 0, "sx_cnf_set_flow: negative n_rows / n_steps");
-    SX_REQUIRE(n_rows % net.set_size == 0, "sx_cnf_set_flow: n_rows (%lld) is not a multiple of set_size (%d)", (long long)n_rows, net.set_size);
-    SX_REQUIRE(n_steps <= 1 || step_size > 0.f, "sx_cnf_set_flow: a grid of %d steps needs step_size > 0", n_steps);
-    SX_REQUIRE(x != nullptr && y != nullptr, "sx_cnf_set_flow: null input / output");
+    const int rc_call = cnf_check_call("sx_cnf_set_flow", solver, n_rows, net.set_size, n_steps, step_size, x, y);
+    if (rc_call != SX_OK) return rc_call;
     SX_REQUIRE(net.latent_dim == 0 || latent != nullptr, "sx_cnf_set_flow: latent rows missing");
     SX_REQUIRE(!want_ldj || (ldj != nullptr && net.trace != nullptr), "sx_cnf_set_flow: want_ldj needs ldj and the trace constants");
     SX_REQUIRE(!want_ldj || net.n_layers == 2 || ((uintptr_t)net.trace & 15) == 0, "sx_cnf_set_flow: the C matrices must be 16-byte aligned");
@@ -567,6 +398,8 @@ extern "C" int sx_cnf_set_flow(const sx_cnf_set_net *net_host, const float *x, c
     a.solver = solver; a.n_steps = n_steps; a.want_ldj = want_ldj ? 1 : 0;
     a.t0 = t0; a.t1 = t1; a.step_size = step_size;
     const int NH = net.n_layers - 1, HT = cs_hidden_tiles(net);
-    if (HT == 1) return NH == 1 ? cs_launch<1, 1>(a, lds, stream) : cs_launch<1, 2>(a, lds, stream);
-    return NH == 1 ? cs_launch<2, 1>(a, lds, stream) : cs_launch<2, 2>(a, lds, stream);
+    const int64_t want = cnf_set_blocks(n_rows, net.set_size);
+    const char *fn = "sx_cnf_set_flow";
+    if (HT == 1) return NH == 1 ? cnf_launch<cnf_set_flow_kernel<1, 1>>(fn, a, lds, want, stream) : cnf_launch<cnf_set_flow_kernel<1, 2>>(fn, a, lds, want, stream);
+    return NH == 1 ? cnf_launch<cnf_set_flow_kernel<2, 1>>(fn, a, lds, want, stream) : cnf_launch<cnf_set_flow_kernel<2, 2>>(fn, a, lds, want, stream);
 }

@@ -1,14 +1,19 @@
 // Host-side sanitizer driver (test infrastructure; built by `make -C stribor_amd/csrc asan`, run by tests/test_host_cpu.py).
 //
-// The library's HOST code -- the launchers and argument validators of every sx_* entry point -- compiled for the CPU only
-// (hipcc --offload-host-only) with -fsanitize=address,undefined, driven WITHOUT a GPU: every call below must come back with a status
-// (never crash, never trip a sanitizer report).  Three parts:
+// The library's HOST code -- every launcher and argument validator -- compiled for the CPU only (hipcc --offload-host-only) with
+// -fsanitize=address,undefined, driven WITHOUT a GPU: every call below must come back with a status (never crash, never trip a
+// sanitizer report).  Driven: every entry point include/stribor_hip.h declares except these eleven, whose host code is compiled and
+// linked here but not called yet: sx_rqs_forward_bwd, sx_rqs_inverse_bwd, sx_cubic_forward_bwd, sx_cubic_inverse_bwd, sx_rqs_slab_bwd,
+// sx_rqs_slab_l1_bwd, sx_resnet_lds_bytes, sx_resnet_flow, sx_spectral_sigma, sx_attention_fwd, sx_attention_bwd.  Four parts:
 //   1. the plain argument checks of the element-wise / packing / weight-gradient entry points (null pointers, bad sizes, bad enums,
 //      misalignment): each must return non-zero and leave a message in sx_last_error();
 //   2. sx_flow_launch_info / sx_flow_run / sx_flow_bwd_partials / sx_flow_bwd_run over VALID programs (cfg 2-, cfg 3-, cfg 4-like, the
 //      128-column backward program) with n_rows = 0 -- the validators run, nothing is launched -- and over every single-field mutation
 //      of those programs with the out-of-range values the round-3 fuzz found (negative / 255 / 256 / 2^30 tile and step fields);
 //   3. a seeded random fuzz of whole sx_program structs through the validators (no launch: n_rows = 0 for sx_flow_run).
+//   4. the four CNF families (sx_cnf_*, sx_cnf_exact_*, sx_cnf_set_*, sx_cnf_exact_set_*): every range check of the network
+//      validators through both the LDS query (0) and the flow call (a status and a message), the per-call argument checks of the flow
+//      calls, and a valid network with n_rows = 0 (returns after every check, before any launch).
 // GPU AddressSanitizer does not exist on this pool: this job covers the host side only (sanitizer row).
 #include "../include/stribor_hip.h"
 #include <limits.h>
@@ -137,6 +142,249 @@ static void touch_validators(const sx_program &p, int64_t rows_info) {
                       SX_BF16, SX_GEMM_F32, nullptr, nullptr, nullptr);
     (void)sx_flow_bwd_partials(&p, rows_info, &np, &pf);
     (void)sx_flow_bwd_run(&p, dummy, dummy, dummy, nullptr, nullptr, dummy, dummy, 0, nullptr, nullptr, nullptr);
+}
+
+// ---- 4. the CNF families --------------------------------------------------------------------------------------------------------
+#define EXPECT_TRUE(cond)                                                                        \
+    do {                                                                                         \
+        ++g_calls;                                                                               \
+        if (!(cond)) { fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++g_fail; } \
+    } while (0)
+
+alignas(16) static float g_cnf_buf[64];          // stands for every device pointer: n_rows = 0, nothing is read
+
+// the per-call arguments the four flow calls share: FLOW(net, x, latent, y, ldj, n_rows, solver, n_steps, step_size, want_ldj).
+// `net` is valid, has latent_dim > 0 and accepts want_ldj = 1 with a non-null ldj.
+#define CNF_CALL_CHECKS(FLOW, net)                                                   \
+    do {                                                                             \
+        float *b_ = g_cnf_buf;                                                       \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, b_, 0, -1, 1, 0.f, 1));                      /* solver */ \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_RK4 + 1, 1, 0.f, 1));          \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, b_, -1, SX_CNF_RK4, 1, 0.f, 1));             /* n_rows < 0 */ \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_RK4, -1, 0.f, 1));             /* n_steps < 0 */ \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_EULER, 2, 0.f, 1));            /* a grid without a step */ \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_EULER, 3, -0.25f, 0));         \
+        EXPECT_BAD(FLOW(net, nullptr, b_, b_, b_, 0, SX_CNF_MIDPOINT, 1, 0.f, 1));    /* null x */ \
+        EXPECT_BAD(FLOW(net, b_, b_, nullptr, b_, 0, SX_CNF_MIDPOINT, 1, 0.f, 1));    /* null y */ \
+        EXPECT_BAD(FLOW(net, b_, nullptr, b_, b_, 0, SX_CNF_MIDPOINT, 1, 0.f, 1));    /* latent rows missing */ \
+        EXPECT_BAD(FLOW(net, b_, b_, b_, nullptr, 0, SX_CNF_MIDPOINT, 1, 0.f, 1));    /* want_ldj without ldj */ \
+        EXPECT_OK(FLOW(net, b_, b_, b_, nullptr, 0, SX_CNF_MIDPOINT, 1, 0.f, 0));     \
+        EXPECT_OK(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_EULER, 0, 0.f, 1));             \
+        EXPECT_OK(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_RK4, 1, 0.f, 1));               \
+        EXPECT_OK(FLOW(net, b_, b_, b_, b_, 0, SX_CNF_RK4, 3, 0.3f, 1));              \
+    } while (0)
+
+// dense: [t, x (dim), latent] -> hidden... -> dim
+static sx_cnf_net cnf_net(int dim, int latent, int h1, int h2) {
+    sx_cnf_net n;
+    memset(&n, 0, sizeof(n));
+    const int w[4] = {1 + dim + latent, h1, h2 > 0 ? h2 : dim, dim};
+    n.n_layers = h2 > 0 ? 3 : 2;
+    for (int l = 0; l < n.n_layers; ++l) { n.layer[l].W = g_cnf_buf; n.layer[l].b = g_cnf_buf; n.layer[l].in_dim = w[l]; n.layer[l].out_dim = w[l + 1]; }
+    n.dim = dim; n.latent_dim = latent; n.act = SX_ACT_TANH; n.trace = g_cnf_buf;
+    return n;
+}
+static int cnf_flow(const sx_cnf_net *n, const float *x, const float *lat, float *y, float *ldj, int64_t rows, int solver, int steps, float step,
+                    int want) {
+    return sx_cnf_flow(n, x, lat, y, ldj, rows, solver, steps, 0.f, 1.f, step, want, nullptr);
+}
+static void cnf_bad_net(const sx_cnf_net &n) {
+    EXPECT_TRUE(sx_cnf_lds_bytes(&n, 0) == 0 && sx_cnf_lds_bytes(&n, 1) == 0);
+    EXPECT_BAD(cnf_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+}
+static void drive_cnf() {
+    const sx_cnf_net ok1 = cnf_net(3, 2, 8, 0), ok2 = cnf_net(3, 2, 8, 40), wide = cnf_net(32, 0, 128, 128);
+    sx_cnf_net n;
+    EXPECT_TRUE(sx_cnf_lds_bytes(nullptr, 1) == 0);
+    EXPECT_BAD(cnf_flow(nullptr, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.n_layers = 1; cnf_bad_net(n);
+    n = ok2; n.n_layers = 4; cnf_bad_net(n);
+    n = ok1; n.dim = 0; cnf_bad_net(n);
+    n = ok1; n.dim = SX_CNF_MAX_DIM + 1; cnf_bad_net(n);
+    n = ok1; n.latent_dim = -1; cnf_bad_net(n);
+    n = cnf_net(64, 64, 8, 0); cnf_bad_net(n);                                  // 1 + dim + latent_dim = 129
+    n = ok1; n.act = -1; cnf_bad_net(n);
+    n = ok1; n.act = SX_ACT_SILU; cnf_bad_net(n);
+    n = ok2; n.layer[2].W = nullptr; cnf_bad_net(n);
+    n = ok1; n.layer[0].in_dim = 5; cnf_bad_net(n);
+    n = ok2; n.layer[2].in_dim = 8; cnf_bad_net(n);
+    n = cnf_net(3, 2, 0, 0); cnf_bad_net(n);                                    // hidden widths
+    n = cnf_net(3, 2, 129, 0); cnf_bad_net(n);
+    n = cnf_net(3, 2, 8, 129); cnf_bad_net(n);
+    n = ok1; n.layer[1].out_dim = 4; cnf_bad_net(n);                            // the last layer maps back to dim
+    n = cnf_net(33, 0, 65, 8); cnf_bad_net(n);                                  // two wide hidden layers need dim <= 32
+    n = cnf_net(33, 0, 8, 65); cnf_bad_net(n);
+    EXPECT_TRUE(sx_cnf_lds_bytes(&ok1, 0) != 0 && sx_cnf_lds_bytes(&ok1, 1) != 0 && sx_cnf_lds_bytes(&ok2, 1) > sx_cnf_lds_bytes(&ok2, 0));
+    EXPECT_TRUE(sx_cnf_lds_bytes(&wide, 1) == sx_cnf_lds_bytes(&wide, 0) && sx_cnf_lds_bytes(&wide, 1) <= SX_CNF_LDS_BYTES);      // C stays in global memory
+    EXPECT_TRUE(sx_cnf_lds_bytes(&(n = cnf_net(33, 0, 64, 64)), 1) != 0 && sx_cnf_lds_bytes(&(n = cnf_net(64, 0, 128, 0)), 1) != 0);
+    CNF_CALL_CHECKS(cnf_flow, &ok1);
+    CNF_CALL_CHECKS(cnf_flow, &ok2);
+    EXPECT_OK(cnf_flow(&wide, g_cnf_buf, nullptr, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.trace = nullptr;
+    EXPECT_BAD(cnf_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));      // want_ldj without the trace constants
+    EXPECT_OK(cnf_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, nullptr, 0, SX_CNF_RK4, 1, 0.f, 0));
+}
+
+// exact trace: two MADEs + the dimwise net; the image's size comes from the library's own query
+static sx_cnf_exact_net cnfx_net(int dim, int d_h, int latent, int h1, int h2) {
+    sx_cnf_exact_net n;
+    memset(&n, 0, sizeof(n));
+    n.image = g_cnf_buf; n.w_latent = latent > 0 ? g_cnf_buf : nullptr;
+    n.dim = dim; n.d_h = d_h; n.latent_dim = latent; n.n_hidden = h2 > 0 ? 2 : 1; n.hidden[0] = h1; n.hidden[1] = h2; n.act = SX_ACT_TANH;
+    n.image_floats = (int32_t)(sx_cnf_exact_lds_bytes(&n) / 4);
+    return n;
+}
+static int cnfx_flow(const sx_cnf_exact_net *n, const float *x, const float *lat, float *y, float *ldj, int64_t rows, int solver, int steps,
+                     float step, int want) {
+    return sx_cnf_exact_flow(n, x, lat, y, ldj, rows, solver, steps, 1.f, 0.f, step, want, nullptr);
+}
+static void cnfx_bad_net(const sx_cnf_exact_net &n) {
+    EXPECT_TRUE(sx_cnf_exact_lds_bytes(&n) == 0);
+    EXPECT_BAD(cnfx_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+}
+static void drive_cnf_exact() {
+    const sx_cnf_exact_net ok1 = cnfx_net(3, 2, 2, 8, 0), ok2 = cnfx_net(16, 8, 64, 64, 64);
+    sx_cnf_exact_net n;
+    EXPECT_TRUE(sx_cnf_exact_lds_bytes(nullptr) == 0);
+    EXPECT_BAD(cnfx_flow(nullptr, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.n_hidden = 0; cnfx_bad_net(n);
+    n = ok2; n.n_hidden = 3; cnfx_bad_net(n);
+    n = ok1; n.dim = 0; cnfx_bad_net(n);
+    n = ok1; n.dim = SX_CNF_EXACT_MAX_DIM + 1; cnfx_bad_net(n);
+    n = ok1; n.d_h = 0; cnfx_bad_net(n);
+    n = ok1; n.d_h = SX_CNF_EXACT_MAX_DH + 1; cnfx_bad_net(n);
+    n = ok1; n.latent_dim = -1; cnfx_bad_net(n);
+    n = ok1; n.latent_dim = SX_CNF_EXACT_MAX_LATENT + 1; cnfx_bad_net(n);
+    n = ok1; n.act = -1; cnfx_bad_net(n);
+    n = ok1; n.act = SX_ACT_GELU; cnfx_bad_net(n);
+    n = ok1; n.hidden[0] = 0; cnfx_bad_net(n);
+    n = ok2; n.hidden[1] = SX_CNF_EXACT_MAX_HIDDEN + 1; cnfx_bad_net(n);
+    EXPECT_TRUE(ok1.image_floats > 0 && ok2.image_floats > ok1.image_floats && (size_t)ok2.image_floats * 4 <= SX_CNF_LDS_BYTES);
+    CNF_CALL_CHECKS(cnfx_flow, &ok1);
+    CNF_CALL_CHECKS(cnfx_flow, &ok2);
+    n = ok1; n.w_latent = nullptr;
+    EXPECT_BAD(cnfx_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));     // latent weights missing
+    n = ok1; n.image = nullptr;
+    EXPECT_BAD(cnfx_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.image_floats -= 32;
+    EXPECT_BAD(cnfx_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));     // not the kernel's plan
+    n = ok1; n.image = g_cnf_buf + 1;
+    EXPECT_BAD(cnfx_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));     // misaligned
+    n = ok1; n.w_latent = g_cnf_buf + 2;
+    EXPECT_BAD(cnfx_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+}
+
+// sets: equivariant layers [t, x (dim), latent] -> hidden... -> dim over sets of `size` rows
+static sx_cnf_set_net cnfs_net(int dim, int latent, int size, int h1, int h2) {
+    sx_cnf_set_net n;
+    memset(&n, 0, sizeof(n));
+    n.n_layers = h2 > 0 ? 3 : 2;
+    for (int l = 0; l < n.n_layers; ++l) { n.A[l] = g_cnf_buf; n.G[l] = g_cnf_buf; n.bias[l] = g_cnf_buf; }
+    n.w0 = g_cnf_buf; n.trace = g_cnf_buf;
+    n.dim = dim; n.latent_dim = latent; n.act = SX_ACT_TANH; n.set_size = size;
+    n.out_dim[0] = h1; n.out_dim[1] = h2 > 0 ? h2 : dim; n.out_dim[2] = h2 > 0 ? dim : 0;
+    return n;
+}
+static int cnfs_flow(const sx_cnf_set_net *n, const float *x, const float *lat, float *y, float *ldj, int64_t rows, int solver, int steps,
+                     float step, int want) {
+    return sx_cnf_set_flow(n, x, lat, y, ldj, rows, solver, steps, 0.f, 1.f, step, want, nullptr);
+}
+static void cnfs_bad_net(const sx_cnf_set_net &n) {
+    EXPECT_TRUE(sx_cnf_set_lds_bytes(&n, 0) == 0 && sx_cnf_set_lds_bytes(&n, 1) == 0);
+    EXPECT_BAD(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+}
+static void drive_cnf_set() {
+    const sx_cnf_set_net ok1 = cnfs_net(2, 2, 3, 8, 0), ok2 = cnfs_net(2, 2, 3, 8, 40);
+    sx_cnf_set_net n;
+    EXPECT_TRUE(sx_cnf_set_lds_bytes(nullptr, 1) == 0);
+    EXPECT_BAD(cnfs_flow(nullptr, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.n_layers = 1; cnfs_bad_net(n);
+    n = ok2; n.n_layers = 4; cnfs_bad_net(n);
+    n = ok1; n.dim = 0; cnfs_bad_net(n);
+    n = ok1; n.dim = SX_CNF_SET_MAX_DIM + 1; cnfs_bad_net(n);
+    n = ok1; n.latent_dim = -1; cnfs_bad_net(n);
+    n = cnfs_net(32, 32, 3, 8, 0); cnfs_bad_net(n);                             // 1 + dim + latent_dim = 65
+    n = ok1; n.act = -1; cnfs_bad_net(n);
+    n = ok1; n.act = SX_ACT_SILU; cnfs_bad_net(n);
+    n = ok1; n.set_size = 0; cnfs_bad_net(n);
+    n = ok1; n.set_size = SX_CNF_SET_MAX_SIZE + 1; cnfs_bad_net(n);
+    n = ok1; n.out_dim[0] = 0; cnfs_bad_net(n);
+    n = ok2; n.out_dim[1] = SX_CNF_SET_MAX_HIDDEN + 1; cnfs_bad_net(n);
+    n = ok2; n.out_dim[2] = 3; cnfs_bad_net(n);                                 // the last layer maps back to dim
+    EXPECT_TRUE(sx_cnf_set_lds_bytes(&ok1, 0) != 0 && sx_cnf_set_lds_bytes(&ok1, 1) != 0 && sx_cnf_set_lds_bytes(&ok2, 1) > sx_cnf_set_lds_bytes(&ok2, 0));
+    EXPECT_TRUE(sx_cnf_set_lds_bytes(&(n = cnfs_net(32, 31, 128, 64, 64)), 1) <= SX_CNF_LDS_BYTES && sx_cnf_set_lds_bytes(&n, 1) != 0);
+    CNF_CALL_CHECKS(cnfs_flow, &ok1);
+    CNF_CALL_CHECKS(cnfs_flow, &ok2);
+    EXPECT_BAD(cnfs_flow(&ok1, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 4, SX_CNF_RK4, 1, 0.f, 1));   // n_rows is no multiple of set_size
+    n = ok2; n.G[1] = nullptr;
+    EXPECT_BAD(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.bias[0] = nullptr;
+    EXPECT_BAD(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.w0 = nullptr;
+    EXPECT_BAD(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.trace = nullptr;
+    EXPECT_BAD(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));     // want_ldj without the trace constants
+    EXPECT_OK(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, nullptr, 0, SX_CNF_RK4, 1, 0.f, 0));
+    n = ok2; n.trace = g_cnf_buf + 1;
+    EXPECT_BAD(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));     // two hidden layers: misaligned C matrices
+    EXPECT_OK(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, nullptr, 0, SX_CNF_RK4, 1, 0.f, 0));
+    n = ok1; n.trace = g_cnf_buf + 1;
+    EXPECT_OK(cnfs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));      // (one hidden layer: two vectors, any alignment)
+}
+
+// exact trace over sets: the MADE, the set embedding with its pooling, the dimwise net
+static sx_cnf_exact_set_net cnfxs_net(int dim, int d_h, int latent, int size, int pooling, int h1, int h2) {
+    sx_cnf_exact_set_net n;
+    memset(&n, 0, sizeof(n));
+    n.image = g_cnf_buf; n.w_latent = latent > 0 ? g_cnf_buf : nullptr;
+    n.dim = dim; n.d_h = d_h; n.latent_dim = latent; n.n_hidden = h2 > 0 ? 2 : 1; n.hidden[0] = h1; n.hidden[1] = h2; n.act = SX_ACT_TANH;
+    n.set_size = size; n.pooling = pooling;
+    n.image_floats = (int32_t)(sx_cnf_exact_set_lds_bytes(&n) / 4) - 128 * 16;
+    return n;
+}
+static int cnfxs_flow(const sx_cnf_exact_set_net *n, const float *x, const float *lat, float *y, float *ldj, int64_t rows, int solver,
+                      int steps, float step, int want) {
+    return sx_cnf_exact_set_flow(n, x, lat, y, ldj, rows, solver, steps, 1.f, 0.f, step, want, nullptr);
+}
+static void cnfxs_bad_net(const sx_cnf_exact_set_net &n) {
+    EXPECT_TRUE(sx_cnf_exact_set_lds_bytes(&n) == 0);
+    EXPECT_BAD(cnfxs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+}
+static void drive_cnf_exact_set() {
+    const sx_cnf_exact_set_net ok1 = cnfxs_net(2, 2, 2, 3, SX_POOL_MAX, 8, 0), ok2 = cnfxs_net(16, 8, 64, 128, SX_POOL_MEAN, 64, 64);
+    sx_cnf_exact_set_net n;
+    EXPECT_TRUE(sx_cnf_exact_set_lds_bytes(nullptr) == 0);
+    EXPECT_BAD(cnfxs_flow(nullptr, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.n_hidden = 0; cnfxs_bad_net(n);
+    n = ok2; n.n_hidden = 3; cnfxs_bad_net(n);
+    n = ok1; n.dim = 0; cnfxs_bad_net(n);
+    n = ok1; n.dim = SX_CNF_EXACT_SET_MAX_DIM + 1; cnfxs_bad_net(n);
+    n = ok1; n.d_h = 0; cnfxs_bad_net(n);
+    n = ok1; n.d_h = SX_CNF_EXACT_SET_MAX_DH + 1; cnfxs_bad_net(n);
+    n = ok1; n.latent_dim = -1; cnfxs_bad_net(n);
+    n = ok1; n.latent_dim = SX_CNF_EXACT_SET_MAX_LATENT + 1; cnfxs_bad_net(n);
+    n = ok1; n.set_size = 0; cnfxs_bad_net(n);
+    n = ok1; n.set_size = SX_CNF_EXACT_SET_MAX_SIZE + 1; cnfxs_bad_net(n);
+    n = ok1; n.pooling = -1; cnfxs_bad_net(n);
+    n = ok1; n.pooling = SX_POOL_MAX + 1; cnfxs_bad_net(n);
+    n = ok1; n.act = -1; cnfxs_bad_net(n);
+    n = ok1; n.act = SX_ACT_GELU; cnfxs_bad_net(n);
+    n = ok1; n.hidden[0] = 0; cnfxs_bad_net(n);
+    n = ok2; n.hidden[1] = SX_CNF_EXACT_SET_MAX_HIDDEN + 1; cnfxs_bad_net(n);
+    EXPECT_TRUE(ok1.image_floats > 0 && ok2.image_floats > ok1.image_floats && sx_cnf_exact_set_lds_bytes(&ok2) <= SX_CNF_LDS_BYTES);
+    CNF_CALL_CHECKS(cnfxs_flow, &ok1);
+    CNF_CALL_CHECKS(cnfxs_flow, &ok2);
+    EXPECT_BAD(cnfxs_flow(&ok1, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 4, SX_CNF_RK4, 1, 0.f, 1));  // n_rows is no multiple of set_size
+    n = ok1; n.w_latent = nullptr;
+    EXPECT_BAD(cnfxs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));    // latent weights missing
+    n = ok1; n.image = nullptr;
+    EXPECT_BAD(cnfxs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
+    n = ok1; n.image_floats += 128 * 16;
+    EXPECT_BAD(cnfxs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));    // the exchange is not part of the image
+    n = ok1; n.image = g_cnf_buf + 3;
+    EXPECT_BAD(cnfxs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));    // misaligned
+    n = ok1; n.w_latent = g_cnf_buf + 1;
+    EXPECT_BAD(cnfxs_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));
 }
 
 int main() {
@@ -343,6 +591,12 @@ int main() {
         }
         if (it % 8 == 0) touch_validators(p, 12345);
     }
+
+    // ---- 4. the CNF families: network validators, per-call checks, n_rows = 0 -------------------------------------------------------
+    drive_cnf();
+    drive_cnf_exact();
+    drive_cnf_set();
+    drive_cnf_exact_set();
     printf("%ld calls, %ld random programs accepted, %d failures\n", g_calls, accepted, g_fail);
     return g_fail ? 1 : 0;
 }

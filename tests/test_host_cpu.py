@@ -417,9 +417,12 @@ def test_fused_kernel_stages_weights_with_mubuf_lds_dma():
 
 def test_host_code_under_address_and_ub_sanitizers():
     """SURVEY 5, sanitizer row: `make asan` builds the library's HOST code (every launcher and argument validator, --offload-host-only,
-    no device code) with -fsanitize=address,undefined and links tests/asan_driver.cpp, which drives every sx_* entry point's argument
-    validation without a GPU: plain bad arguments, every single-field mutation of valid cfg 2 / 3 / 4 / backward / wide / MLP programs
-    with the out-of-range values the round-3 fuzz found, and 60,000 random programs.  No sanitizer report, no accepted bad call."""
+    no device code) with -fsanitize=address,undefined and links tests/asan_driver.cpp, which drives the argument validation of the sx_*
+    entry points without a GPU (all but the eleven its header comment lists -- the spline backward calls sx_rqs_{forward,inverse}_bwd,
+    sx_cubic_{forward,inverse}_bwd, sx_rqs_slab_bwd, sx_rqs_slab_l1_bwd, and sx_resnet_*, sx_spectral_sigma, sx_attention_* --, which
+    it links and does not call): plain bad arguments, every single-field mutation of valid cfg 2 / 3 / 4 / backward / wide / MLP programs with the out-of-range values the
+    round-3 fuzz found, 60,000 random programs, and every range check and per-call check of the four CNF families.  No sanitizer report,
+    no accepted bad call."""
     import subprocess
     csrc = os.path.join(ROOT, 'stribor_amd', 'csrc')
     b = subprocess.run(['make', '-C', csrc, '-j', str(min(8, os.cpu_count() or 1)), 'asan'], capture_output=True, text=True, timeout=900)
