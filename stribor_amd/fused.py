@@ -373,6 +373,13 @@ class _TimeConstJob:
             blobs[self.dst_off:self.dst_off + val.numel()] = val
 
 
+def needs_aligned_copy(data_ptr: int, identity_cols) -> bool:
+    """Must x be copied into a fresh (16-byte aligned) buffer before sx_flow_run2 sees it?  Programs with identity_cols read x with
+    16-byte vector loads and the C ABI rejects any other base (sx_flow_fused.hip: "x must be 16-byte aligned"); the gathered-columns
+    form loads element by element and takes any pointer."""
+    return bool(identity_cols) and data_ptr % 16 != 0
+
+
 class CompiledProgram:
     def __init__(self, prog: _hip.sx_program, blob_floats: int, jobs: List, in_col: Optional[np.ndarray],
                  out_col: Optional[np.ndarray], device: torch.device, mlp_out_dim: int = 0):
@@ -480,6 +487,8 @@ class CompiledProgram:
         assert x.dim() == 2 and x.shape[1] == (self.prog.pad_ or self.prog.dim), (x.shape, self.prog.dim, self.prog.pad_)
         if not x.is_contiguous():
             x = x.contiguous()
+        if needs_aligned_copy(x.data_ptr(), self.prog.identity_cols):
+            x = x.clone()                   # a contiguous view keeps its offset (buf[1:1 + n * d].view(n, d), xb[1:])
         _hip.poll_errors(device=x.device)   # a data-dependent condition of an EARLIER call on x's device (its current stream) surfaces here
         n = x.shape[0]
         if n == 0:        # empty batch: nothing to launch (the reference returns empty tensors too)

@@ -497,3 +497,22 @@ def test_kernel_mode_families_cover_every_mode_once():
     assert 'FAMS    := 0 1 2' in mk and '-DSX_FAMILY=$(1)' in mk
     fused = open(os.path.join(csrc, 'sx_flow_fused.hip')).read()
     assert 'SX_MODE_FAMILY(mlp_mode)' in fused and '_f2(a)' in fused
+
+
+def test_alignment_predicate_picks_the_copy_for_offset_views_of_identity_programs():
+    """CompiledProgram.run copies x exactly when the program loads it with vector accesses (identity_cols) AND its base is not
+    16-byte aligned -- the pointers sx_flow_run2 rejects (sx_flow_fused.hip: "x must be 16-byte aligned"): a contiguous view such as
+    buf[1:1 + n * d].view(n, d) or xb[1:] keeps its offset through .contiguous()."""
+    from stribor_amd.fused import needs_aligned_copy
+    base = 0x7F0000001000
+    for off in range(0, 64, 2):
+        assert needs_aligned_copy(base + off, 1) == (off % 16 != 0), off
+        assert needs_aligned_copy(base + off, 0) is False, off         # gathered columns: element loads, any base
+    buf = torch.zeros(64 + 8)
+    lead = (-(buf.data_ptr() // 4)) % 4
+    for k in range(4):                                                  # fp32 views k elements past a 16-byte boundary
+        v = buf[lead + k: lead + k + 64].view(8, 8).contiguous()
+        assert v.data_ptr() % 16 == 4 * k and needs_aligned_copy(v.data_ptr(), 1) == (k != 0)
+    xb = torch.zeros(9, 12, dtype=torch.bfloat16)                       # bf16 rows of 24 bytes: every other row start is 8 bytes off
+    assert [needs_aligned_copy(xb[i:].data_ptr(), 1) for i in range(4)] == [(xb.data_ptr() + 24 * i) % 16 != 0 for i in range(4)]
+    assert needs_aligned_copy(xb[1:].data_ptr(), 1) != needs_aligned_copy(xb.data_ptr(), 1)
