@@ -1,6 +1,6 @@
 // HBM-bound element-wise kernels of the coupling-flow path (parameters already in HBM).
 // One pass over [n_rows, dim]: coalesced 8/16-byte accesses, per-row log-det sums by wave shuffles.
-#include "sx_common.h"
+#include "sx_stream.h"
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -17,64 +17,14 @@ void sx_set_error(const char *fmt, ...) {
 extern "C" const char *sx_last_error(void) { return g_err; }
 extern "C" int sx_abi_version(void) { return SX_ABI_VERSION; }
 
-static int grid_for(int64_t work_items, int block, int max_blocks = 256 * 8) {
-    int64_t g = (work_items + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > max_blocks) g = max_blocks;
-    return (int)g;
-}
-
-// ------------------------------------------------------------------------------------------------
-// vector row access: 4 consecutive columns per thread
-// ------------------------------------------------------------------------------------------------
-template <bool BF16>
-__device__ __forceinline__ f32x4 load4(const void *base, int64_t elem_off) {
-    if constexpr (BF16) {
-        u16x4 v = *reinterpret_cast<const u16x4 *>(reinterpret_cast<const uint16_t *>(base) + elem_off);
-        return f32x4{bf16_to_f32(v.x), bf16_to_f32(v.y), bf16_to_f32(v.z), bf16_to_f32(v.w)};
-    } else {
-        return *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(base) + elem_off);
-    }
-}
-template <bool BF16>
-__device__ __forceinline__ void store4(void *base, int64_t elem_off, f32x4 v) {
-    if constexpr (BF16) {
-        u16x4 o{f32_to_bf16(v.x), f32_to_bf16(v.y), f32_to_bf16(v.z), f32_to_bf16(v.w)};
-        *reinterpret_cast<u16x4 *>(reinterpret_cast<uint16_t *>(base) + elem_off) = o;
-    } else {
-        *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(base) + elem_off) = v;
-    }
-}
-template <bool BF16>
-__device__ __forceinline__ float load1(const void *base, int64_t elem_off) {
-    if constexpr (BF16) return bf16_to_f32(reinterpret_cast<const uint16_t *>(base)[elem_off]);
-    else return reinterpret_cast<const float *>(base)[elem_off];
-}
-template <bool BF16>
-__device__ __forceinline__ void store1(void *base, int64_t elem_off, float v) {
-    if constexpr (BF16) reinterpret_cast<uint16_t *>(base)[elem_off] = f32_to_bf16(v);
-    else reinterpret_cast<float *>(base)[elem_off] = v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // K3: affine coupling, element-wise part            (stribor/flows/affine.py:104-109, coupling.py:78,95)
 // Fast path: every access is 16 B per lane (8-B accesses run at 0.54-0.70x the 16-B rate on this chip): a thread owns
 // CPT = 8 (bf16 storage) or 4 (fp32) consecutive columns of one row; TPR = dim / CPT threads per row is a power of two
 // <= 64, live columns are the contiguous CPT-aligned range [l0, l0 + n_live).
 // ------------------------------------------------------------------------------------------------
-typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
 // NT: streaming (non-temporal) loads of x / params and stores of y -- every byte is touched once; UNR: rows in flight
 // per thread (independent iterations issued together: more loads outstanding per lane).
-template <bool NT, typename T>
-__device__ __forceinline__ T ld_stream(const T *p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-template <bool NT, typename T>
-__device__ __forceinline__ void st_stream(T *p, T v) {
-    if constexpr (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
 template <bool BF16, bool REVERSE, int UNR, bool NT>
 __global__ __launch_bounds__(256) void affine_coupling_vec_kernel(
     const void *__restrict__ x, void *__restrict__ y, float *__restrict__ ldj,
@@ -97,15 +47,7 @@ __global__ __launch_bounds__(256) void affine_coupling_vec_kernel(
             row[u] = ok[u] ? v >> tpr_log2 : 0;
             c[u] = ((int)(v & (tpr - 1))) * CPT;
             live[u] = ok[u] && c[u] >= l0 && c[u] < l0 + n_live;
-            if (ok[u]) {
-                if constexpr (BF16) {
-                    const u16x8 q = ld_stream<NT>(reinterpret_cast<const u16x8 *>(reinterpret_cast<const uint16_t *>(x) + row[u] * dim + c[u]));
-                    xv[u][0] = f32x4{bf16_to_f32(q[0]), bf16_to_f32(q[1]), bf16_to_f32(q[2]), bf16_to_f32(q[3])};
-                    xv[u][1] = f32x4{bf16_to_f32(q[4]), bf16_to_f32(q[5]), bf16_to_f32(q[6]), bf16_to_f32(q[7])};
-                } else {
-                    xv[u][0] = ld_stream<NT>(reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(x) + row[u] * dim + c[u]));
-                }
-            }
+            if (ok[u]) sx_ldv<BF16, CPT, NT>(x, row[u] * dim + c[u], xv[u]);
             if (live[u]) {
                 const float *p = params + row[u] * pstride + (c[u] - l0);
 #pragma unroll
@@ -137,16 +79,7 @@ __global__ __launch_bounds__(256) void affine_coupling_vec_kernel(
                     s += (L.x + L.y) + (L.z + L.w);
                 }
             }
-            if (ok[u]) {
-                if constexpr (BF16) {
-                    u16x8 o;
-                    o[0] = f32_to_bf16(xv[u][0].x); o[1] = f32_to_bf16(xv[u][0].y); o[2] = f32_to_bf16(xv[u][0].z); o[3] = f32_to_bf16(xv[u][0].w);
-                    o[4] = f32_to_bf16(xv[u][1].x); o[5] = f32_to_bf16(xv[u][1].y); o[6] = f32_to_bf16(xv[u][1].z); o[7] = f32_to_bf16(xv[u][1].w);
-                    st_stream<NT>(reinterpret_cast<u16x8 *>(reinterpret_cast<uint16_t *>(y) + row[u] * dim + c[u]), o);
-                } else {
-                    st_stream<NT>(reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(y) + row[u] * dim + c[u]), xv[u][0]);
-                }
-            }
+            if (ok[u]) sx_stv<BF16, CPT, NT>(y, row[u] * dim + c[u], xv[u]);
             if (ldj != nullptr) {   // wave-uniform (the whole wave shares ok[u] except in the last, partial wave: tpr divides 64)
                 s = group_sum_rt(s, tpr);
                 if (ok[u] && ((v0 + u * stride) & (tpr - 1)) == 0) ldj[row[u]] = (ldj_acc ? ldj[row[u]] : 0.f) + ldj_scale * s;
@@ -173,7 +106,7 @@ __global__ __launch_bounds__(256) void affine_coupling_generic_kernel(
     for (int64_t row = wave; row < n_rows; row += n_waves) {
         float s = 0.f;
         for (int c = lane; c < dim; c += 64) {
-            float xv = load1<BF16>(x, row * dim + c);
+            float xv = sx_ld<BF16>(x, row * dim + c);
             int i = pos[c];
             if (i >= 0) {
                 float ls = params[row * pstride + i];
@@ -181,7 +114,7 @@ __global__ __launch_bounds__(256) void affine_coupling_generic_kernel(
                 xv = REVERSE ? (xv - sh) * fast_exp(-ls) : xv * fast_exp(ls) + sh;
                 s += ls;
             }
-            store1<BF16>(y, row * dim + c, xv);
+            sx_st<BF16>(y, row * dim + c, xv);
         }
         if (ldj != nullptr) {
             s = group_sum<64>(s);
@@ -190,7 +123,6 @@ __global__ __launch_bounds__(256) void affine_coupling_generic_kernel(
     }
 }
 
-static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 extern "C" int sx_affine_coupling(const void *x, void *y, float *ldj, const float *params,
@@ -203,7 +135,7 @@ extern "C" int sx_affine_coupling(const void *x, void *y, float *ldj, const floa
     if (n_rows == 0) return SX_OK;
     hipStream_t st = sx_stream(stream);
     const int cpt = dtype == SX_BF16 ? 8 : 4;
-    const bool fast = live_idx == nullptr && dim % cpt == 0 && pow2(dim / cpt) && dim / cpt <= 64 &&
+    const bool fast = live_idx == nullptr && dim % cpt == 0 && sx_pow2(dim / cpt) && dim / cpt <= 64 &&
                       live_start % cpt == 0 && n_live % cpt == 0 && params_stride % 4 == 0 &&
                       live_start + n_live <= dim && (((uintptr_t)params) & 15) == 0 &&
                       (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 15) == 0;
@@ -213,21 +145,17 @@ extern "C" int sx_affine_coupling(const void *x, void *y, float *ldj, const floa
         // of 8 TB/s): plain loads 0.64-0.69, nt 0.72-0.73, nt + 2 rows + 32 workgroups per CU 0.75 (bf16) / 0.70 (fp32).
         const int unr = dtype == SX_BF16 ? 2 : 1;
         const int grid = grid_for((n_rows << tl) / unr + 1, 256, 256 * (dtype == SX_BF16 ? 32 : 16));
-#define SX_AC(BF, RV, U)                                                                      \
-    hipLaunchKernelGGL((affine_coupling_vec_kernel<BF, RV, U, true>), dim3(grid), dim3(256), 0, st, x, y, ldj, \
-                       params, params_stride, live_start, n_live, n_rows, dim, tl, ldj_accumulate, ldj_scale)
-        if (dtype == SX_BF16) { if (reverse) SX_AC(true, true, 2); else SX_AC(true, false, 2); }
-        else { if (reverse) SX_AC(false, true, 1); else SX_AC(false, false, 1); }
-#undef SX_AC
+        sx_dispatch(dtype == SX_BF16, reverse != 0, [&](auto BF, auto RV) {
+            hipLaunchKernelGGL((affine_coupling_vec_kernel<BF(), RV(), BF() ? 2 : 1, true>), dim3(grid), dim3(256), 0, st, x, y, ldj,
+                               params, params_stride, live_start, n_live, n_rows, dim, tl, ldj_accumulate, ldj_scale);
+        });
     } else {
         const int grid = grid_for(n_rows * 64, 256);
         const size_t lds = (size_t)dim * sizeof(int);
-#define SX_AG(BF, RV)                                                                               \
-    hipLaunchKernelGGL((affine_coupling_generic_kernel<BF, RV>), dim3(grid), dim3(256), lds, st, x, y, ldj, \
-                       params, params_stride, live_idx, live_start, n_live, n_rows, dim, ldj_accumulate, ldj_scale)
-        if (dtype == SX_BF16) { if (reverse) SX_AG(true, true); else SX_AG(true, false); }
-        else { if (reverse) SX_AG(false, true); else SX_AG(false, false); }
-#undef SX_AG
+        sx_dispatch(dtype == SX_BF16, reverse != 0, [&](auto BF, auto RV) {
+            hipLaunchKernelGGL((affine_coupling_generic_kernel<BF(), RV()>), dim3(grid), dim3(256), lds, st, x, y, ldj,
+                               params, params_stride, live_idx, live_start, n_live, n_rows, dim, ldj_accumulate, ldj_scale);
+        });
     }
     SX_LAUNCH_CHECK();
     return SX_OK;
@@ -324,7 +252,7 @@ __global__ __launch_bounds__(256) void time_affine_coupling_kernel(const void *_
         float ld = 0.f;
         const int col = (int)(e - row * dim);
         const int i = slot[col];
-        float xv = BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t *>(x)[e]) : reinterpret_cast<const float *>(x)[e];
+        const float xv = sx_ld<BF16>(x, e);
         float out = xv;
         if (i >= 0) {
             const float tv = t[row];
@@ -333,8 +261,7 @@ __global__ __launch_bounds__(256) void time_affine_coupling_kernel(const void *_
             out = reverse ? (xv - sh) * expf(-ls) : xv * expf(ls) + sh;   // coupling.py:196-199
             ld = ls;                                                       // :201
         }
-        if (BF16) reinterpret_cast<uint16_t *>(y)[e] = f32_to_bf16(out);
-        else reinterpret_cast<float *>(y)[e] = out;
+        sx_st<BF16>(y, e, out);
         return ld;
     };
     if constexpr (ALIGNED) {    // any row length, no atomics: row-aligned units (sx_common.h), fixed-order sums
@@ -342,26 +269,16 @@ __global__ __launch_bounds__(256) void time_affine_coupling_kernel(const void *_
         const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = stride >> 6;
         const sx_units units = sx_make_units(n_rows, dim, true);
         for (int64_t u = wave; u < units.n_units; u += n_waves) {
-            float row_acc = 0.f;
+            sx_row_ldj rl{ldj, ldj_acc, ldj_scale};
             for (int chunk = 0; chunk < units.chunks; ++chunk) {
                 int64_t e0;
                 int n_here;
                 sx_unit_span(units, u, chunk, n_rows, dim, &e0, &n_here);
                 const bool valid = lane < n_here;
                 const int64_t e = e0 + lane, row = valid ? e / dim : 0;
-                const float s0 = valid ? body(e, row) : 0.f;
-                if (units.chunks == 1) {
-                    const int pos = lane % dim;
-                    const float s = segment_sum_rt(s0, pos, dim);
-                    if (valid && pos == 0) ldj[row] = (ldj_acc ? ldj[row] : 0.f) + ldj_scale * s;
-                } else {
-                    row_acc += s0;
-                }
+                rl.chunk(units, valid ? body(e, row) : 0.f, lane % dim, dim, valid, row);
             }
-            if (units.chunks > 1) {
-                const float s = group_sum<64>(row_acc);
-                if (lane == 0) ldj[u] = (ldj_acc ? ldj[u] : 0.f) + ldj_scale * s;
-            }
+            rl.finish(units, lane, u);
         }
         return;
     }
@@ -369,10 +286,7 @@ __global__ __launch_bounds__(256) void time_affine_coupling_kernel(const void *_
         const bool valid = e < total;
         const int64_t row = valid ? e / dim : 0;
         const float ld = valid ? body(e, row) : 0.f;
-        if (ldj_mode == 1) {
-            const float s = group_sum_rt(ld, dim);
-            if (valid && (e & (dim - 1)) == 0) ldj[row] = (ldj_acc ? ldj[row] : 0.f) + ldj_scale * s;
-        }
+        if (ldj_mode == 1) sx_row_ldj{ldj, ldj_acc, ldj_scale}.group(ld, dim, valid && (e & (dim - 1)) == 0, row);
     }
 }
 
@@ -387,18 +301,13 @@ extern "C" int sx_time_affine_coupling(const void *x, void *y, float *ldj, const
     SX_REQUIRE(time_kind == SX_TIME_IDENTITY || tscale != nullptr, "sx_time_affine_coupling: this time net needs its scale vector");
     if (n_rows == 0) return SX_OK;
     hipStream_t st = sx_stream(stream);
-    int ldj_mode = 0;
-    if (ldj) {
-        ldj_mode = (pow2(dim) && dim <= 64) ? 1 : 2;      // 2: row-aligned units, deterministic sums (no atomics)
-    }
+    const int ldj_mode = sx_ldj_mode(ldj, dim);
     const int grid = ldj_mode == 2 ? grid_for(sx_make_units(n_rows, dim, true).n_units * 64, 256) : grid_for(n_rows * dim, 256);
     const size_t lds = (size_t)dim * sizeof(int);
-#define SX_TA(BF, AL)                                                                                             \
-    hipLaunchKernelGGL((time_affine_coupling_kernel<BF, AL>), dim3(grid), dim3(256), lds, st, x, y, ldj, params, params_stride, t, \
-                       tscale, time_kind, live_idx, live_start, n_live, n_rows, dim, reverse, ldj_mode, ldj_accumulate, ldj_scale)
-    if (dtype == SX_BF16) { if (ldj_mode == 2) SX_TA(true, true); else SX_TA(true, false); }
-    else { if (ldj_mode == 2) SX_TA(false, true); else SX_TA(false, false); }
-#undef SX_TA
+    sx_dispatch(dtype == SX_BF16, ldj_mode == 2, [&](auto BF, auto AL) {
+        hipLaunchKernelGGL((time_affine_coupling_kernel<BF(), AL()>), dim3(grid), dim3(256), lds, st, x, y, ldj, params, params_stride,
+                           t, tscale, time_kind, live_idx, live_start, n_live, n_rows, dim, reverse, ldj_mode, ldj_accumulate, ldj_scale);
+    });
     SX_LAUNCH_CHECK();
     return SX_OK;
 }
@@ -445,7 +354,7 @@ __global__ __launch_bounds__(256) void permute_lds_kernel(const T *__restrict__ 
             // every byte is touched once: non-temporal accesses for 4-byte elements (measured: fp32 0.66 -> 0.73 of the HBM peak;
             // 2-byte elements 0.72 -> 0.67, so they keep the plain form)
             const f32x4 *src = reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(x) + (row0 + r) * row_bytes + ch * 16);
-            *reinterpret_cast<f32x4 *>(tile + threadIdx.x * 16) = sizeof(T) == 4 ? __builtin_nontemporal_load(src) : *src;
+            *reinterpret_cast<f32x4 *>(tile + threadIdx.x * 16) = ld_stream<sizeof(T) == 4>(src);
         }
         __syncthreads();
         if (ok) {
@@ -454,8 +363,7 @@ __global__ __launch_bounds__(256) void permute_lds_kernel(const T *__restrict__ 
 #pragma unroll
             for (int e = 0; e < EPC; ++e) o[e] = trow[sidx[ch * EPC + e]];
             f32x4 *dstp = reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(y) + (row0 + r) * row_bytes + ch * 16);
-            if (sizeof(T) == 4) __builtin_nontemporal_store(*reinterpret_cast<const f32x4 *>(o), dstp);
-            else *dstp = *reinterpret_cast<const f32x4 *>(o);
+            st_stream<sizeof(T) == 4>(dstp, *reinterpret_cast<const f32x4 *>(o));
         }
     }
 }
@@ -502,14 +410,13 @@ extern "C" int sx_permute(const void *x, void *y, const int32_t *idx, int64_t n_
 __global__ __launch_bounds__(256) void unit_normal_bf16x8_kernel(const void *__restrict__ x, const float *__restrict__ ldj,
                                                                  float *__restrict__ out, int64_t n_rows, int dim,
                                                                  int tpr_log2) {
-    typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
     const int tpr = 1 << tpr_log2;
     const int64_t n_vec = n_rows << tpr_log2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += stride) {
         const int64_t row = v >> tpr_log2;
         const int c = ((int)(v & (tpr - 1))) << 3;
-        const u16x8 u = *reinterpret_cast<const u16x8 *>(reinterpret_cast<const uint16_t *>(x) + row * dim + c);
+        const sx_u16v<8> u = *reinterpret_cast<const sx_u16v<8> *>(reinterpret_cast<const uint16_t *>(x) + row * dim + c);
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -532,7 +439,8 @@ __global__ __launch_bounds__(256) void unit_normal_vec4_kernel(const void *__res
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += stride) {
         const int64_t row = v >> tpr_log2;
         const int c = ((int)(v & (tpr - 1))) << 2;
-        f32x4 xv = load4<BF16>(x, row * dim + c);
+        f32x4 xv;
+        sx_ldv<BF16, 4, false>(x, row * dim + c, &xv);
         float s = (xv.x * xv.x + xv.y * xv.y) + (xv.z * xv.z + xv.w * xv.w);
         s = group_sum_rt(s, tpr);
         if ((v & (tpr - 1)) == 0)
@@ -549,7 +457,7 @@ __global__ __launch_bounds__(256) void unit_normal_generic_kernel(const void *__
     for (int64_t row = wave; row < n_rows; row += n_waves) {
         float s = 0.f;
         for (int c = lane; c < dim; c += 64) {
-            float v = load1<BF16>(x, row * dim + c);
+            float v = sx_ld<BF16>(x, row * dim + c);
             s += v * v;
         }
         s = group_sum<64>(s);
@@ -564,24 +472,22 @@ extern "C" int sx_unit_normal_logprob(const void *x, const float *ldj, float *ou
     SX_REQUIRE(dtype == SX_F32 || dtype == SX_BF16, "sx_unit_normal_logprob: bad dtype");
     if (n_rows == 0) return SX_OK;
     hipStream_t st = sx_stream(stream);
-    const bool fast = dim % 4 == 0 && pow2(dim / 4) && dim / 4 <= 64 && (((uintptr_t)x) & 15) == 0;
-    if (dtype == SX_BF16 && dim % 8 == 0 && pow2(dim / 8) && dim / 8 <= 64 && (((uintptr_t)x) & 15) == 0) {
+    const bool fast = dim % 4 == 0 && sx_pow2(dim / 4) && dim / 4 <= 64 && (((uintptr_t)x) & 15) == 0;
+    if (dtype == SX_BF16 && dim % 8 == 0 && sx_pow2(dim / 8) && dim / 8 <= 64 && (((uintptr_t)x) & 15) == 0) {
         const int tl = ilog2(dim / 8);
         hipLaunchKernelGGL(unit_normal_bf16x8_kernel, dim3(grid_for(n_rows << tl, 256)), dim3(256), 0, st, x, ldj, out,
                            n_rows, dim, tl);
     } else if (fast) {
         const int tl = ilog2(dim / 4);
         const int grid = grid_for(n_rows << tl, 256);
-        if (dtype == SX_BF16)
-            hipLaunchKernelGGL(unit_normal_vec4_kernel<true>, dim3(grid), dim3(256), 0, st, x, ldj, out, n_rows, dim, tl);
-        else
-            hipLaunchKernelGGL(unit_normal_vec4_kernel<false>, dim3(grid), dim3(256), 0, st, x, ldj, out, n_rows, dim, tl);
+        sx_dispatch(dtype == SX_BF16, [&](auto BF) {
+            hipLaunchKernelGGL(unit_normal_vec4_kernel<BF()>, dim3(grid), dim3(256), 0, st, x, ldj, out, n_rows, dim, tl);
+        });
     } else {
         const int grid = grid_for(n_rows * 64, 256);
-        if (dtype == SX_BF16)
-            hipLaunchKernelGGL(unit_normal_generic_kernel<true>, dim3(grid), dim3(256), 0, st, x, ldj, out, n_rows, dim);
-        else
-            hipLaunchKernelGGL(unit_normal_generic_kernel<false>, dim3(grid), dim3(256), 0, st, x, ldj, out, n_rows, dim);
+        sx_dispatch(dtype == SX_BF16, [&](auto BF) {
+            hipLaunchKernelGGL(unit_normal_generic_kernel<BF()>, dim3(grid), dim3(256), 0, st, x, ldj, out, n_rows, dim);
+        });
     }
     SX_LAUNCH_CHECK();
     return SX_OK;

@@ -7,21 +7,8 @@
 // Element kinds: one lane per element, consecutive lanes = consecutive addresses; the row sum is a shuffle sum when a
 // row is a power-of-two group inside a wave, float atomics otherwise.  Cumsum is a sequential scan per row (one lane
 // per row, running sum in double) so that it reproduces torch.cumsum bit for bit (test_cumsum.py asserts equality).
-#include "sx_common.h"
+#include "sx_stream.h"
 #include <stdlib.h>
-
-__device__ __forceinline__ float pw_softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }   // F.softplus
-
-template <bool BF16>
-__device__ __forceinline__ float pw_load(const void *p, int64_t off) {
-    if constexpr (BF16) return bf16_to_f32(reinterpret_cast<const uint16_t *>(p)[off]);
-    else return reinterpret_cast<const float *>(p)[off];
-}
-template <bool BF16>
-__device__ __forceinline__ void pw_store(void *p, int64_t off, float v) {
-    if constexpr (BF16) reinterpret_cast<uint16_t *>(p)[off] = f32_to_bf16(v);
-    else reinterpret_cast<float *>(p)[off] = v;
-}
 
 #include "sx_pointwise_core.h"
 
@@ -40,21 +27,17 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const void *__restrict__
         float ld_sum = 0.f;
         float xv[VEC], out[VEC], ld[VEC];
         if constexpr (VEC == 4) {
-            if constexpr (BF16) {
-                const u16x4 u = __builtin_nontemporal_load(reinterpret_cast<const u16x4 *>(x) + i);     // every byte is touched once
-                xv[0] = bf16_to_f32(u.x); xv[1] = bf16_to_f32(u.y); xv[2] = bf16_to_f32(u.z); xv[3] = bf16_to_f32(u.w);
-            } else {
-                const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(x) + i);
-                xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
-            }
-        } else xv[0] = pw_load<BF16>(x, i);
+            f32x4 v;
+            sx_ldv<BF16, 4, true>(x, 4 * i, &v);                 // streaming: every byte is touched once
+            xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
+        } else xv[0] = sx_ld<BF16>(x, i);
 #pragma unroll
         for (int c = 0; c < VEC; ++c) { pw_eval(kind, param, log_slope, xv[c], out[c], ld[c]); ld_sum += ld[c]; }
         if (y) {
             if constexpr (VEC == 4) {
-                if constexpr (BF16) __builtin_nontemporal_store(u16x4{f32_to_bf16(out[0]), f32_to_bf16(out[1]), f32_to_bf16(out[2]), f32_to_bf16(out[3])}, reinterpret_cast<u16x4 *>(y) + i);
-                else __builtin_nontemporal_store(f32x4{out[0], out[1], out[2], out[3]}, reinterpret_cast<f32x4 *>(y) + i);
-            } else pw_store<BF16>(y, i, out[0]);
+                const f32x4 o{out[0], out[1], out[2], out[3]};
+                sx_stv<BF16, 4, true>(y, 4 * i, &o);
+            } else sx_st<BF16>(y, i, out[0]);
         }
         if (ldiag) {
             if constexpr (VEC == 4) reinterpret_cast<f32x4 *>(ldiag)[i] = f32x4{ld[0], ld[1], ld[2], ld[3]};
@@ -68,25 +51,15 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const void *__restrict__
         const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = stride >> 6;
         const sx_units units = sx_make_units(n_rows, gdim, true);
         for (int64_t u = wave; u < units.n_units; u += n_waves) {
-            float row_acc = 0.f;
+            sx_row_ldj rl{ldj, ldj_acc, 1.f};                   // no scale here: * 1.f is exact
             for (int chunk = 0; chunk < units.chunks; ++chunk) {
                 int64_t e0;
                 int n_here;
                 sx_unit_span(units, u, chunk, n_rows, gdim, &e0, &n_here);
                 const bool valid = lane < n_here;
-                const float s0 = valid ? body(e0 + lane) : 0.f;
-                if (units.chunks == 1) {
-                    const int pos = lane % gdim;
-                    const float s = segment_sum_rt(s0, pos, gdim);
-                    if (valid && pos == 0) { const int64_t r = (e0 + lane) / gdim; ldj[r] = (ldj_acc ? ldj[r] : 0.f) + s; }
-                } else {
-                    row_acc += s0;
-                }
+                rl.chunk(units, valid ? body(e0 + lane) : 0.f, lane % gdim, gdim, valid, (e0 + lane) / gdim);
             }
-            if (units.chunks > 1) {
-                const float s = group_sum<64>(row_acc);
-                if (lane == 0) ldj[u] = (ldj_acc ? ldj[u] : 0.f) + s;
-            }
+            rl.finish(units, lane, u);
         }
         return;
     }
@@ -95,10 +68,7 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const void *__restrict__
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_up; i += stride) {
         const bool valid = i < total;
         const float ld_sum = valid ? body(i) : 0.f;
-        if (ldj_mode == 1) {            // gdim is a power of two <= 64: rows are aligned lane groups
-            const float s = group_sum_rt(ld_sum, gdim);
-            if (valid && (i & (gdim - 1)) == 0) { const int64_t r = i >> row_shift; ldj[r] = (ldj_acc ? ldj[r] : 0.f) + s; }
-        }
+        if (ldj_mode == 1) sx_row_ldj{ldj, ldj_acc, 1.f}.group(ld_sum, gdim, valid && (i & (gdim - 1)) == 0, i >> row_shift);
     }
 }
 
@@ -120,7 +90,7 @@ __global__ __launch_bounds__(256) void cumsum_kernel(const void *__restrict__ x,
         if (staged) {
             for (int i = lane; i < total; i += 64) {
                 const int r = i / dim, c = i - r * dim;
-                sp[r * RS + c] = pw_load<BF16>(x, r0 * dim + i);
+                sp[r * RS + c] = sx_ld<BF16>(x, r0 * dim + i);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -133,11 +103,11 @@ __global__ __launch_bounds__(256) void cumsum_kernel(const void *__restrict__ x,
             float *row = sp + lane * RS;
             const int64_t g0 = (r0 + lane) * dim;
             for (int c = 0; c < dim; ++c) {
-                const float v = staged ? row[c] : pw_load<BF16>(x, g0 + c);
+                const float v = staged ? row[c] : sx_ld<BF16>(x, g0 + c);
                 float o;
                 if (diff) { o = v - prev; prev = v; }
                 else { acc += (double)v; o = (float)acc; }
-                if (staged) row[c] = o; else pw_store<BF16>(y, g0 + c, o);
+                if (staged) row[c] = o; else sx_st<BF16>(y, g0 + c, o);
             }
         }
         if (staged) {
@@ -145,7 +115,7 @@ __global__ __launch_bounds__(256) void cumsum_kernel(const void *__restrict__ x,
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             for (int i = lane; i < total; i += 64) {
                 const int r = i / dim, c = i - r * dim;
-                pw_store<BF16>(y, r0 * dim + i, sp[r * RS + c]);
+                sx_st<BF16>(y, r0 * dim + i, sp[r * RS + c]);
             }
         }
     }
@@ -326,13 +296,9 @@ extern "C" int sx_pointwise_bwd(const float *x, const float *gy, const float *gl
     if (n_rows == 0) return SX_OK;
     hipStream_t st = sx_stream(stream);
     if (kind == SX_PW_CUMSUM || kind == SX_PW_DIFF) {
-        int64_t g = (n_rows + 255) / 256;
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(cumsum_bwd_kernel, dim3((int)g), dim3(256), 0, st, gy, gx, n_rows, dim, kind == SX_PW_DIFF);
+        hipLaunchKernelGGL(cumsum_bwd_kernel, dim3(grid_for(n_rows, 256)), dim3(256), 0, st, gy, gx, n_rows, dim, kind == SX_PW_DIFF);
     } else {
-        int64_t g = (n_rows * dim + 255) / 256;
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(pointwise_bwd_kernel, dim3((int)g), dim3(256), 0, st, x, gy, gldj, gldiag, gx, n_rows, dim, kind, param);
+        hipLaunchKernelGGL(pointwise_bwd_kernel, dim3(grid_for(n_rows * dim, 256)), dim3(256), 0, st, x, gy, gldj, gldiag, gx, n_rows, dim, kind, param);
     }
     SX_LAUNCH_CHECK();
     return SX_OK;
@@ -349,8 +315,7 @@ extern "C" int sx_pointwise(const void *x, void *y, float *ldj, float *ldiag, in
     if (kind == SX_PW_CUMSUM || kind == SX_PW_DIFF) {
         SX_REQUIRE(x != y, "sx_pointwise: cumsum / diff need a separate output");
         if (y != nullptr) {                 // y == NULL: only the (zero) log-determinants are wanted
-            int64_t g = (n_rows + 255) / 256;
-            if (g > 2048) g = 2048;
+            const int g = grid_for(n_rows, 256);
             const size_t lds4 = (size_t)4 * 64 * (dim + 4) * sizeof(float);
             if (dtype == SX_F32 && dim % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && lds4 <= 150 * 1024 && dim <= 16384) {
                 // the attribute is set to this launch's need (a blanket 160 KiB cost the spline slab backward a workgroup
@@ -375,7 +340,7 @@ extern "C" int sx_pointwise(const void *x, void *y, float *ldj, float *ldiag, in
                     hipLaunchKernelGGL(cumsum_vec_pipe_kernel, dim3((int)gp), dim3(256), lds4, st, (const float *)x, (float *)y, n_rows,
                                        dim, kind == SX_PW_DIFF);
                 } else
-                hipLaunchKernelGGL(cumsum_vec_kernel, dim3((int)g), dim3(256), lds4, st, (const float *)x, (float *)y, n_rows, dim,
+                hipLaunchKernelGGL(cumsum_vec_kernel, dim3(g), dim3(256), lds4, st, (const float *)x, (float *)y, n_rows, dim,
                                    kind == SX_PW_DIFF);
                 SX_LAUNCH_CHECK();
             } else {
@@ -386,8 +351,9 @@ extern "C" int sx_pointwise(const void *x, void *y, float *ldj, float *ldiag, in
                 (void)hipFuncSetAttribute((const void *)cumsum_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
                 (void)hipFuncSetAttribute((const void *)cumsum_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
             }
-            if (dtype == SX_BF16) hipLaunchKernelGGL(cumsum_kernel<true>, dim3((int)g), dim3(256), dyn, st, x, y, n_rows, dim, kind == SX_PW_DIFF, staged);
-            else hipLaunchKernelGGL(cumsum_kernel<false>, dim3((int)g), dim3(256), dyn, st, x, y, n_rows, dim, kind == SX_PW_DIFF, staged);
+            sx_dispatch(dtype == SX_BF16, [&](auto BF) {
+                hipLaunchKernelGGL(cumsum_kernel<BF()>, dim3(g), dim3(256), dyn, st, x, y, n_rows, dim, kind == SX_PW_DIFF, staged);
+            });
             SX_LAUNCH_CHECK();
             }
         }
@@ -405,27 +371,18 @@ extern "C" int sx_pointwise(const void *x, void *y, float *ldj, float *ldiag, in
     const bool vec4 = (dim % 4 == 0) && (((uintptr_t)x % (4 * esz)) == 0) && (y == nullptr || ((uintptr_t)y % (4 * esz)) == 0) &&
                       (ldiag == nullptr || ((uintptr_t)ldiag % 16) == 0);
     const int gdim = vec4 ? dim / 4 : dim;
-    int ldj_mode = 0;
-    if (ldj) {
-        ldj_mode = ((gdim & (gdim - 1)) == 0 && gdim <= 64) ? 1 : 2;      // 2: row-aligned units, deterministic sums
-    }
+    const int ldj_mode = sx_ldj_mode(ldj, gdim);
     // log(negative_slope) in double like math.log (activations.py:99); the inverse kind carries 1 / slope
     float log_slope = 0.f;
     if (kind == SX_PW_LEAKY_RELU || kind == SX_PW_LEAKY_RELU_INV) {
         SX_REQUIRE(param > 0.f, "sx_pointwise: LeakyReLU slope must be positive");
         log_slope = (float)(kind == SX_PW_LEAKY_RELU ? log((double)param) : -log((double)param));
     }
-    int64_t g = ldj_mode == 2 ? (sx_make_units(n_rows, gdim, true).n_units + 3) / 4 : (n_rows * gdim + 255) / 256;
-    if (g > 256 * 8) g = 256 * 8;
-    if (g < 1) g = 1;
-#define SX_PWL2(BF, V, AL)                                                                                        \
-    hipLaunchKernelGGL((pointwise_kernel<BF, V, AL>), dim3((int)g), dim3(256), 0, st, x, y, ldj, ldiag, n_rows, dim, kind, \
-                       param, log_slope, ldj_mode, ldj_accumulate)
-#define SX_PWL(BF, V) do { if (ldj_mode == 2) SX_PWL2(BF, V, true); else SX_PWL2(BF, V, false); } while (0)
-    if (dtype == SX_BF16) { if (vec4) SX_PWL(true, 4); else SX_PWL(true, 1); }
-    else { if (vec4) SX_PWL(false, 4); else SX_PWL(false, 1); }
-#undef SX_PWL
-#undef SX_PWL2
+    const int g = grid_for(ldj_mode == 2 ? sx_make_units(n_rows, gdim, true).n_units * 64 : n_rows * gdim, 256);
+    sx_dispatch(dtype == SX_BF16, vec4, ldj_mode == 2, [&](auto BF, auto V4, auto AL) {
+        hipLaunchKernelGGL((pointwise_kernel<BF(), V4() ? 4 : 1, AL()>), dim3(g), dim3(256), 0, st, x, y, ldj, ldiag, n_rows, dim, kind,
+                           param, log_slope, ldj_mode, ldj_accumulate);
+    });
     SX_LAUNCH_CHECK();
     return SX_OK;
 }

@@ -11,7 +11,7 @@
 // loads, then each lane walks its element's parameters at stride 3K-1 dwords — an odd stride, so the 32
 // lanes of a ds_read_b32 group hit 32 different banks.  No compaction: tails are predicated.  The per-row
 // log-det is a shuffle sum when a row's live columns sit inside one wave, float atomics otherwise.
-#include "sx_common.h"
+#include "sx_stream.h"
 
 #define RQS_MIN_BIN 1e-3f
 #define RQS_MIN_DERIV 1e-3f
@@ -38,46 +38,9 @@ __device__ __forceinline__ void rqs_dma_span(const float *__restrict__ g, float 
     }
 }
 
-__device__ __forceinline__ float softplus_ref(float v) { return v > 20.f ? v : log1pf(expf(v)); }  // F.softplus
-
-template <bool BF16>
-__device__ __forceinline__ float rqs_load(const void *p, int64_t off) {
-    if constexpr (BF16) return bf16_to_f32(reinterpret_cast<const uint16_t *>(p)[off]);
-    else return reinterpret_cast<const float *>(p)[off];
-}
-template <bool BF16>
-__device__ __forceinline__ void rqs_store(void *p, int64_t off, float v) {
-    if constexpr (BF16) reinterpret_cast<uint16_t *>(p)[off] = f32_to_bf16(v);
-    else reinterpret_cast<float *>(p)[off] = v;
-}
-
-// copies the pass-through (mask == 1) columns: y = T(x)*(1-m) + x*m (coupling.py:78)
-template <bool BF16>
-__global__ __launch_bounds__(256) void rqs_copy_passthrough_kernel(const void *__restrict__ x, void *__restrict__ y,
-                                                                   float *__restrict__ ldiag,
-                                                                   const int32_t *__restrict__ live_idx, int l0,
-                                                                   int n_live, int64_t n_rows, int dim, int copy_x) {
-    extern __shared__ __attribute__((aligned(16))) char cp_smem[];
-    int *is_live = reinterpret_cast<int *>(cp_smem);
-    for (int c = threadIdx.x; c < dim; c += blockDim.x) is_live[c] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n_live; i += blockDim.x) is_live[live_idx ? live_idx[i] : l0 + i] = 1;
-    __syncthreads();
-    const int64_t total = n_rows * dim;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const int c = (int)(i % dim);
-        if (!is_live[c]) {
-            if (copy_x) rqs_store<BF16>(y, i, rqs_load<BF16>(x, i));
-            if (ldiag) ldiag[i] = 0.f;
-        }
-    }
-}
-
 // ---- straight-line evaluation for K = 16 (the BASELINE configuration): parameters in registers, selects only ----
-__device__ __forceinline__ float rqs_fast_exp(float v) { return __builtin_amdgcn_exp2f(v * 1.44269504088896341f); }
 __device__ __forceinline__ float rqs_fast_log(float v) { return __builtin_amdgcn_logf(v) * 0.69314718055994531f; }
-__device__ __forceinline__ float rqs_fast_softplus(float v) { return v > 20.f ? v : rqs_fast_log(1.f + rqs_fast_exp(v)); }
+__device__ __forceinline__ float rqs_fast_softplus(float v) { return v > 20.f ? v : rqs_fast_log(1.f + fast_exp(v)); }
 
 // softmax numerators in place; returns the factor turning them into bin sizes (size_k = MIN + e_k * inv), :101-105
 __device__ __forceinline__ float rqs16_softmax(float (&u)[16]) {
@@ -87,7 +50,7 @@ __device__ __forceinline__ float rqs16_softmax(float (&u)[16]) {
     float sum = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-        u[k] = rqs_fast_exp(u[k] - mx);
+        u[k] = fast_exp(u[k] - mx);
         sum += u[k];
     }
     return (1.f - RQS_MIN_BIN * 16.f) * __builtin_amdgcn_rcpf(sum);
@@ -208,16 +171,15 @@ __global__ __launch_bounds__(256) void rqs_kernel(const void *__restrict__ x, vo
     auto load_x = [&](int64_t e) {
         const int64_t row = e / n_live;
         const int i = (int)(e - row * n_live);
-        return rqs_load<BF16>(x, row * dim + (live_idx ? live_idx[i] : l0 + i));
+        return sx_ld<BF16>(x, row * dim + (live_idx ? live_idx[i] : l0 + i));
     };
     for (int64_t grp = (int64_t)blockIdx.x * waves_per_block + wave; grp < n_groups;
          grp += (int64_t)gridDim.x * waves_per_block) {
-      [[maybe_unused]] float row_acc = 0.f;    // ALIGNED, rows wider than a wave: the row's sum over its chunks
+      sx_row_ldj rl{ldj, ldj_acc, ldj_scale};
       for (int chunk = 0; chunk < (ALIGNED ? units.chunks : 1); ++chunk) {
         int64_t e0;
         int n_here;
-        if constexpr (ALIGNED) sx_unit_span(units, grp, chunk, n_rows, n_live, &e0, &n_here);
-        else { e0 = grp << 6; n_here = (int)((n_elem - e0) < 64 ? (n_elem - e0) : 64); }
+        sx_unit_span(units, grp, chunk, n_rows, n_live, &e0, &n_here);      // dense units unless ALIGNED
         // ---- stage the elements' parameters: consecutive idx -> consecutive HBM addresses inside a row ----
         const int total = n_here * P;
         [[maybe_unused]] rqs16_regs pr;
@@ -260,7 +222,7 @@ __global__ __launch_bounds__(256) void rqs_kernel(const void *__restrict__ x, vo
         const int64_t row = valid ? e / n_live : 0;
         const int i = valid ? (int)(e - row * n_live) : 0;
         const int col = live_idx ? live_idx[i] : l0 + i;
-        const float xv = dense16 ? x_dense : (valid ? rqs_load<BF16>(x, row * dim + col) : lo_in);
+        const float xv = dense16 ? x_dense : (valid ? sx_ld<BF16>(x, row * dim + col) : lo_in);
         float out, ljd;
         if (K == 16) {      // wave-uniform: straight-line register path
             bool bad;
@@ -299,8 +261,8 @@ __global__ __launch_bounds__(256) void rqs_kernel(const void *__restrict__ x, vo
         const float w_b = cw_n - cw_b;                                           // :185
         const float h_b = ch_n - ch_b;                                           // :192
         const float s_b = h_b / w_b;                                             // :203-204
-        const float d_b = RQS_MIN_DERIV + softplus_ref(b == 0 ? bconst : ud[b - 1]);        // :107, :206
-        const float d_n = RQS_MIN_DERIV + softplus_ref(b + 1 == K ? bconst : ud[b]);        // :207
+        const float d_b = RQS_MIN_DERIV + sx_softplus(b == 0 ? bconst : ud[b - 1]);        // :107, :206
+        const float d_n = RQS_MIN_DERIV + sx_softplus(b + 1 == K ? bconst : ud[b]);        // :207
 
         if constexpr (INVERSE) {
             const float dy = xin - ch_b;
@@ -330,34 +292,15 @@ __global__ __launch_bounds__(256) void rqs_kernel(const void *__restrict__ x, vo
         if (!inside) { out = xv; ljd = 0.f; }                                    // :86-87 linear tails
         }
         if (valid) {
-            rqs_store<BF16>(y, row * dim + col, out);
+            sx_st<BF16>(y, row * dim + col, out);
             if (ldiag) ldiag[row * dim + col] = ljd;
         }
-        if (ldj_mode == 1) {                 // n_live is a power of two <= 64: a row never leaves the wave
-            float s = valid ? ljd : 0.f;
-            s = group_sum_rt(s, n_live);
-            if (valid && (lane & (n_live - 1)) == 0) ldj[row] = (ldj_acc ? ldj[row] : 0.f) + ldj_scale * s;
-        }
-        if constexpr (ALIGNED) {             // row-aligned units: fixed-order sums, no atomics
-            const float s0 = valid ? ljd : 0.f;
-            if (units.chunks == 1) {
-                const float s = segment_sum_rt(s0, i, n_live);
-                if (valid && i == 0) ldj[row] = (ldj_acc ? ldj[row] : 0.f) + ldj_scale * s;
-            } else {
-                row_acc += s0;
-            }
-        }
+        if (ldj_mode == 1) rl.group(valid ? ljd : 0.f, n_live, valid && (lane & (n_live - 1)) == 0, row);
+        if constexpr (ALIGNED) rl.chunk(units, valid ? ljd : 0.f, i, n_live, valid, row);
       }
-      if constexpr (ALIGNED) {
-          if (units.chunks > 1) {
-              const float s = group_sum<64>(row_acc);
-              if (lane == 0) ldj[grp] = (ldj_acc ? ldj[grp] : 0.f) + ldj_scale * s;
-          }
-      }
+      if constexpr (ALIGNED) rl.finish(units, lane, grp);
     }
 }
-
-static bool rqs_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 extern "C" int sx_rqs_coupling(const void *x, void *y, float *ldj, float *ldiag, const float *params,
                                int64_t params_stride, const int32_t *live_idx, int32_t live_start, int32_t n_live,
@@ -373,57 +316,16 @@ extern "C" int sx_rqs_coupling(const void *x, void *y, float *ldj, float *ldiag,
     SX_REQUIRE(right > left && top > bottom, "sx_rqs_coupling: empty domain");
     if (n_rows == 0) return SX_OK;
     hipStream_t st = sx_stream(stream);
-    const int P = 3 * n_bins - 1;
-    int block = 256;
-    size_t lds = (size_t)(block / 64) * 64 * P * sizeof(float);
-    if (lds > 64 * 1024) { block = 64; lds = (size_t)64 * P * sizeof(float); }
-    SX_REQUIRE(lds <= 160 * 1024, "sx_rqs_coupling: n_bins %d needs %zu B of LDS per wave", n_bins, lds);
-
-    // pass-through columns (and their zero log-diag entries)
-    if (n_live < dim && (x != y || ldiag)) {
-        int64_t g = (n_rows * dim + 255) / 256;
-        if (g > 2048) g = 2048;
-        if (dtype == SX_BF16)
-            hipLaunchKernelGGL(rqs_copy_passthrough_kernel<true>, dim3((int)g), dim3(256), dim * sizeof(int), st, x, y,
-                               ldiag, live_idx, live_start, n_live, n_rows, dim, x != y);
-        else
-            hipLaunchKernelGGL(rqs_copy_passthrough_kernel<false>, dim3((int)g), dim3(256), dim * sizeof(int), st, x, y,
-                               ldiag, live_idx, live_start, n_live, n_rows, dim, x != y);
-        SX_LAUNCH_CHECK();
-    }
-    if (n_live == 0) {
-        if (ldj && !ldj_accumulate) {
-            hipError_t e = hipMemsetAsync(ldj, 0, n_rows * sizeof(float), st);
-            if (e != hipSuccess) { sx_set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-        }
-        return SX_OK;
-    }
-    int ldj_mode = 0;
-    if (ldj) {
-        ldj_mode = (rqs_pow2(n_live) && n_live <= 64) ? 1 : 2;      // 2: row-aligned units, deterministic sums
-    }
-    const int64_t n_groups = sx_make_units(n_rows, n_live, ldj_mode == 2).n_units;
-    const int wpb = block / 64;
-    int64_t grid = (n_groups + wpb - 1) / wpb;
-    const int64_t max_grid = 256 * (int64_t)((160 * 1024) / (lds ? lds : 1) > 8 ? 8 : (160 * 1024) / (lds ? lds : 1));
-    if (grid > max_grid) grid = max_grid;
-    if (grid < 1) grid = 1;
-    if (lds > 48 * 1024) {
-#define SX_ATTR(BF, INV)                                                                                          \
-    (void)hipFuncSetAttribute((const void *)rqs_kernel<BF, INV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    (void)hipFuncSetAttribute((const void *)rqs_kernel<BF, INV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-        SX_ATTR(true, true); SX_ATTR(true, false); SX_ATTR(false, true); SX_ATTR(false, false);
-#undef SX_ATTR
-    }
-#define SX_RQ2(BF, INV, AL)                                                                                      \
-    hipLaunchKernelGGL((rqs_kernel<BF, INV, AL>), dim3((int)grid), dim3(block), lds, st, x, y, ldj, ldiag, params, \
-                       params_stride, live_idx, live_start, n_live, n_bins, left, right, bottom, top, n_rows, dim, \
-                       ldj_mode, ldj_accumulate, ldj_scale, err_flag)
-#define SX_RQ(BF, INV) do { if (ldj_mode == 2) SX_RQ2(BF, INV, true); else SX_RQ2(BF, INV, false); } while (0)
-    if (dtype == SX_BF16) { if (reverse) SX_RQ(true, true); else SX_RQ(true, false); }
-    else { if (reverse) SX_RQ(false, true); else SX_RQ(false, false); }
-#undef SX_RQ
-#undef SX_RQ2
+    sx_spline_plan pl;
+    const int rc = sx_plan_spline("sx_rqs_coupling", x, y, ldj, ldiag, live_idx, live_start, n_live, n_bins, 3 * n_bins - 1, n_rows, dim,
+                                  dtype, ldj_accumulate, st,
+                                  [](auto BF, auto INV, auto AL) { return (const void *)rqs_kernel<BF(), INV(), AL()>; }, &pl);
+    if (rc != SX_OK || pl.grid == 0) return rc;
+    sx_dispatch(dtype == SX_BF16, reverse != 0, pl.ldj_mode == 2, [&](auto BF, auto INV, auto AL) {
+        hipLaunchKernelGGL((rqs_kernel<BF(), INV(), AL()>), dim3(pl.grid), dim3(pl.sl.block), pl.sl.lds, st, x, y, ldj, ldiag, params,
+                           params_stride, live_idx, live_start, n_live, n_bins, left, right, bottom, top, n_rows, dim,
+                           pl.ldj_mode, ldj_accumulate, ldj_scale, err_flag);
+    });
     SX_LAUNCH_CHECK();
     return SX_OK;
 }
@@ -522,7 +424,7 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
     auto load_x = [&](int64_t e) {
         const int64_t row = e / n_live;
         const int i = (int)(e - row * n_live);
-        return rqs_load<BF16>(x, row * dim + (live_idx ? live_idx[i] : l0 + i));
+        return sx_ld<BF16>(x, row * dim + (live_idx ? live_idx[i] : l0 + i));
     };
     const float span = upper - lower;                            // right - left = top - bottom
     const float inv_span = 1.0f / span;
@@ -531,12 +433,11 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
 
     for (int64_t grp = (int64_t)blockIdx.x * waves_per_block + wave; grp < n_groups;
          grp += (int64_t)gridDim.x * waves_per_block) {
-      [[maybe_unused]] float row_acc = 0.f;    // ALIGNED, rows wider than a wave: the row's sum over its chunks
+      sx_row_ldj rl{ldj, ldj_acc, ldj_scale};
       for (int chunk = 0; chunk < (ALIGNED ? units.chunks : 1); ++chunk) {
         int64_t e0;
         int n_here;
-        if constexpr (ALIGNED) sx_unit_span(units, grp, chunk, n_rows, n_live, &e0, &n_here);
-        else { e0 = grp << 6; n_here = (int)((n_elem - e0) < 64 ? (n_elem - e0) : 64); }
+        sx_unit_span(units, grp, chunk, n_rows, n_live, &e0, &n_here);      // dense units unless ALIGNED
         const int total = n_here * P;
         // ---- stage: consecutive idx -> consecutive HBM addresses (one contiguous span when rows are packed) ----
         // K even (P / 2 odd): the span is copied as it is (16 B per lane in, 16 B out) and a lane reads its element's parameters
@@ -609,7 +510,7 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
         const int64_t row = valid ? e / n_live : 0;
         const int i = valid ? (int)(e - row * n_live) : 0;
         const int col = live_idx ? live_idx[i] : l0 + i;
-        const float xv = dma16 ? x_dense : (valid ? rqs_load<BF16>(x, row * dim + col) : lower);
+        const float xv = dma16 ? x_dense : (valid ? sx_ld<BF16>(x, row * dim + col) : lower);
         const bool inside = (xv >= lower) && (xv <= upper);      // :40 closed interval
         const float xin = ((inside ? xv : lower) - lower) * inv_span;        // :98-101
         float *p = sp + (valid ? lane : 0) * (lin ? P : PS);     // [0,K) widths, [K,2K) heights, 2K / 2K+1 derivatives
@@ -754,30 +655,13 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
         }
         if (!inside) { out = xv; ljd = 0.f; }                                              // :46-48 linear tails
         if (valid) {
-            rqs_store<BF16>(y, row * dim + col, out);
+            sx_st<BF16>(y, row * dim + col, out);
             if (ldiag) ldiag[row * dim + col] = ljd;
         }
-        if (ldj_mode == 1) {
-            float s = valid ? ljd : 0.f;
-            s = group_sum_rt(s, n_live);
-            if (valid && (lane & (n_live - 1)) == 0) ldj[row] = (ldj_acc ? ldj[row] : 0.f) + ldj_scale * s;
-        }
-        if constexpr (ALIGNED) {             // row-aligned units: fixed-order sums, no atomics
-            const float s0 = valid ? ljd : 0.f;
-            if (units.chunks == 1) {
-                const float s = segment_sum_rt(s0, i, n_live);
-                if (valid && i == 0) ldj[row] = (ldj_acc ? ldj[row] : 0.f) + ldj_scale * s;
-            } else {
-                row_acc += s0;
-            }
-        }
+        if (ldj_mode == 1) rl.group(valid ? ljd : 0.f, n_live, valid && (lane & (n_live - 1)) == 0, row);
+        if constexpr (ALIGNED) rl.chunk(units, valid ? ljd : 0.f, i, n_live, valid, row);
       }
-      if constexpr (ALIGNED) {
-          if (units.chunks > 1) {
-              const float s = group_sum<64>(row_acc);
-              if (lane == 0) ldj[grp] = (ldj_acc ? ldj[grp] : 0.f) + ldj_scale * s;
-          }
-      }
+      if constexpr (ALIGNED) rl.finish(units, lane, grp);
     }
 }
 
@@ -794,54 +678,16 @@ extern "C" int sx_cubic_coupling(const void *x, void *y, float *ldj, float *ldia
     if (n_rows == 0) return SX_OK;
     hipStream_t st = sx_stream(stream);
     const float log_span = (float)log((double)upper - (double)lower);      // math.log(top - bottom), cast as torch does
-    const int PS = (2 * n_bins + 2) | 1;
-    int block = 256;
-    size_t lds = (size_t)(block / 64) * 64 * PS * sizeof(float);
-    if (lds > 64 * 1024) { block = 64; lds = (size_t)64 * PS * sizeof(float); }
-    SX_REQUIRE(lds <= 160 * 1024, "sx_cubic_coupling: n_bins %d needs %zu B of LDS per wave", n_bins, lds);
-    if (n_live < dim && (x != y || ldiag)) {            // pass-through columns (and their zero log-diag entries)
-        int64_t g = (n_rows * dim + 255) / 256;
-        if (g > 2048) g = 2048;
-        if (dtype == SX_BF16)
-            hipLaunchKernelGGL(rqs_copy_passthrough_kernel<true>, dim3((int)g), dim3(256), dim * sizeof(int), st, x, y,
-                               ldiag, live_idx, live_start, n_live, n_rows, dim, x != y);
-        else
-            hipLaunchKernelGGL(rqs_copy_passthrough_kernel<false>, dim3((int)g), dim3(256), dim * sizeof(int), st, x, y,
-                               ldiag, live_idx, live_start, n_live, n_rows, dim, x != y);
-        SX_LAUNCH_CHECK();
-    }
-    int ldj_mode = 0;
-    if (ldj) {
-        ldj_mode = (n_live > 0 && rqs_pow2(n_live) && n_live <= 64) ? 1 : 2;      // 2: row-aligned units, deterministic
-        if (n_live == 0 && !ldj_accumulate) {
-            hipError_t e = hipMemsetAsync(ldj, 0, n_rows * sizeof(float), st);
-            if (e != hipSuccess) { sx_set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-        }
-    }
-    if (n_live == 0) return SX_OK;
-    const int64_t n_groups = sx_make_units(n_rows, n_live, ldj_mode == 2).n_units;
-    const int wpb = block / 64;
-    int64_t grid = (n_groups + wpb - 1) / wpb;
-    const int64_t per_cu = (160 * 1024) / (int64_t)lds > 8 ? 8 : (160 * 1024) / (int64_t)lds;
-    if (grid > 256 * per_cu) grid = 256 * per_cu;
-    if (grid < 1) grid = 1;
-    if (lds > 48 * 1024) {
-#define SX_ATTR(BF, INV)                                                                                          \
-    (void)hipFuncSetAttribute((const void *)cubic_kernel<BF, INV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    (void)hipFuncSetAttribute((const void *)cubic_kernel<BF, INV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-        SX_ATTR(true, true); SX_ATTR(true, false); SX_ATTR(false, true); SX_ATTR(false, false);
-#undef SX_ATTR
-    }
-#define SX_CB2(BF, INV, AL)                                                                                       \
-    hipLaunchKernelGGL((cubic_kernel<BF, INV, AL>), dim3((int)grid), dim3(block), lds, st, x, y, ldj, ldiag, params, \
-                       params_stride, live_idx, live_start, n_live, n_bins, lower, upper, log_span, n_rows, dim,   \
-                       ldj_mode,                                                                                  \
-                       ldj_accumulate, ldj_scale, (int)(reverse == 2))
-#define SX_CB(BF, INV) do { if (ldj_mode == 2) SX_CB2(BF, INV, true); else SX_CB2(BF, INV, false); } while (0)
-    if (dtype == SX_BF16) { if (reverse) SX_CB(true, true); else SX_CB(true, false); }
-    else { if (reverse) SX_CB(false, true); else SX_CB(false, false); }
-#undef SX_CB
-#undef SX_CB2
+    sx_spline_plan pl;
+    const int rc = sx_plan_spline("sx_cubic_coupling", x, y, ldj, ldiag, live_idx, live_start, n_live, n_bins, (2 * n_bins + 2) | 1, n_rows,
+                                  dim, dtype, ldj_accumulate, st,
+                                  [](auto BF, auto INV, auto AL) { return (const void *)cubic_kernel<BF(), INV(), AL()>; }, &pl);
+    if (rc != SX_OK || pl.grid == 0) return rc;
+    sx_dispatch(dtype == SX_BF16, reverse != 0, pl.ldj_mode == 2, [&](auto BF, auto INV, auto AL) {
+        hipLaunchKernelGGL((cubic_kernel<BF(), INV(), AL()>), dim3(pl.grid), dim3(pl.sl.block), pl.sl.lds, st, x, y, ldj, ldiag, params,
+                           params_stride, live_idx, live_start, n_live, n_bins, lower, upper, log_span, n_rows, dim,
+                           pl.ldj_mode, ldj_accumulate, ldj_scale, (int)(reverse == 2));
+    });
     SX_LAUNCH_CHECK();
     return SX_OK;
 }
@@ -928,29 +774,18 @@ static int rqs_bwd_launch(bool inverse, const float *x, const float *gout, const
     SX_REQUIRE(dim > 0 && n_live > 0 && n_live <= dim && n_rows >= 0 && n_bins >= 1, "sx_rqs_*_bwd: bad sizes");
     SX_REQUIRE(right > left && top > bottom, "sx_rqs_*_bwd: empty domain");
     if (n_rows == 0) return SX_OK;
-    const int P = 3 * n_bins - 1;
-    int block = 256;
-    size_t lds = (size_t)(block / 64) * 64 * P * sizeof(float);
-    if (lds > 64 * 1024) { block = 64; lds = (size_t)64 * P * sizeof(float); }
-    SX_REQUIRE(lds <= 160 * 1024, "sx_rqs_*_bwd: n_bins %d needs %zu B of LDS per wave", n_bins, lds);
-    if (lds > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void *)rqs_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void *)rqs_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const sx_slice_plan sl = sx_plan_slices(3 * n_bins - 1);
+    SX_REQUIRE(sl.lds <= 160 * 1024, "sx_rqs_*_bwd: n_bins %d needs %zu B of LDS per wave", n_bins, sl.lds);
+    if (sl.lds > 48 * 1024) {
+        (void)hipFuncSetAttribute((const void *)rqs_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds);
+        (void)hipFuncSetAttribute((const void *)rqs_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds);
     }
-    const int64_t n_groups = (n_rows * n_live + 63) / 64;
-    const int wpb = block / 64;
-    int64_t grid = (n_groups + wpb - 1) / wpb;
-    const int64_t per_cu = (160 * 1024) / (int64_t)lds > 8 ? 8 : (160 * 1024) / (int64_t)lds;
-    if (grid > 256 * per_cu) grid = 256 * per_cu;
-    if (grid < 1) grid = 1;
-    if (inverse)
-        hipLaunchKernelGGL(rqs_bwd_kernel<true>, dim3((int)grid), dim3(block), lds, sx_stream(stream), x, gout, gldj, gldiag, params,
+    const int grid = sl.grid((n_rows * n_live + 63) / 64);
+    sx_dispatch(inverse, [&](auto INV) {
+        hipLaunchKernelGGL(rqs_bwd_kernel<INV()>, dim3(grid), dim3(sl.block), sl.lds, sx_stream(stream), x, gout, gldj, gldiag, params,
                            params_stride, gx, gparams, live_idx, live_start, n_live, n_bins, left, right, bottom, top, n_rows,
                            dim, ldj_scale);
-    else
-        hipLaunchKernelGGL(rqs_bwd_kernel<false>, dim3((int)grid), dim3(block), lds, sx_stream(stream), x, gout, gldj, gldiag, params,
-                           params_stride, gx, gparams, live_idx, live_start, n_live, n_bins, left, right, bottom, top, n_rows,
-                           dim, ldj_scale);
+    });
     SX_LAUNCH_CHECK();
     return SX_OK;
 }
@@ -1159,30 +994,18 @@ static int cubic_bwd_launch(bool inverse, const float *yin, const float *xout, c
     SX_REQUIRE(dim > 0 && n_live > 0 && n_live <= dim && n_rows >= 0 && n_bins >= 1, "sx_cubic_inverse_bwd: bad sizes");
     SX_REQUIRE(upper > lower, "sx_cubic_inverse_bwd: empty domain");
     if (n_rows == 0) return SX_OK;
-    const int PS = (2 * n_bins + 2) | 1;
-    int block = 256;
-    size_t lds = (size_t)(block / 64) * 64 * PS * sizeof(float);
-    if (lds > 64 * 1024) { block = 64; lds = (size_t)64 * PS * sizeof(float); }
-    SX_REQUIRE(lds <= 160 * 1024, "sx_cubic_inverse_bwd: n_bins %d needs %zu B of LDS per wave", n_bins, lds);
-    if (lds > 48 * 1024)
-        {
-        (void)hipFuncSetAttribute((const void *)cubic_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void *)cubic_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const sx_slice_plan sl = sx_plan_slices((2 * n_bins + 2) | 1);
+    SX_REQUIRE(sl.lds <= 160 * 1024, "sx_cubic_inverse_bwd: n_bins %d needs %zu B of LDS per wave", n_bins, sl.lds);
+    if (sl.lds > 48 * 1024) {
+        (void)hipFuncSetAttribute((const void *)cubic_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds);
+        (void)hipFuncSetAttribute((const void *)cubic_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds);
     }
-    const int64_t n_groups = (n_rows * n_live + 63) / 64;
-    const int wpb = block / 64;
-    int64_t grid = (n_groups + wpb - 1) / wpb;
-    const int64_t per_cu = (160 * 1024) / (int64_t)lds > 8 ? 8 : (160 * 1024) / (int64_t)lds;
-    if (grid > 256 * per_cu) grid = 256 * per_cu;
-    if (grid < 1) grid = 1;
-    if (inverse)
-        hipLaunchKernelGGL(cubic_bwd_kernel<true>, dim3((int)grid), dim3(block), lds, sx_stream(stream), yin, xout, gout, gldj, gldiag,
+    const int grid = sl.grid((n_rows * n_live + 63) / 64);
+    sx_dispatch(inverse, [&](auto INV) {
+        hipLaunchKernelGGL(cubic_bwd_kernel<INV()>, dim3(grid), dim3(sl.block), sl.lds, sx_stream(stream), yin, xout, gout, gldj, gldiag,
                            params, params_stride, gx, gparams, live_idx, live_start, n_live, n_bins, lower, upper, n_rows, dim,
                            ldj_scale);
-    else
-        hipLaunchKernelGGL(cubic_bwd_kernel<false>, dim3((int)grid), dim3(block), lds, sx_stream(stream), yin, xout, gout, gldj, gldiag,
-                           params, params_stride, gx, gparams, live_idx, live_start, n_live, n_bins, lower, upper, n_rows, dim,
-                           ldj_scale);
+    });
     SX_LAUNCH_CHECK();
     return SX_OK;
 }

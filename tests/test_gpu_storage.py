@@ -140,7 +140,7 @@ def affine_call(x, params, pstride, idx, l0, nl, reverse, ldj=None, acc=0, scale
 
 
 def affine_vec_expected(x, y, params, pstride, idx, l0, nl):
-    """sx_elementwise.hip:205-209, restated"""
+    """sx_affine_coupling's `fast` condition, restated"""
     d = x.shape[1]
     cpt = 8 if x.dtype == torch.bfloat16 else 4
     return (idx is None and d % cpt == 0 and pow2(d // cpt) and d // cpt <= 64 and l0 % cpt == 0 and nl % cpt == 0 and pstride % 4 == 0
@@ -149,19 +149,19 @@ def affine_vec_expected(x, y, params, pstride, idx, l0, nl):
 
 def affine_table(c):
     """(branch, dim, live_start, n_live, params_stride - 2 n_live | 'row', live_idx?, vec kernel?) in units of c = columns per thread
-    (fp32 4, bf16 8); the reason a row leaves the vec kernel is the ONE clause of sx_elementwise.hip:206-209 it violates."""
+    (fp32 4, bf16 8); the reason a row leaves the vec kernel is the ONE clause of sx_affine_coupling's `fast` condition it violates."""
     return [('vec, dim/cpt = 1', c, 0, c, 0, False, True),
             ('vec, dim/cpt = 2', 2 * c, c, c, 0, False, True),
             ('vec, dim/cpt = 64', 64 * c, 16 * c, 32 * c, 0, False, True),
             ('vec, padded parameter rows (stride % 4 == 0)', 8 * c, 0, 4 * c, 4, False, True),
             ('vec, one broadcast parameter row (stride 0)', 8 * c, 4 * c, 4 * c, 'row', False, True),
-            ('generic: dim % cpt != 0', 8 * c + 2, c, c, 0, False, False),                       # :206 dim % cpt == 0
-            ('generic: dim/cpt = 3, not a power of two', 3 * c, c, c, 0, False, False),          # :206 pow2(dim / cpt)
-            ('generic: dim/cpt = 128 > 64', 128 * c, 0, 64 * c, 0, False, False),                # :206 dim / cpt <= 64
-            ('generic: live_start % cpt != 0', 8 * c, c + 1, c, 0, False, False),                # :207
-            ('generic: n_live % cpt != 0', 8 * c, c, c + 1, 0, False, False),                    # :207
-            ('generic: params_stride % 4 != 0', 8 * c, c, c, 1, False, False),                   # :207
-            ('generic: live_idx list', 8 * c, 0, 2 * c, 0, True, False)]                         # :206 live_idx == nullptr
+            ('generic: dim % cpt != 0', 8 * c + 2, c, c, 0, False, False),                       # dim % cpt == 0
+            ('generic: dim/cpt = 3, not a power of two', 3 * c, c, c, 0, False, False),          # sx_pow2(dim / cpt)
+            ('generic: dim/cpt = 128 > 64', 128 * c, 0, 64 * c, 0, False, False),                # dim / cpt <= 64
+            ('generic: live_start % cpt != 0', 8 * c, c + 1, c, 0, False, False),                # live_start % cpt == 0
+            ('generic: n_live % cpt != 0', 8 * c, c, c + 1, 0, False, False),                    # n_live % cpt == 0
+            ('generic: params_stride % 4 != 0', 8 * c, c, c, 1, False, False),                   # params_stride % 4 == 0
+            ('generic: live_idx list', 8 * c, 0, 2 * c, 0, True, False)]                         # live_idx == nullptr
 
 
 def affine_case(n, d, l0, nl, pad, use_idx, bf, seed):
@@ -206,7 +206,7 @@ def test_affine_coupling_dispatch(row, bf):
 # sx_time_affine_coupling
 # ------------------------------------------------------------------------------------------------------------------------------
 TIME_KINDS = ('identity', 'linear', 'tanh', 'log')
-# dim -> ldj_mode with an ldj buffer (sx_elementwise.hip:392: power-of-two width <= 64 ? 1 : 2; dim 1 is a power of two there)
+# dim -> ldj_mode with an ldj buffer (sx_ldj_mode in sx_time_affine_coupling: power-of-two width <= 64 ? 1 : 2; dim 1 is a power of two there)
 TIME_DIMS = {1: 1, 8: 1, 64: 1, 7: 2, 65: 2, 100: 2}
 
 
@@ -293,7 +293,7 @@ def spline_refs(cubic, xl, table, nl, K, reverse, dtype):
     return f(xl.to(dtype), uw, uh, ud, reverse, LO, HI)
 
 
-# (form, dim, live_start, n_live, live_idx?, params_stride - n_live P, ldj_mode with an ldj buffer -- sx_rqs.hip:403 / :815)
+# (form, dim, live_start, n_live, live_idx?, params_stride - n_live P, ldj_mode with an ldj buffer -- sx_ldj_mode(ldj, n_live) in sx_plan_spline)
 SPLINE_FORMS = [('dense 64-element spans, n_live 4', 12, 3, 4, False, 0, 1),
                 ('dense 64-element spans, n_live 32', 40, 8, 32, False, 0, 1),
                 ('row-aligned units, n_live 5', 12, 3, 5, False, 0, 2),
@@ -303,7 +303,7 @@ SPLINE_FORMS = [('dense 64-element spans, n_live 4', 12, 3, 4, False, 0, 1),
                 ('padded parameter rows: per-element staging', 12, 3, 4, False, 3, 1)]
 # rqs: K = 16 is the register path (and the LDS-DMA pipeline on whole dense spans), 17 needs the raised LDS limit (> 48 KiB per
 # workgroup), 32 runs one wave per workgroup (> 64 KiB); cubic: the same thresholds sit at K = 16 (pair loads + DMA), 24 (> 48 KiB:
-# 4 x 64 x 51 x 4 B) and 32 (> 64 KiB); every K takes the 16-byte staging of an aligned packed span (2K + 2 is even: sx_rqs.hip:577)
+# 4 x 64 x 51 x 4 B) and 32 (> 64 KiB); every K takes the 16-byte staging of an aligned packed span (2K + 2 is even: cubic_kernel's staging)
 SPLINE_K = {False: (1, 5, 16, 17, 32), True: (1, 5, 16, 24, 32)}
 
 
@@ -355,7 +355,7 @@ def test_spline_coupling_dispatch(cubic, form, K):
 # ------------------------------------------------------------------------------------------------------------------------------
 SLOPE = 0.2
 PW = {1: 'sigmoid', 2: 'logit', 3: 'elu', 4: 'elu_inv', 5: 'leaky_relu', 6: 'leaky_relu_inv'}
-# dim -> (vec4 kernel?, ldj_mode with an ldj buffer): sx_pointwise.hip:405-410 (lanes per row = dim / 4 or dim; power of two <= 64 ? 1 : 2)
+# dim -> (vec4 kernel?, ldj_mode with an ldj buffer): sx_pointwise's `vec4` and sx_ldj_mode (lanes per row = dim / 4 or dim; power of two <= 64 ? 1 : 2)
 PW_DIMS = {8: (True, 1), 12: (True, 2), 260: (True, 2), 2: (False, 1), 7: (False, 2), 65: (False, 2)}
 
 
@@ -416,7 +416,7 @@ def test_pointwise_dispatch(kind, d):
                         C.store((bf, 'ldiag'), ldiag, l32, l64, what + ' ldiag')
 
 
-# (kernel, storage, dim): sx_pointwise.hip:355 (fp32, dim % 4 == 0, aligned -> 16-byte kernels; :365 dim <= 64 -> the pipelined one)
+# (kernel, storage, dim): sx_pointwise's cumsum / diff branch (fp32, dim % 4 == 0, aligned -> 16-byte kernels; dim <= 64 -> the pipelined one)
 CUMSUM = [('cumsum_vec_pipe_kernel', False, 8), ('cumsum_vec_pipe_kernel', False, 64), ('cumsum_vec_kernel', False, 68),
           ('cumsum_kernel', False, 7), ('cumsum_kernel', True, 8), ('cumsum_kernel', True, 7)]
 
@@ -450,7 +450,7 @@ def test_cumsum_diff_dispatch(kernel, bf, d, diff):
 # ------------------------------------------------------------------------------------------------------------------------------
 # sx_unit_normal_logprob
 # ------------------------------------------------------------------------------------------------------------------------------
-# (dim, bf16) -> kernel: sx_elementwise.hip:567-568 (bf16x8: dim / 8 a power of two <= 64; vec4: dim / 4 a power of two <= 64)
+# (dim, bf16) -> kernel: sx_unit_normal_logprob (bf16x8: dim / 8 a power of two <= 64; vec4: dim / 4 a power of two <= 64)
 NORMAL = {(1, False): 'generic', (4, False): 'vec4', (8, False): 'vec4', (12, False): 'generic', (256, False): 'vec4',
           (260, False): 'generic', (512, False): 'generic',
           (1, True): 'generic', (4, True): 'vec4', (8, True): 'bf16x8', (12, True): 'generic', (256, True): 'bf16x8',
@@ -493,7 +493,7 @@ def test_unit_normal_dispatch(d, bf):
 # ------------------------------------------------------------------------------------------------------------------------------
 # sx_permute
 # ------------------------------------------------------------------------------------------------------------------------------
-# row bytes -> kernel: sx_elementwise.hip:471 (rows of a multiple of 16 bytes that divide 4096 go through LDS)
+# row bytes -> kernel: sx_permute (rows of a multiple of 16 bytes that divide 4096 go through LDS)
 PERMUTE = {16: 'lds', 4096: 'lds', 48: 'plain', 4112: 'plain'}
 
 
@@ -686,14 +686,14 @@ def test_special_values_through_unit_normal(bf):
 # offset views: base pointers that are element-aligned only
 #
 # What each launcher does with such a pointer, read from the code before any of this ran:
-#   sx_affine_coupling       x, y, params tested at sx_elementwise.hip:208-209 -> generic kernel (element accesses); ldj: elements
+#   sx_affine_coupling       x, y, params tested in its `fast` condition -> generic kernel (element accesses); ldj: elements
 #   sx_time_affine_coupling  element accesses only
 #   sx_rqs / sx_cubic        x, y, ldiag, ldj: element accesses; params: 16-byte staging / LDS-DMA only behind
-#                            (params & 15) == 0 (sx_rqs.hip:204, :547, :577), else per-element staging
-#   sx_pointwise             x, y tested against 4 elements and ldiag against 16 bytes at sx_pointwise.hip:405-406 -> scalar kernel;
-#                            cumsum / diff: x | y tested at :355 -> cumsum_kernel
-#   sx_unit_normal_logprob   x tested at sx_elementwise.hip:567-568 -> generic kernel; ldj, out: elements
-#   sx_permute               x | y tested at sx_elementwise.hip:472 -> plain kernel
+#                            (params & 15) == 0 (rqs_kernel's `contig`, cubic_kernel's `lin` and vector staging), else per-element staging
+#   sx_pointwise             x, y tested against 4 elements and ldiag against 16 bytes in its `vec4` condition -> scalar kernel;
+#                            cumsum / diff: x | y tested before the 16-byte kernels -> cumsum_kernel
+#   sx_unit_normal_logprob   x tested by both vector branches -> generic kernel; ldj, out: elements
+#   sx_permute               x | y tested by the LDS branch -> plain kernel
 #   sx_flow_run2             identity_cols programs load x / store y as 16-byte (fp32) or 8-byte (bf16) vectors; x is REJECTED
 #                            unless 16-byte aligned (sx_flow_fused.hip:314) -- the binding copies (fused.needs_aligned_copy); y is the
 #                            binding's own allocation; latent and the gathered-columns form: element accesses
