@@ -855,6 +855,49 @@ size_t sx_cnf_set_lds_bytes(const sx_cnf_set_net *net_host, int32_t want_ldj);
 int sx_cnf_set_flow(const sx_cnf_set_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                     int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- continuous normalizing flow over sets with self attention (ContinuousTransform with set_data=True or divergence='compute_set'
+ * over DiffeqSelfAttention: stribor/net/diffeq.py:97-113 around net/attention.py's SelfAttention) ----
+ * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  With u_i = [t, x_i, latent_i]:
+ * q_i, k_i, v_i = the query / key / value embedding of u_i (one Linear, or Linear - act - Linear; `embed` = E outputs), n_heads heads of
+ * width dh = E / n_heads, scale = (1 / dh) ** 0.5; per head s_ij = scale q_i . k_j over the set of row i (mask_diagonal: s_ii = -inf),
+ * p_i = softmax_j(s_ij) (a fully masked row: zeros), o_i = sum_j p_ij v_j; f_i = P o_i + pb.  The log-det is the integral of the
+ * divergence of the whole set's dynamics, kept per element (tr_i = sum_d d f_i[d] / d x_i[d]), from a forward tangent per coordinate:
+ * no constant is derived by the caller, every pointer is a parameter of the module.  A set with a k or v value that is not finite
+ * comes back as NaN in every element; no other set sees it.  The same solvers, grid and roundings as sx_cnf_flow; exact fp32
+ * (v_mfma_f32_32x32x2_f32). */
+#define SX_CNF_ATTN_MAX_DIM    8
+#define SX_CNF_ATTN_MAX_IN     33        /* 1 + dim + latent_dim: x and latent share one 32-feature tile                 */
+#define SX_CNF_ATTN_MAX_HIDDEN 64
+#define SX_CNF_ATTN_MAX_EMBED  32
+#define SX_CNF_ATTN_MAX_SIZE   128
+typedef struct {
+    const float *W1[3];     /* the first Linear of the query, key, value embedding (in this order): [hidden[0] or embed, 1 + dim +
+                               latent_dim] row-major                                                                     */
+    const float *b1[3];     /* its bias                                                                                 */
+    const float *W2[3];     /* n_hidden == 1: the second Linear, [embed, hidden[0]] row-major; else unused               */
+    const float *b2[3];     /* its bias                                                                                 */
+    const float *P;         /* proj.weight, [dim, embed] row-major                                                      */
+    const float *pb;        /* proj.bias, [dim]                                                                         */
+    int32_t dim;            /* 1..SX_CNF_ATTN_MAX_DIM                                                                   */
+    int32_t latent_dim;     /* 1 + dim + latent_dim <= SX_CNF_ATTN_MAX_IN                                               */
+    int32_t act;            /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU, the same in the three embeddings                    */
+    int32_t set_size;       /* 1..SX_CNF_ATTN_MAX_SIZE                                                                  */
+    int32_t n_hidden;       /* hidden layers of an embedding: 0 (one Linear) or 1                                       */
+    int32_t hidden[2];      /* hidden[0]: 1..SX_CNF_ATTN_MAX_HIDDEN when n_hidden == 1; hidden[1] unused                */
+    int32_t embed;          /* 1..SX_CNF_ATTN_MAX_EMBED                                                                 */
+    int32_t n_heads;        /* 1, 2 or 4, dividing embed                                                                */
+    int32_t mask_diagonal;  /* 0 / 1                                                                                    */
+} sx_cnf_attn_net;
+
+/* Bytes of LDS of a launch for this network: the weight images, the vectors, two k / v exchange areas and the set flags; 0 for a
+ * network outside the coverage above or beyond SX_CNF_LDS_BYTES.  Reads the integer fields only. */
+size_t sx_cnf_attn_lds_bytes(const sx_cnf_attn_net *net_host);
+
+/* The arguments of sx_cnf_set_flow; n_rows must be a multiple of set_size.  A workgroup takes floor(128 / set_size) whole sets at a
+ * time; a set's result does not depend on the other sets (bitwise, in the same slot). */
+int sx_cnf_attn_flow(const sx_cnf_attn_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                     int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
+
 /* ---- multi-head attention core (stribor/net/attention.py:8-49 with util/safe_softmax.py:3-14) ---------------------------------
  * q [R, Nq, E], k / v [R, Nk, E]: element (r, n, e) at base + r * bs + n * rs + e (unit column stride; bs = 0 broadcasts one
  * [N, E] block over R).  n_heads heads of width dh = E / n_heads (1..SX_ATTENTION_MAX_HEAD_DIM), scale (1 / dh) ** 0.5

@@ -61,7 +61,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
            'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
-           'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow']
+           'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
@@ -74,6 +74,8 @@ CNF_LDS_BYTES = 160 * 1024
 CNF_SOLVERS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
 # ... over sets (sx_cnf_set_flow)
 CNF_SET_MAX_DIM, CNF_SET_MAX_IN, CNF_SET_MAX_HIDDEN, CNF_SET_MAX_SIZE = 32, 64, 64, 128
+# ... over sets with self attention (sx_cnf_attn_flow)
+CNF_ATTN_MAX_DIM, CNF_ATTN_MAX_IN, CNF_ATTN_MAX_HIDDEN, CNF_ATTN_MAX_EMBED, CNF_ATTN_MAX_SIZE = 8, 33, 64, 32, 128
 
 # multi-head attention core (include/stribor_hip.h: sx_attention_fwd / sx_attention_bwd)
 ATTENTION_MAX_HEAD_DIM = 128
@@ -130,6 +132,13 @@ class sx_cnf_set_net(C.Structure):
     _fields_ = [('A', C.c_void_p * 3), ('G', C.c_void_p * 3), ('bias', C.c_void_p * 3), ('w0', C.c_void_p), ('trace', C.c_void_p),
                 ('n_layers', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32), ('set_size', C.c_int32),
                 ('out_dim', C.c_int32 * 3)]
+
+
+class sx_cnf_attn_net(C.Structure):
+    _fields_ = [('W1', C.c_void_p * 3), ('b1', C.c_void_p * 3), ('W2', C.c_void_p * 3), ('b2', C.c_void_p * 3), ('P', C.c_void_p),
+                ('pb', C.c_void_p), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32), ('set_size', C.c_int32),
+                ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 2), ('embed', C.c_int32), ('n_heads', C.c_int32),
+                ('mask_diagonal', C.c_int32)]
 
 
 class sx_cnf_exact_net(C.Structure):
@@ -284,6 +293,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_set_lds_bytes.argtypes = [C.POINTER(sx_cnf_set_net), i32]
     lib.sx_cnf_set_flow.restype = i32
     lib.sx_cnf_set_flow.argtypes = [C.POINTER(sx_cnf_set_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_attn_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_attn_lds_bytes.argtypes = [C.POINTER(sx_cnf_attn_net)]
+    lib.sx_cnf_attn_flow.restype = i32
+    lib.sx_cnf_attn_flow.argtypes = [C.POINTER(sx_cnf_attn_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

@@ -1,4 +1,4 @@
-// What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip) have in common:
+// What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip, sx_cnf_attn.hip) have in common:
 //   * the layout: a workgroup of 4 waves, one wave = 32 rows on the MFMA column (lane & 31), features on the C rows, a 32-feature tile
 //     of a row = one f32x16 C fragment = the B operand of the next GEMM; feature kmap(r, h) sits in register r of lane half h;
 //   * the seven activations whose derivative is a function of the activation's OUTPUT;
@@ -7,7 +7,7 @@
 //     -ffp-contract=off: the tableau's parenthesisation is the reference solver's sequence of roundings;
 //   * the launcher and the per-call argument checks.
 // sx_cnf.hip uses all of it but cnf_act_all (its own sweep keeps its widest kernel free of spills) and cnf_latent_packed.
-// Everything here has internal linkage: four translation units include it.
+// Everything here has internal linkage: five translation units include it.
 #pragma once
 #include "sx_common.h"
 

@@ -23,6 +23,12 @@ into the kernel's LDS image once (cached, guarded on weights and masks) and the 
 value.  Over a ``net.DiffeqExactTraceDeepSet`` on sets (..., N, dim) (N <= 128, the same widths, sum / mean / max pooling) it is ONE
 launch of ``sx_cnf_exact_set_flow``: the same image scheme plus one ordered exchange through LDS per evaluation for the exclusive
 pooling.  Any other net under 'exact' runs the composition path over ``net.FuncAndDiagJac``.
+
+Sets under ``set_data=True`` / ``divergence='compute_set'`` (or ``'none'``) over a ``net.DiffeqSelfAttention`` (embeddings of one or two
+Linear layers, hidden <= 64, embedding <= 32, 1, 2 or 4 heads, N <= 128, dim <= 8, dim + latent <= 32) are ONE launch of
+``sx_cnf_attn_flow``: keys and values meet in LDS once per evaluation, and the per-element divergence comes from a forward tangent per
+coordinate (``net.self_attention_closed_form`` states it in torch) -- 1 + dim attentions per evaluation where
+``divergence_exact_for_sets`` makes N * dim reverse passes (DESIGN.md "CNF on sets with attention").
 """
 import ctypes
 from typing import Dict, Optional
@@ -35,7 +41,8 @@ from .. import _hip
 from ..flow import Transform, flatten_rows, graph_wanted
 from ..fused import ProgramCache
 from ..net import diffeq_exact_trace as exact_trace
-from ..net.diffeq import DiffeqDeepset, DiffeqMLP
+from ..net.attention import SelfAttention
+from ..net.diffeq import DiffeqDeepset, DiffeqMLP, DiffeqSelfAttention
 from ..net.diffeq_zero_trace import DiffeqZeroTraceDeepSet
 from ..net.equivariant import EquivariantLayer, EquivariantNet
 from ..net.mlp import MLP
@@ -366,6 +373,54 @@ class ContinuousTransform(Transform):
                 return image, offsets
         return self._trace.get(('set', set_size, str(device)), build, guards=guards)
 
+    def _attn_kernel_net(self, set_size: int, latent_dim: int, device):
+        """(sx_cnf_attn_net, keep-alive list) for sx_cnf_attn_flow over sets of `set_size` elements, or None outside its coverage.  The
+        kernel reads the module's own parameters: there is no derived constant to cache."""
+        diffeq = self.odefunc.diffeq
+        if type(diffeq) is not DiffeqSelfAttention or type(diffeq.net) is not SelfAttention:
+            return None
+        net = diffeq.net
+        embeds = (net.query, net.key, net.value)
+        if any(type(m) is not MLP or m._wrapped or m.final_activation_name is not None for m in embeds):
+            return None
+        act = embeds[0].activation_name
+        lins = []
+        for m in embeds:
+            layers = list(m.net)
+            if len(layers) not in (1, 3) or any(type(l) is not type(layers[0]) for l in layers[0::2]) or not isinstance(layers[0], nn.Linear):
+                return None
+            if len(layers) == 3:
+                # the in-kernel activations and derivatives are those of torch's DEFAULT parameters, the same in the three embeddings
+                a = layers[1]
+                if m.activation_name != act or type(a) is not getattr(nn, act, None) or _hip.ACT_CODES.get(act, 99) > 6 \
+                        or _ACT_DEFAULTS.get(type(a), lambda m: True)(a) is not True:
+                    return None
+            lins.append(layers[0::2])
+        n_hidden = len(lins[0]) - 1
+        proj = net.proj
+        if any(len(l) != n_hidden + 1 for l in lins) or not isinstance(proj, nn.Linear):
+            return None
+        E, in_dim = lins[0][-1].out_features, 1 + self.dim + latent_dim
+        H1 = lins[0][0].out_features
+        if any(l[0].in_features != in_dim or l[0].out_features != H1 or l[-1].out_features != E or l[-1].in_features != (H1 if n_hidden else in_dim)
+               for l in lins) or proj.in_features != E or proj.out_features != self.dim:
+            return None
+        tensors = [t for l in lins for lin in l for t in (lin.weight, lin.bias)] + [proj.weight, proj.bias]
+        if any(t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device for t in tensors):
+            return None
+        d = _hip.sx_cnf_attn_net()
+        for i, l in enumerate(lins):
+            d.W1[i], d.b1[i] = l[0].weight.data_ptr(), l[0].bias.data_ptr()
+            if n_hidden:
+                d.W2[i], d.b2[i] = l[1].weight.data_ptr(), l[1].bias.data_ptr()
+        d.P, d.pb = proj.weight.data_ptr(), proj.bias.data_ptr()
+        d.dim, d.latent_dim, d.act, d.set_size = self.dim, latent_dim, (_hip.ACT_CODES[act] if n_hidden else 0), set_size
+        d.n_hidden, d.embed, d.n_heads, d.mask_diagonal = n_hidden, E, int(net.n_heads), int(bool(net.mask_diagonal))
+        d.hidden[0] = H1 if n_hidden else 0
+        if _hip.lib().sx_cnf_attn_lds_bytes(d) == 0:
+            return None
+        return d, [t.detach() for t in tensors]
+
     def _exact_kernel_net(self, latent_dim: int, device):
         """(sx_cnf_exact_net, keep-alive list) for sx_cnf_exact_flow, or None when the ODE function is outside its coverage."""
         s = exact_trace.kernel_coverage(self.odefunc.diffeq, self.dim, latent_dim)
@@ -481,6 +536,9 @@ class ContinuousTransform(Transform):
         if plan is None and not graph and mask is None and x.dim() >= 2 and (func.divergence == 'none' or func.exact_set_trace()):
             trace, entry = want_ldj and func.divergence != 'none', 'sx_cnf_set_flow'
             plan = self._set_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
+            if plan is None:
+                entry = 'sx_cnf_attn_flow'
+                plan = self._attn_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
         if plan is not None:
             x2, lead = flatten_rows(x)
             lat2 = None if latent is None else flatten_rows(latent)[0]

@@ -1,8 +1,8 @@
 from .mlp import MLP
 from .time_net import TimeFourier, TimeFourierBounded, TimeIdentity, TimeLinear, TimeLog, TimeTanh
-from .attention import Attention, InducedSelfAttention, SelfAttention, attention
+from .attention import Attention, InducedSelfAttention, SelfAttention, attention, self_attention_closed_form
 from .equivariant import EquivariantLayer, EquivariantNet
-from .diffeq import DiffeqConcat, DiffeqDeepset, DiffeqMLP, DiffeqNet
+from .diffeq import DiffeqConcat, DiffeqDeepset, DiffeqMLP, DiffeqNet, DiffeqSelfAttention
 from .made import MADE
 from .diffeq_zero_trace import DiffeqZeroTraceDeepSet, DiffeqZeroTraceMLP
 from .diagjac import FuncAndDiagJac

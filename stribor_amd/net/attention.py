@@ -24,7 +24,7 @@ from ..fused import StructureTracked
 from ..util.safe_softmax import safe_softmax
 from .mlp import MLP, _Linear, batch_linear
 
-__all__ = ['attention', 'Attention', 'SelfAttention', 'InducedSelfAttention']
+__all__ = ['attention', 'Attention', 'SelfAttention', 'InducedSelfAttention', 'self_attention_closed_form']
 
 
 def _core_args(q, k, v, mask2, n_heads: int, mask_diagonal: bool, out_mask: bool):
@@ -212,6 +212,13 @@ class Attention(StructureTracked, nn.Module):
         q, k, v = self._embed_all(query, key, value)
         return self._project(attention(q, k, v, self.n_heads, self.mask_diagonal, mask))
 
+    def forward_twice_differentiable(self, query, key, value, mask=None, **kwargs):
+        """The layer through plain torch ops (library GEMMs): differentiable to any order, where `forward`'s attention core and
+        `batch_linear` are differentiable once.  For callers that differentiate a derivative (a CNF's divergence in training)."""
+        q, k, v = (m.forward_twice_differentiable(t) for m, t in ((self.query, query), (self.key, key), (self.value, value)))
+        y = _attention_composed(q, k, v, self.n_heads, self.mask_diagonal, None if mask is None else mask.to(q.dtype))
+        return F.linear(y, self.proj.weight, self.proj.bias)
+
 
 class SelfAttention(Attention):
     """Attention of a set with itself (attention.py:101-122): forward(x, mask)."""
@@ -221,6 +228,9 @@ class SelfAttention(Attention):
 
     def forward(self, x, mask=None, **kwargs):
         return super().forward(x, x, x, mask=mask)
+
+    def forward_twice_differentiable(self, x, mask=None, **kwargs):
+        return super().forward_twice_differentiable(x, x, x, mask=mask)
 
 
 class InducedSelfAttention(StructureTracked, nn.Module):
@@ -237,3 +247,90 @@ class InducedSelfAttention(StructureTracked, nn.Module):
         h = self.points.expand(*x.shape[:-2], *self.points.shape)
         h = self.att1(h, x, x, mask=mask, **kwargs)
         return self.att2(x * (1 if mask is None else mask), h, h, **kwargs)
+
+
+def _act_prime(layer: nn.Module, z: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """act'(z) of an elementwise activation `layer` with a = layer(z): closed forms for the activations the CNF kernels know (torch's
+    default parameters are read off the layer), one elementwise reverse pass for any other."""
+    kind = type(layer)
+    if kind is nn.Identity:
+        return torch.ones_like(z)
+    if kind is nn.Tanh:
+        return 1 - a * a
+    if kind is nn.ReLU:
+        return (z > 0).to(z.dtype)
+    if kind is nn.Sigmoid:
+        return a * (1 - a)
+    if kind is nn.ELU:
+        return torch.where(z > 0, torch.ones_like(z), a + layer.alpha)
+    if kind is nn.Softplus:
+        return torch.where(z * layer.beta > layer.threshold, torch.ones_like(z), torch.sigmoid(z * layer.beta))
+    if kind is nn.LeakyReLU:
+        return torch.where(z > 0, torch.ones_like(z), torch.full_like(z, layer.negative_slope))
+    with torch.enable_grad():
+        zz = z.detach().requires_grad_(True)
+        return torch.autograd.grad(layer(zz).sum(), zz)[0]
+
+
+def self_attention_closed_form(net, t, x, latent=None, want_div: bool = True, dtype=None):
+    """f = net(t, x, latent) of a ``DiffeqSelfAttention`` (or its ``SelfAttention`` over the columns [t, x, latent]) on sets (..., N,
+    dim), and -- `want_div` -- div[..., i, d] = d f_i[d] / d x_i[d] WITHOUT autograd: what ``divergence_exact_for_sets`` gives with N *
+    dim reverse passes, and what ``sx_cnf_attn_flow`` integrates (DESIGN.md "CNF on sets with attention").  Per coordinate d a forward
+    tangent of x_i[d] runs through element i's own embeddings (qd, kd, vd); per head, with s = scale q k^T, p = safe_softmax(s):
+        sd_ij = scale qd_i . k_j + [i == j] scale q_i . kd_i            (the second term is absent under mask_diagonal: p_ii = 0)
+        od_i  = sum_j p_ij (sd_ij - sum_m p_im sd_im) v_j + p_ii vd_i
+        div[i, d] = proj.weight[d, head columns] . od_i, summed over the heads.
+    Plain torch on any device in `dtype` (default: x's).  -> (dy, div | None)."""
+    att = net.net if isinstance(getattr(net, 'net', None), Attention) else net
+    dtype = dtype or x.dtype
+    x = x.to(dtype)
+    D, H = x.shape[-1], att.n_heads
+    cols = [torch.ones_like(x[..., :1]) * torch.as_tensor(t).reshape(-1)[0].to(x), x]
+    if latent is not None:
+        cols.append(latent.to(device=x.device, dtype=dtype).expand(*x.shape[:-1], latent.shape[-1]))
+    u = torch.cat(cols, -1)
+
+    def embed(mlp):
+        h, hd = u, None                                       # hd [..., N, D, width]: the tangent of x_i[d] through element i
+        for layer in mlp.net:
+            if isinstance(layer, nn.Linear):
+                W = layer.weight.detach().to(dtype)
+                b = None if layer.bias is None else layer.bias.detach().to(dtype)
+                if want_div:
+                    hd = W[:, 1:1 + D].t() if hd is None else hd @ W.t()
+                h = F.linear(h, W, b)
+            else:
+                a = layer(h)
+                if want_div:
+                    hd = hd * _act_prime(layer, h, a).unsqueeze(-2)
+                h = a
+        return h, hd
+    (q, qd), (k, kd), (v, vd) = embed(att.query), embed(att.key), embed(att.value)
+    E = q.shape[-1]
+    dh = E // H
+    N = x.shape[-2]
+    scale = (1 / dh) ** 0.5
+    heads = lambda z: z.reshape(*z.shape[:-1], H, dh)
+    qh, kh, vh = heads(q), heads(k), heads(v)
+    s = torch.einsum('...ihe,...jhe->...hij', qh, kh) * scale
+    eye = torch.eye(N, dtype=torch.bool, device=x.device)
+    if att.mask_diagonal:
+        s = s.masked_fill(eye, -float('inf'))
+    p = safe_softmax(s, -1)
+    P = att.proj.weight.detach().to(dtype)
+    o = torch.einsum('...hij,...jhe->...ihe', p, vh)
+    dy = F.linear(o.reshape(*x.shape[:-1], E), P, None if att.proj.bias is None else att.proj.bias.detach().to(dtype))
+    if not want_div:
+        return dy, None
+    expand = lambda z: heads(z.expand(*x.shape[:-1], D, E))                          # [..., N, D, H, dh]
+    qdh, kdh, vdh = expand(qd), expand(kd), expand(vd)
+    sd = torch.einsum('...idhe,...jhe->...hidj', qdh, kh) * scale
+    if not att.mask_diagonal:
+        own = torch.einsum('...ihe,...idhe->...hid', qh, kdh) * scale
+        sd = sd + own.unsqueeze(-1) * eye.to(dtype).unsqueeze(-2)                     # [..., H, N, D, N]: only at j == i
+    pe = p.unsqueeze(-2)                                                             # [..., H, N, 1, N]
+    w = pe * (sd - (pe * sd).sum(-1, keepdim=True))
+    pii = torch.diagonal(p, dim1=-2, dim2=-1)                                        # [..., H, N]
+    od = torch.einsum('...hidj,...jhe->...idhe', w, vh) + pii.transpose(-1, -2)[..., None, :, None] * vdh
+    div = torch.einsum('...ide,de->...id', od.reshape(*x.shape[:-1], D, E), P)
+    return dy, div

@@ -21,7 +21,15 @@ The exact-set line: divergence='exact' over DiffeqExactTraceDeepSet(2, [64, 64],
 evaluation: the MADE and the set embedding 2 (D H1 + H1 H2 + H2 d_h D) + 2 (D H1 + H1 H2 + H2 d_h), and per dimension the dimwise net
 as in the exact-trace line (padding and the exchange are not counted).
 
-    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json]
+The attention line: set_data=True / 'compute_set' over DiffeqSelfAttention(3, [64, 32], 2, n_heads=4) on sx_cnf_attn_flow, the set
+line's (B, N, dim) and grid, against its composition path (divergence_exact_for_sets through the twice-differentiable attention) timed at
+--set-fallback-sets sets and scaled.  FLOPs per element and evaluation: the three embeddings 3 x 2 (dim H1 + H1 E), scores and P.V
+2 x 2 N E, the projection 2 E dim, and per coordinate the tangent embeddings 3 x 2 H1 E plus one more score and P.V product 2 x 2 N E
+(the recomputed scores, padding and the exchange are not counted).  This line times at least 50 calls (a window over a second), and its
+TF / fraction of peak are algorithmic work over CALL time (device events around whole calls: the launch, the output allocation and the
+kernel), not over kernel time.  --attention-only prints this line alone.
+
+    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only]
 """
 import argparse
 import json
@@ -49,6 +57,35 @@ def timed(fn, reps, warm=2):
     return e0.elapsed_time(e1) / reps
 
 
+def attention_line(a, results):
+    torch.manual_seed(0)
+    B, N, D, hidden, heads = a.sets, 32, 2, [64, 32], 4
+    f = st.ContinuousTransform(D, net=st.net.DiffeqSelfAttention(D + 1, hidden, D, n_heads=heads), divergence='compute_set', solver='rk4',
+                               solver_options={'step_size': 1.0 / a.steps}, set_data=True).eval().to('cuda')
+    y = torch.randn(B, N, D, device='cuda')
+    ys = y[:a.set_fallback_sets]
+    H1, E = hidden
+    flop_eval = 6 * (D * H1 + H1 * E) + 4 * N * E + 2 * E * D + D * (6 * H1 * E + 4 * N * E)
+    reps = max(a.reps, 50)                 # (a call takes tens of ms: at least 50 of them, so that the timed window is over a second)
+    with torch.no_grad():
+        ms = timed(lambda: f.inverse_and_log_det_jacobian(y), reps)
+        assert f._last_path == 'kernel'
+        ms_x = timed(lambda: f.inverse(y), reps)
+        fb = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=0) * (B / ys.shape[0])
+        xk, lk = f.inverse_and_log_det_jacobian(ys)
+        xc, lc = f._composed_reference(ys, reverse=True)
+    fl = B * N * 4 * a.steps * flop_eval
+    r = results[f'attention_b{B}_n{N}_dim{D}_h{"x".join(map(str, hidden))}_heads{heads}'] = {
+        'solve_ldj_ms': ms, 'solve_only_ms': ms_x, 'composed_ms_scaled': fb, 'rows_per_s': B * N / ms * 1e3, 'tflops': fl / ms / 1e9,
+        'frac_of_peak': fl / (ms * 1e-3) / PEAK_F32_MFMA, 'composed_over_kernel': fb / ms, 'reps': reps,
+        'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item()}
+    print(f'attention sets (B, N, dim) = ({B}, {N}, {D}) {hidden} heads {heads} rk4 x {a.steps}: solve + log-det {ms:.2f} ms '
+          f'per call over {reps} calls ({r["rows_per_s"]:.3g} elements/s, {r["tflops"]:.1f} TF of algorithmic work per call time = '
+          f'{r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path {fb:.0f} ms (timed at '
+          f'{ys.shape[0]} sets, scaled) = {r["composed_over_kernel"]:.0f} x; kernel vs composition max abs x {r["max_abs_x"]:.2e} ldj '
+          f'{r["max_abs_ldj"]:.2e}')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=1 << 18)
@@ -58,9 +95,21 @@ def main():
     ap.add_argument('--steps', type=int, default=16)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--json', default=None)
+    ap.add_argument('--attention-only', action='store_true', help='print the attention line alone')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_cnf needs a GPU'
     results = {}
+    if not a.attention_only:
+        earlier_lines(a, results)
+    attention_line(a, results)
+    results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows, 'sets': a.sets,
+                         'set_fallback_sets': a.set_fallback_sets}
+    if a.json:
+        with open(a.json, 'w') as fh:
+            json.dump(results, fh, indent=1)
+
+
+def earlier_lines(a, results):
     for dim, hidden in ((2, [64]), (32, [128, 128])):
         torch.manual_seed(0)
         f = st.ContinuousTransform(dim, net=st.net.DiffeqMLP(dim + 1, hidden, dim), divergence='compute', solver='rk4',
@@ -159,10 +208,6 @@ def main():
           f'({r["rows_per_s"]:.3g} elements/s, {r["tflops"]:.1f} TF = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone '
           f'{ms_x:.2f} ms; composition path {fb:.0f} ms (timed at {ys.shape[0]} sets, scaled) = {r["composed_over_kernel"]:.1f} x; kernel '
           f'vs composition max abs x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
-    results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows}
-    if a.json:
-        with open(a.json, 'w') as fh:
-            json.dump(results, fh, indent=1)
 
 
 if __name__ == '__main__':
