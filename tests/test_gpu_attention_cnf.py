@@ -166,7 +166,8 @@ def test_set_independence_is_bitwise_and_position_is_within_the_bound():
     _check('slot 1 y', y3[1], y32, y64)
     _check('slot 1 ldj', l3[1], l32, l64)
     big = torch.cat([x2, x2, x2[:1], x[4:5], x2[:3]]), torch.cat([lat2, lat2, lat2[:1], lat[4:5], lat2[:3]])      # 25 sets fill a pass:
-    y4, l4 = _kernel(f, *big)                                              # ... and to the front of a second workgroup's pass
+    y4, l4 = _kernel(f, *big)                                              # ... and to the front of pass 1: a second workgroup's FIRST
+    # trip (the grid is 2 here; a workgroup's second and later trips round the pass loop: test_gpu_cnf_passes.py)
     _check('second pass y', y4[25], y32, y64)
     _check('second pass ldj', l4[25], l32, l64)
 
