@@ -721,6 +721,42 @@ size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj);
 int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                 int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- training the dense CNF: the Hutchinson forward and its discrete adjoint (ContinuousTransform with divergence='approximate' in
+ * training mode, cnf.py:76-97) ----
+ * The network is an sx_cnf_net -- its `trace` is not read -- within: dim <= SX_CNF_TRAIN_MAX_DIM, 1 + dim + latent_dim <= SX_CNF_TRAIN_MAX_IN,
+ * one or two hidden layers of <= SX_CNF_TRAIN_MAX_HIDDEN units, the activations of sx_cnf_flow.  e: fp32 [n_rows, dim], the noise row
+ * of the estimate q = e^T (df/dx) e that replaces the exact trace; it is constant along a row's solve.  Grid, solvers and roundings are
+ * sx_cnf_flow's: for the same network, rows and grid, y is bit-identical to sx_cnf_flow's. */
+#define SX_CNF_TRAIN_MAX_DIM    32
+#define SX_CNF_TRAIN_MAX_IN     64
+#define SX_CNF_TRAIN_MAX_HIDDEN 32        /* one tile: the adjoint of a two-tile hidden layer does not fit the register file */
+typedef struct {
+    float *dW[3];          /* per Linear layer: [out_dim, in_dim] row-major, or NULL (not wanted); written, not accumulated       */
+    float *db[3];          /* [out_dim] or NULL                                                                                   */
+} sx_cnf_train_grads;
+
+/* Bytes of LDS the forward (backward == 0) or the backward launch stages for this network; 0 outside the coverage above.  Reads the
+ * integer fields and tests the weight pointers for NULL only; never launches. */
+size_t sx_cnf_train_lds_bytes(const sx_cnf_net *net_host, int32_t backward);
+
+/* Floats of the partial buffer sx_cnf_train_bwd needs for n_rows rows (one partial per wave of at most 512 workgroups); 0 outside
+ * the coverage.  Never launches. */
+int64_t sx_cnf_train_partial_floats(const sx_cnf_net *net_host, int64_t n_rows);
+
+/* x, e, y: fp32 [n_rows, dim]; latent: fp32 [n_rows, latent_dim] or NULL; ldj: fp32 [n_rows], the integral of q over the grid;
+ * checkpoints: fp32 [n_steps, n_rows, dim], the state at the start of every step, or NULL (a call that builds no graph).  Every
+ * pointer may be 4-byte aligned. */
+int sx_cnf_train_fwd(const sx_cnf_net *net_host, const float *x, const float *latent, const float *e, float *y, float *ldj,
+                     float *checkpoints, int64_t n_rows, int32_t solver, int32_t n_steps, float t0, float t1, float step_size, void *stream);
+
+/* The discrete adjoint of sx_cnf_train_fwd on the same grid: gy [n_rows, dim] and gldj [n_rows] are the gradients of y and ldj; gx
+ * [n_rows, dim] and, unless NULL, g_latent [n_rows, latent_dim] are written, and so is every gradient `grads` names, summed over the
+ * rows: per-wave partials go to `partial` (sx_cnf_train_partial_floats floats) and a second launch adds them in a fixed order -- no
+ * floating-point atomics, so two calls on the same inputs return the same bits. */
+int sx_cnf_train_bwd(const sx_cnf_net *net_host, const float *checkpoints, const float *latent, const float *e, const float *gy,
+                     const float *gldj, float *gx, float *g_latent, float *partial, const sx_cnf_train_grads *grads, int64_t n_rows,
+                     int32_t solver, int32_t n_steps, float t0, float t1, float step_size, void *stream);
+
 /* ---- exact-trace continuous normalizing flow (ContinuousTransform with divergence='exact' over DiffeqExactTraceMLP:
  * stribor/net/diffeq_exact_trace.py:48-72, diffeq_zero_trace.py:14-56, made.py, diagjac.py) ----
  * f_i = g(t, x_i, h_i, latent) with h = MADE_1(x) + MADE_2(x) (d_h values per dimension, dh_i/dx_i = 0) and g one MLP shared by

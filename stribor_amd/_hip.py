@@ -61,7 +61,8 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
            'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
-           'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow']
+           'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow',
+           'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd']
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
@@ -72,6 +73,8 @@ RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
 CNF_MAX_DIM = 64
 CNF_LDS_BYTES = 160 * 1024
 CNF_SOLVERS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
+# ... training the dense CNF (sx_cnf_train_fwd / sx_cnf_train_bwd)
+CNF_TRAIN_MAX_DIM, CNF_TRAIN_MAX_IN, CNF_TRAIN_MAX_HIDDEN = 32, 64, 32
 # ... over sets (sx_cnf_set_flow)
 CNF_SET_MAX_DIM, CNF_SET_MAX_IN, CNF_SET_MAX_HIDDEN, CNF_SET_MAX_SIZE = 32, 64, 64, 128
 # ... over sets with self attention (sx_cnf_attn_flow)
@@ -126,6 +129,10 @@ class sx_cnf_layer(C.Structure):
 class sx_cnf_net(C.Structure):
     _fields_ = [('layer', sx_cnf_layer * 3), ('n_layers', C.c_int32), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('act', C.c_int32),
                 ('trace', C.c_void_p)]
+
+
+class sx_cnf_train_grads(C.Structure):
+    _fields_ = [('dW', C.c_void_p * 3), ('db', C.c_void_p * 3)]
 
 
 class sx_cnf_set_net(C.Structure):
@@ -281,6 +288,15 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_lds_bytes.argtypes = [C.POINTER(sx_cnf_net), i32]
     lib.sx_cnf_flow.restype = i32
     lib.sx_cnf_flow.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_train_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_train_lds_bytes.argtypes = [C.POINTER(sx_cnf_net), i32]
+    lib.sx_cnf_train_partial_floats.restype = i64
+    lib.sx_cnf_train_partial_floats.argtypes = [C.POINTER(sx_cnf_net), i64]
+    lib.sx_cnf_train_fwd.restype = i32
+    lib.sx_cnf_train_fwd.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, vp]
+    lib.sx_cnf_train_bwd.restype = i32
+    lib.sx_cnf_train_bwd.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sx_cnf_train_grads), i64, i32, i32,
+                                     f32, f32, f32, vp]
     lib.sx_cnf_exact_lds_bytes.restype = C.c_size_t
     lib.sx_cnf_exact_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_net)]
     lib.sx_cnf_exact_flow.restype = i32

@@ -8,8 +8,14 @@ raise ``NotImplementedError`` when evaluated (DESIGN.md "CNF").
 Without an autograd graph, a ``DiffeqMLP`` with one or two hidden layers is ONE launch of ``sx_cnf_flow``: the state, the stage
 vectors and the log-det accumulator stay in registers for the whole grid, the weights sit in LDS, and the exact divergence comes
 from a closed form whose weight-only constants (``trace_constants``) are derived once in fp64.  Everything else -- other nets,
-``mask``, ``set_data``, the Hutchinson estimator of training mode, and every call that has to build a graph -- runs the same grid
-and tableau as a loop of torch ops over the module (``_solve_composed``); gradients are those of the discretised steps.
+``mask``, ``set_data``, and every other call that has to build a graph -- runs the same grid and tableau as a loop of torch ops over
+the module (``_solve_composed``); gradients are those of the discretised steps.
+
+Training with the default ``divergence='approximate'`` (training mode, no mask, no sets) over a ``DiffeqMLP`` with hidden layers of
+<= 32 units, dim <= 32 and 1 + dim + latent <= 64 runs on two kernels: ``sx_cnf_train_fwd`` (the solve with Hutchinson's estimate for
+the noise drawn once per solve, plus one checkpoint per step) and ``sx_cnf_train_bwd`` (the discrete adjoint of the same grid and
+tableau, weight gradients contracted in-kernel and summed in a fixed order); ``hutchinson_closed_form`` states one evaluation and its
+adjoints in torch (DESIGN.md "CNF", training on the kernel).
 
 Sets of shape (..., N, dim): a ``net.DiffeqDeepset`` over a ``net.EquivariantNet`` (one or two hidden layers of <= 64 units, N <= 128,
 dim <= 32, 1 + dim + latent <= 64, no final activation) under ``set_data=True`` / ``divergence='compute_set'`` (or ``'none'``) is ONE
@@ -105,6 +111,137 @@ def set_trace_constants(weights, dim: int, n: int):
     A3, G3 = weights[2][0], weights[2][1] / n
     C = lambda Q, R, P: Q * (R @ P).t()
     return torch.stack([C(A2, E1 + F1, A3) + C(G2, E1, A3) + C(A2, E1, G3), C(G2, F1, A3), C(A2, F1, G3), C(G2, E1, G3), C(G2, F1, G3)])
+
+
+def _act_and_derivatives(name: str, a):
+    """(act(a), act'(a), act''(a)) with both derivatives taken from the activation's OUTPUT, as the kernels take them."""
+    one = torch.ones_like(a)
+    if name == 'Identity':
+        return a, one, torch.zeros_like(a)
+    if name == 'Tanh':
+        h = torch.tanh(a)
+        d = 1 - h * h
+        return h, d, -2 * h * d
+    if name == 'ReLU':
+        h = torch.relu(a)
+        return h, (h > 0).to(a.dtype), torch.zeros_like(a)
+    if name == 'Sigmoid':
+        h = torch.sigmoid(a)
+        d = h * (1 - h)
+        return h, d, d * (1 - 2 * h)
+    if name == 'ELU':
+        h = nn.functional.elu(a)
+        return h, torch.where(h > 0, one, h + 1), torch.where(h > 0, torch.zeros_like(a), h + 1)
+    if name == 'Softplus':
+        h = nn.functional.softplus(a)
+        d = 1 - torch.exp(-h)
+        return h, d, d * (1 - d)
+    if name == 'LeakyReLU':
+        h = nn.functional.leaky_relu(a)
+        return h, torch.where(h > 0, one, 0.01 * one), torch.zeros_like(a)
+    raise ValueError(f'no closed form for activation {name!r}')
+
+
+def hutchinson_closed_form(weights, biases, activation: str, t, z, e, latent=None, k_bar=None, q_bar=None):
+    """One evaluation of the training CNF in torch ops, as ``sx_cnf_train_fwd`` / ``sx_cnf_train_bwd`` compute it (any dtype and
+    device): f = MLP([t, z, latent]) with one or two hidden layers and no final activation, and Hutchinson's estimate q = e^T (df/dz) e
+    for a fixed noise row e, without autograd -- u1 = W1x e and v = W_last^T e are constant along a solve, d = act', s = act'':
+      one hidden layer:  q = sum d1 u1 v;      two:  w = d1 u1, r = W2 w, q = sum v d2 r.
+    -> (k, q [...]).  With the adjoints `k_bar` [..., dim] and `q_bar` [...] also a dict: 'z', 'latent' (None without latent) and 'W',
+    'b' (lists, one entry per Linear layer, summed over the rows) -- the reverse pass of the two values, i.e. what
+    ``autograd.grad(..., create_graph=True)`` followed by a second differentiation gives."""
+    D = z.shape[-1]
+    W1 = weights[0]
+    W1x, W1l, Wl = W1[:, 1:1 + D], W1[:, 1 + D:], weights[-1]
+    zero = lambda W: torch.zeros(W.shape[0], dtype=z.dtype, device=z.device)
+    bs = [zero(W) if b is None else b for W, b in zip(weights, biases)]
+    u1, v = e @ W1x.t(), e @ Wl
+    a1 = z @ W1x.t() + bs[0] + t * W1[:, 0]
+    if latent is not None:
+        a1 = a1 + latent @ W1l.t()
+    h1, d1, s1 = _act_and_derivatives(activation, a1)
+    if len(weights) == 2:
+        k = h1 @ Wl.t() + bs[1]
+        q = (d1 * u1 * v).sum(-1)
+    else:
+        W2 = weights[1]
+        h2, d2, s2 = _act_and_derivatives(activation, h1 @ W2.t() + bs[1])
+        k = h2 @ Wl.t() + bs[2]
+        w = d1 * u1
+        r = w @ W2.t()
+        q = (v * d2 * r).sum(-1)
+    if k_bar is None:
+        return k, q
+    qb = q_bar.unsqueeze(-1)
+    rows = lambda m: m.reshape(-1, m.shape[-1])
+    outer = lambda a, b: rows(a).t() @ rows(b)
+    if len(weights) == 2:
+        a1b = (k_bar @ Wl) * d1 + qb * s1 * u1 * v
+        u1b, vb = qb * d1 * v, qb * d1 * u1
+        gW = [None, outer(k_bar, h1) + outer(e, vb)]
+        gb = [None, rows(k_bar).sum(0)]
+    else:
+        rb = qb * v * d2
+        a2b = (k_bar @ Wl) * d2 + qb * s2 * v * r
+        vb = qb * d2 * r
+        wb = rb @ W2
+        a1b = (a2b @ W2) * d1 + wb * s1 * u1
+        u1b = wb * d1
+        gW = [None, outer(a2b, h1) + outer(rb, w), outer(k_bar, h2) + outer(e, vb)]
+        gb = [None, rows(a2b).sum(0), rows(k_bar).sum(0)]
+    cols = [torch.full_like(z[..., :1], 1.0) * t, z] + ([] if latent is None else [latent])
+    gW[0] = outer(a1b, torch.cat(cols, -1))
+    gW[0][:, 1:1 + D] += outer(u1b, e)
+    gb[0] = rows(a1b).sum(0)
+    return k, q, {'z': a1b @ W1x, 'latent': None if latent is None else a1b @ W1l, 'W': gW, 'b': gb}
+
+
+class _CNFTrain(torch.autograd.Function):
+    """(y, ldj) = the Hutchinson solve of sx_cnf_train_fwd with checkpoints; backward: sx_cnf_train_bwd, the discrete adjoint of the
+    same grid and tableau, weight gradients contracted in-kernel.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, module, name, step, grid, x2, lat2, e2, *params):
+        n_steps = len(grid) - 1
+        ckpt = torch.empty(n_steps, *x2.shape, dtype=torch.float32, device=x2.device)
+        y, ldj = module._train_forward(x2, lat2, e2, name, step, grid, ckpt)
+        ctx.module, ctx.solve = module, (name, step, grid)
+        ctx.has_latent = lat2 is not None
+        ctx.save_for_backward(ckpt, e2, *( [lat2] if lat2 is not None else []), *[p for p in params if p is not None])
+        ctx.bias_mask = [p is not None for p in params]
+        return y, ldj
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, gldj):
+        module, (name, step, grid) = ctx.module, ctx.solve
+        saved = list(ctx.saved_tensors)
+        ckpt, e2 = saved[0], saved[1]
+        lat2 = saved[2] if ctx.has_latent else None
+        n, dim = e2.shape
+        need = ctx.needs_input_grad
+        plan = module._train_kernel_net(0 if lat2 is None else lat2.shape[-1], e2.device)
+        if plan is None:
+            raise RuntimeError('stribor_amd: the CNF changed between the forward and the backward of a training step')
+        d, keep = plan
+        gy = gy.to(torch.float32).contiguous()
+        gldj = gldj.to(torch.float32).reshape(-1).contiguous()
+        gx = torch.empty_like(gy)
+        glat = torch.empty_like(lat2) if lat2 is not None and need[5] else None
+        partial = torch.empty(max(1, _hip.lib().sx_cnf_train_partial_floats(d, n)), dtype=torch.float32, device=e2.device)
+        grads = _hip.sx_cnf_train_grads()
+        out = []
+        for i in range(d.n_layers):
+            W = keep[2 * i]
+            gW = torch.empty_like(W) if need[7 + 2 * i] else None
+            gb = torch.empty_like(keep[2 * i + 1]) if ctx.bias_mask[2 * i + 1] and need[8 + 2 * i] else None
+            grads.dW[i], grads.db[i] = _hip.ptr(gW), _hip.ptr(gb)
+            out += [gW, gb]
+        _hip.call('sx_cnf_train_bwd', e2, ctypes.byref(d), ckpt.data_ptr(), _hip.ptr(lat2), e2.data_ptr(), gy.data_ptr(), gldj.data_ptr(),
+                  gx.data_ptr(), _hip.ptr(glat), partial.data_ptr(), ctypes.byref(grads), n, _hip.CNF_SOLVERS[name], len(grid) - 1,
+                  float(grid[0]), float(grid[-1]), float(step or 0.0))
+        del keep
+        return (None, None, None, None, gx if need[4] else None, glat, None, *out)
 
 
 class ODEfunc(nn.Module):
@@ -288,6 +425,37 @@ class ContinuousTransform(Transform):
         if lds == 0 or lds > _hip.CNF_LDS_BYTES:
             return None
         return d, keep
+
+    def _train_kernel_net(self, latent_dim: int, device):
+        """(sx_cnf_net, keep-alive list [W1, b1, W2, b2, ...]) for sx_cnf_train_fwd / sx_cnf_train_bwd, or None outside their coverage
+        (DESIGN.md "CNF": dim <= 32, 1 + dim + latent <= 64, hidden layers of <= 32 units)."""
+        plan = self._kernel_net(latent_dim, False, device)
+        if plan is None or _hip.lib().sx_cnf_train_lds_bytes(plan[0], 1) == 0 or _hip.lib().sx_cnf_train_lds_bytes(plan[0], 0) == 0:
+            return None
+        return plan
+
+    def _train_forward(self, x2, lat2, e2, name, step, grid, ckpt=None):
+        """sx_cnf_train_fwd on rows -> (y, ldj [n]); `ckpt` [n_steps, n, dim] receives the state at the start of every step."""
+        d, keep = self._train_kernel_net(0 if lat2 is None else lat2.shape[-1], x2.device)
+        n = x2.shape[0]
+        y = torch.empty_like(x2)
+        ldj = torch.empty(n, dtype=torch.float32, device=x2.device)
+        if n:
+            _hip.call('sx_cnf_train_fwd', x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), e2.data_ptr(), y.data_ptr(), ldj.data_ptr(),
+                      _hip.ptr(ckpt), n, _hip.CNF_SOLVERS[name], len(grid) - 1, float(grid[0]), float(grid[-1]), float(step or 0.0))
+        del keep
+        return y, ldj
+
+    def _draw_noise(self, x):
+        """The Hutchinson noise of one solve, drawn as the composition path's first evaluation draws it (cnf.py:76-80) and left in
+        odefunc._e."""
+        func = self.odefunc
+        func.before_odeint()
+        if func.rademacher:
+            func._e = torch.randint(low=0, high=2, size=x.shape).to(x) * 2 - 1
+        else:
+            func._e = torch.randn_like(x)
+        return func._e
 
     def _trace_constants(self, weights, device):
         """c / C of `trace_constants` as the kernel reads them: fp32 on the device, C zero-padded to a square of whole tiles.
@@ -522,6 +690,23 @@ class ContinuousTransform(Transform):
         n_evals = (len(grid) - 1) * STAGES[name]
         graph = graph_wanted(self, x, latent)
         plan, entry = None, 'sx_cnf_flow'
+        if func.divergence == 'approximate' and self.training and not func.set_data and mask is None \
+                and self._train_kernel_net(0 if latent is None else latent.shape[-1], x.device) is not None:
+            # training with the Hutchinson estimator: one forward launch (with checkpoints when a graph is wanted) and one adjoint
+            e = self._draw_noise(x)
+            x2, lead = flatten_rows(x)
+            lat2 = None if latent is None else flatten_rows(latent)[0].contiguous()
+            x2, e2 = x2.contiguous(), flatten_rows(e)[0].contiguous()
+            if graph:
+                lins = [m for m in func.diffeq.net.net if isinstance(m, nn.Linear)]
+                y2, ldj = _CNFTrain.apply(self, name, step, grid, x2, lat2, e2, *[p for l in lins for p in (l.weight, l.bias)])
+            else:
+                with torch.no_grad():
+                    y2, ldj = self._train_forward(x2, lat2, e2, name, step, grid)
+            y, ldj = y2.reshape(*lead, self.dim), (ldj.reshape(*lead, 1) if want_ldj else None)
+            self._last_path = 'kernel'
+            func._num_evals.fill_(n_evals)
+            return (y.to(out_dtype) if out_dtype == torch.bfloat16 else y), ldj
         if not graph and mask is None and (func.divergence == 'none' or func.exact_trace()):
             ld = 0 if latent is None else latent.shape[-1]
             trace = want_ldj and func.divergence != 'none'

@@ -29,7 +29,13 @@ line's (B, N, dim) and grid, against its composition path (divergence_exact_for_
 TF / fraction of peak are algorithmic work over CALL time (device events around whole calls: the launch, the output allocation and the
 kernel), not over kernel time.  --attention-only prints this line alone.
 
-    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only]
+The training lines: one step's -log_prob(x).mean().backward() including the zeroing of the gradients, divergence='approximate' in
+training mode, at dim 2 / [32] and dim 32 / [32, 32] (the widest hidden layers sx_cnf_train_fwd / sx_cnf_train_bwd cover; dim 2 / [64]
+and dim 32 / [64, 64] train on the composition path and are timed on it alone), --train-rows rows, rk4 x --steps: the kernel path, the
+composition path on the same build and rows (forced by hiding the kernel plan), and the checkpoint bytes n_steps x rows x dim x 4.
+--train-only prints these lines alone.
+
+    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only] [--train-only] [--train-rows 16384]
 """
 import argparse
 import json
@@ -86,6 +92,38 @@ def attention_line(a, results):
           f'{r["max_abs_ldj"]:.2e}')
 
 
+def training_lines(a, results):
+    n = a.train_rows
+    for dim, hidden in ((2, [32]), (32, [32, 32]), (2, [64]), (32, [64, 64])):
+        torch.manual_seed(0)
+        cnf = st.ContinuousTransform(dim, net=st.net.DiffeqMLP(dim + 1, hidden, dim), divergence='approximate', solver='rk4',
+                                     solver_options={'step_size': 1.0 / a.steps})
+        flow = st.NormalizingFlow(st.UnitNormal(dim), [cnf]).to('cuda').train()
+        x = torch.randn(n, dim, device='cuda')
+
+        def step():
+            flow.zero_grad(set_to_none=True)
+            (-flow.log_prob(x).mean()).backward()
+        covered = cnf._train_kernel_net(0, x.device) is not None
+        ms = timed(step, a.reps) if covered else None
+        assert not covered or cnf._last_path == 'kernel'
+        plan = cnf._train_kernel_net
+        cnf._train_kernel_net = lambda *args: None          # (the composition path on the same build)
+        fb = timed(step, max(1, a.reps // 2), warm=1)
+        assert cnf._last_path == 'composed'
+        cnf._train_kernel_net = plan
+        ckpt = a.steps * n * dim * 4
+        key = f'train_dim{dim}_h{"x".join(map(str, hidden))}'
+        results[key] = {'rows': n, 'kernel_step_ms': ms, 'composed_step_ms': fb, 'composed_over_kernel': (fb / ms if covered else None),
+                        'checkpoint_bytes': ckpt if covered else 0}
+        if covered:
+            print(f'training dim {dim} {hidden} N={n} rk4 x {a.steps}: kernel path {ms:.2f} ms per step, composition path {fb:.1f} ms '
+                  f'= {fb / ms:.1f} x; checkpoints {ckpt} bytes')
+        else:
+            print(f'training dim {dim} {hidden} N={n} rk4 x {a.steps}: outside the training kernels (hidden > 32), composition path '
+                  f'{fb:.1f} ms per step')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=1 << 18)
@@ -96,14 +134,20 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--json', default=None)
     ap.add_argument('--attention-only', action='store_true', help='print the attention line alone')
+    ap.add_argument('--train-only', action='store_true', help='print the training lines alone')
+    ap.add_argument('--train-rows', type=int, default=1 << 14, help='rows of the training lines (the composition path finishes in seconds)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_cnf needs a GPU'
     results = {}
-    if not a.attention_only:
+    if not a.attention_only and not a.train_only:
         earlier_lines(a, results)
-    attention_line(a, results)
+    if not a.train_only:
+        attention_line(a, results)
+    if not a.attention_only:
+        training_lines(a, results)
     results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows, 'sets': a.sets,
-                         'set_fallback_sets': a.set_fallback_sets}
+                         'set_fallback_sets': a.set_fallback_sets, 'train_rows': a.train_rows,
+                         'build_id': st._hip.build_id()}
     if a.json:
         with open(a.json, 'w') as fh:
             json.dump(results, fh, indent=1)
