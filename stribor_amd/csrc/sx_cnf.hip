@@ -24,52 +24,24 @@
 // Coverage: dim <= 64 (<= 32 with two hidden layers wider than 64 units: that kernel would spill), 1 + dim + latent_dim <= 128,
 // one or two hidden layers of <= 128 units, activations Identity / Tanh /
 // ReLU / Sigmoid / ELU / Softplus / LeakyReLU (the ones whose derivative is a function of the activation's OUTPUT).
-#include "sx_cnf_common.h"
+//
+// The hidden layers, the output layer, the activation sweep, the network validator and the plan of the forward images are
+// sx_cnf_dense.h's, shared with sx_cnf_train.hip; this file's own are the trace and its constants in LDS.  The staging, the row load
+// and store and the latent GEMM are written out in cnf_flow_kernel, not taken from that header's functions, and the hidden and
+// output layers are expanded as its macros: cnf_flow_kernel<1, 4, 2> uses every register there is, any other form of these
+// statements allocates it differently, and each form tried cost dim 32 / [128, 128] 0.2 .. 0.8 % (29.18 ms for 29.01, 18.73 for 18.58).
+#include "sx_cnf_dense.h"
 
 namespace {
 
 // (inlined on purpose: an out-of-line call would spill the live stage vectors around it)
-__device__ __forceinline__ void cn_act_tile(f32x16 *v, int act) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) (*v)[r] = cnf_act((*v)[r], act);
-}
-
 __device__ __forceinline__ void cn_dact_tile(f32x16 *v, int act) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) (*v)[r] = cnf_dact((*v)[r], act);
 }
 
-// out[m] = (W . in)[m], m < MT; W: an image at `wb` (already offset by lane * 4), KT input tiles
-template <int KT, int MT>
-__device__ __forceinline__ void cn_gemm(const cnf_tile<KT> &in, cnf_tile<MT> &out, const float *wb) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        f32x16 acc = {};
-        cnf_mma<KT>(acc, in, wb + m * KT * 1024);
-        out.v[m] = acc;
-    }
-}
-
-// this file's own sweep, not cnf_act_all: with that one the (1, 4, 2)-tile kernel spills (30 VGPRs, 124 bytes of scratch per lane)
-template <int T>
-__device__ __forceinline__ void cn_act_all(cnf_tile<T> &v, int act) {
-#pragma unroll
-    for (int m = 0; m < T; ++m) {
-        if (act == SX_ACT_RELU) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v.v[m][r] = fmaxf(v.v[m][r], 0.f);
-        } else if (act != SX_ACT_IDENTITY) {
-            cn_act_tile(&v.v[m], act);
-        }
-    }
-}
-
-struct cn_args {
-    sx_cnf_net net;
-    int base_w[3];          // LDS float offset of W1x, W2(, W3)
-    int base_b[3];          // ... of the biases
-    int base_w0;            // ... of W1[:, 0] (the time column)
-    int base_tr;            // ... of c (one hidden layer) or C (two, when c_in_lds)
+struct cn_args : cnf_dense_args {
+    int base_tr;            // LDS float offset of c (one hidden layer) or C (two, when c_in_lds)
     const float *x;
     const float *latent;
     float *y;
@@ -84,17 +56,8 @@ template <int DT, int HT, int NH>
 __device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xin, float t, const cnf_tile<HT> &lat, cnf_tile<DT> &k, bool want, float &tr,
                                         int lane) {
     const int h = lane >> 5, act = a.net.act;
-    // the weights in LDS never change, so their loads are loop-invariant: without this the compiler hoists them out of the step
-    // loop and holds whole matrices in registers
-    asm volatile("" ::: "memory");
-    const float *b1 = cnf_smem + a.base_b[0] + 4 * h, *w0 = cnf_smem + a.base_w0 + 4 * h;
     cnf_tile<HT> h1;
-    cn_gemm<DT, HT>(xin, h1, cnf_smem + a.base_w[0] + lane * 4);
-#pragma unroll
-    for (int m = 0; m < HT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h1.v[m][r] = (h1.v[m][r] + lat.v[m][r]) + (cnf_vec(b1, m, r) + t * cnf_vec(w0, m, r));
-    cn_act_all<HT>(h1, act);
+    CNF_DENSE_H1(DT, HT, false, a, xin, t, lat, h1, lane, h, act);
     float s = 0.f;
     if (NH == 1) {
         if (want) {
@@ -108,21 +71,10 @@ __device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xi
                 for (int r = 0; r < 16; ++r) s += d[r] * cnf_vec(cv, m, r);
             }
         }
-        cn_gemm<HT, DT>(h1, k, cnf_smem + a.base_w[1] + lane * 4);
-        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
-#pragma unroll
-        for (int m = 0; m < DT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) k.v[m][r] += cnf_vec(b2, m, r);
+        CNF_DENSE_OUT(DT, HT, 1, a, h1, k, lane, h);
     } else {
         cnf_tile<HT> h2;
-        cn_gemm<HT, HT>(h1, h2, cnf_smem + a.base_w[1] + lane * 4);
-        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
-#pragma unroll
-        for (int m = 0; m < HT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) h2.v[m][r] += cnf_vec(b2, m, r);
-        cn_act_all<HT>(h2, act);
+        CNF_DENSE_H2(HT, false, a, h1, h2, lane, h, act);
         if (want) {
             // h1 <- d1, v = C d1, s = d2 . v
 #pragma unroll
@@ -144,12 +96,7 @@ __device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xi
             }
         }
         asm volatile("" ::: "memory");
-        cn_gemm<HT, DT>(h2, k, cnf_smem + a.base_w[2] + lane * 4);
-        const float *b3 = cnf_smem + a.base_b[2] + 4 * h;
-#pragma unroll
-        for (int m = 0; m < DT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) k.v[m][r] += cnf_vec(b3, m, r);
+        CNF_DENSE_OUT(DT, HT, 2, a, h2, k, lane, h);
     }
     if (want) tr = s + __shfl_xor(s, 32, 64);          // the two lane halves hold the two feature halves of a row
 }
@@ -245,48 +192,25 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
     }
 }
 
-// the LDS plan: float offsets into `a` (may be null), -> floats used.  C goes into LDS when it fits beside the rest.
-size_t cn_plan(const sx_cnf_net &net, int want_ldj, cn_args *a) {
-    const int DT = cnf_tiles(net.dim), NH = net.n_layers - 1;
-    int HT = 1;
-    for (int l = 0; l < NH; ++l) HT = cnf_tiles(net.layer[l].out_dim) > HT ? cnf_tiles(net.layer[l].out_dim) : HT;
-    size_t off = 0;
-    int bw[3] = {0, 0, 0}, bb[3] = {0, 0, 0};
-    for (int l = 0; l <= NH; ++l) {
-        const int KT = l == 0 ? DT : HT, MT = l == NH ? DT : HT;
-        bw[l] = (int)off; off += (size_t)MT * KT * 1024;
-        bb[l] = (int)off; off += (size_t)MT * 32;
-    }
-    const int base_w0 = (int)off; off += (size_t)HT * 32;
-    const int base_tr = (int)off;
-    int c_in_lds = 1;
+// the LDS plan: the forward images, then c / C.  C goes into LDS when it fits beside the rest.  -> floats used
+size_t cn_plan(const sx_cnf_net &net, int want_ldj, cn_args &a) {
+    const int NH = net.n_layers - 1, HT = cnf_dense_hidden_tiles(net);
+    size_t off = cnf_dense_plan(net, a);
+    a.base_tr = (int)off;
+    a.c_in_lds = 1;
     if (NH == 1) off += (size_t)HT * 32;
     else if (want_ldj) {
         const size_t c_floats = (size_t)HT * HT * 1024;
         if ((off + c_floats) * 4 <= SX_CNF_LDS_BYTES) off += c_floats;
-        else c_in_lds = 0;
-    }
-    if (a) {
-        for (int l = 0; l < 3; ++l) { a->base_w[l] = bw[l]; a->base_b[l] = bb[l]; }
-        a->base_w0 = base_w0; a->base_tr = base_tr; a->c_in_lds = c_in_lds;
+        else a.c_in_lds = 0;
     }
     return off;
 }
 
 int cn_check_net(const sx_cnf_net *net_host) {
-    SX_REQUIRE(net_host != nullptr, "sx_cnf_flow: null network");
+    const int rc = cnf_dense_check_net("sx_cnf_flow", net_host, SX_CNF_MAX_DIM, 128, 128);
+    if (rc != SX_OK) return rc;
     const sx_cnf_net &net = *net_host;
-    SX_REQUIRE(net.n_layers == 2 || net.n_layers == 3, "sx_cnf_flow: one or two hidden layers (got %d Linear layers)", net.n_layers);
-    SX_REQUIRE(net.dim >= 1 && net.dim <= SX_CNF_MAX_DIM, "sx_cnf_flow: dim must be in 1..%d (got %d)", SX_CNF_MAX_DIM, net.dim);
-    SX_REQUIRE(net.latent_dim >= 0 && 1 + net.dim + net.latent_dim <= 128, "sx_cnf_flow: 1 + dim + latent_dim must be <= 128");
-    SX_REQUIRE(net.act >= SX_ACT_IDENTITY && net.act <= SX_ACT_LEAKYRELU, "sx_cnf_flow: activation %d has no in-kernel derivative", net.act);
-    for (int l = 0; l < net.n_layers; ++l) {
-        const sx_cnf_layer &L = net.layer[l];
-        SX_REQUIRE(L.W != nullptr, "sx_cnf_flow: layer %d has no weight", l);
-        SX_REQUIRE(L.in_dim == (l == 0 ? 1 + net.dim + net.latent_dim : net.layer[l - 1].out_dim), "sx_cnf_flow: layer %d input width", l);
-        SX_REQUIRE(L.out_dim >= 1 && L.out_dim <= 128, "sx_cnf_flow: layer %d width must be in 1..128", l);
-    }
-    SX_REQUIRE(net.layer[net.n_layers - 1].out_dim == net.dim, "sx_cnf_flow: the last layer must map back to dim");
     // two hidden layers of four tiles beside a two-tile state do not fit the register file (the build would spill): not offered
     SX_REQUIRE(!(net.n_layers == 3 && net.dim > 32 && (net.layer[0].out_dim > 64 || net.layer[1].out_dim > 64)),
                "sx_cnf_flow: two hidden layers wider than 64 units need dim <= 32 (got dim %d)", net.dim);
@@ -297,7 +221,8 @@ int cn_check_net(const sx_cnf_net *net_host) {
 
 extern "C" size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj) {
     if (cn_check_net(net_host) != SX_OK) return 0;
-    return cn_plan(*net_host, want_ldj, nullptr) * 4;
+    cn_args a{};
+    return cn_plan(*net_host, want_ldj, a) * 4;
 }
 
 extern "C" int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
@@ -311,15 +236,13 @@ extern "C" int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const flo
     SX_REQUIRE(!want_ldj || (ldj != nullptr && net.trace != nullptr), "sx_cnf_flow: want_ldj needs ldj and the trace constants");
     cn_args a{};
     a.net = net;
-    const size_t lds = cn_plan(net, want_ldj ? 1 : 0, &a) * 4;
+    const size_t lds = cn_plan(net, want_ldj ? 1 : 0, a) * 4;
     SX_REQUIRE(lds <= SX_CNF_LDS_BYTES, "sx_cnf_flow: the padded weights need %zu bytes of LDS (budget %d)", lds, SX_CNF_LDS_BYTES);
     if (n_rows == 0) return SX_OK;
     a.x = x; a.latent = latent; a.y = y; a.ldj = ldj; a.n_rows = n_rows;
     a.solver = solver; a.n_steps = n_steps; a.want_ldj = want_ldj ? 1 : 0;
     a.t0 = t0; a.t1 = t1; a.step_size = step_size;
-    const int DT = cnf_tiles(net.dim), NH = net.n_layers - 1;
-    int HT = 1;
-    for (int l = 0; l < NH; ++l) HT = cnf_tiles(net.layer[l].out_dim) > HT ? cnf_tiles(net.layer[l].out_dim) : HT;
+    const int DT = cnf_tiles(net.dim), NH = net.n_layers - 1, HT = cnf_dense_hidden_tiles(net);
     const int64_t want = cnf_row_blocks(n_rows);
 #define CN_CASE(D_, H_)                                                                                  \
     if (DT == D_ && HT == H_)                                                                            \

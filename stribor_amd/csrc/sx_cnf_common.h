@@ -1,4 +1,5 @@
-// What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip, sx_cnf_attn.hip) have in common:
+// What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip, sx_cnf_attn.hip) and the training
+// kernels of the dense CNF (sx_cnf_train.hip) have in common:
 //   * the layout: a workgroup of 4 waves, one wave = 32 rows on the MFMA column (lane & 31), features on the C rows, a 32-feature tile
 //     of a row = one f32x16 C fragment = the B operand of the next GEMM; feature kmap(r, h) sits in register r of lane half h;
 //   * the seven activations whose derivative is a function of the activation's OUTPUT;
@@ -6,8 +7,9 @@
 //   * the fixed grid and the euler / midpoint / rk4 (3/8 rule) tableau.  The files that include this header are compiled with
 //     -ffp-contract=off: the tableau's parenthesisation is the reference solver's sequence of roundings;
 //   * the launcher and the per-call argument checks.
-// sx_cnf.hip uses all of it but cnf_act_all (its own sweep keeps its widest kernel free of spills) and cnf_latent_packed.
-// Everything here has internal linkage: five translation units include it.
+// sx_cnf.hip and sx_cnf_train.hip take it through sx_cnf_dense.h, which adds what the two dense files share with each other alone;
+// they use all of it but cnf_act_all (sx_cnf_dense.h's sweep keeps the widest dense kernel free of spills) and cnf_latent_packed.
+// Everything here has internal linkage: six translation units include it.
 #pragma once
 #include "sx_common.h"
 
@@ -126,7 +128,18 @@ __device__ __forceinline__ void cnf_mma(f32x16 &acc, const cnf_tile<KT> &in, con
     }
 }
 
-// the same with the 32 matrix rows read from global memory: `W` = row 32m of a row-major matrix of KT * 32 columns, zero-padded (a
+// out[m] = (W . in)[m], m < MT; W: an image at `wb` (already offset by lane * 4), KT input tiles
+template <int KT, int MT>
+__device__ __forceinline__ void cnf_gemm(const cnf_tile<KT> &in, cnf_tile<MT> &out, const float *wb) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        f32x16 acc = {};
+        cnf_mma<KT>(acc, in, wb + m * KT * 1024);
+        out.v[m] = acc;
+    }
+}
+
+// cnf_mma with the 32 matrix rows read from global memory: `W` = row 32m of a row-major matrix of KT * 32 columns, zero-padded (a
 // lane's four A values of k-group g are the contiguous columns 32c + 8g + 4h .. + 3 of row lane & 31)
 template <int KT>
 __device__ __forceinline__ void cnf_mma_global(f32x16 &acc, const cnf_tile<KT> &in, const float *__restrict__ W, int lane) {

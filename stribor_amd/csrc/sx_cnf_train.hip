@@ -20,9 +20,14 @@
 // the wave's own partial in global memory.  cnf_train_reduce_kernel sums the partials in slot order: no atomics anywhere, so two
 // calls on the same inputs give the same bits.
 //
+// Everything the solve has in common with sx_cnf_flow -- the staging of the forward images, the row load / store, the latent GEMM,
+// the hidden layers, the output layer, the network validator and the plan of the forward images -- is sx_cnf_dense.h's, used here
+// with one state tile and one hidden tile; this file's own are the estimate, the adjoint sweep and the partial sums.
+//
 // Coverage: dim <= 32, 1 + dim + latent_dim <= 64, one or two hidden layers of <= 32 units (one tile: the adjoint sweep of a
-// two-tile hidden layer does not build without scratch), the seven activations of sx_cnf_flow.
-#include "sx_cnf_common.h"
+// two-tile hidden layer does not build without scratch, so every hidden quantity below is ONE tile), the seven activations of
+// sx_cnf_flow.
+#include "sx_cnf_dense.h"
 
 #define SX_CNF_TRAIN_MAX_BLOCKS 512      /* partial slots = 4 waves x min(row blocks, this) */
 #if SX_CNF_TRAIN_MAX_HIDDEN != 32 || SX_CNF_TRAIN_MAX_DIM != 32 || SX_CNF_TRAIN_MAX_IN != 64
@@ -32,10 +37,10 @@
 
 namespace {
 
-struct ct_args {
-    sx_cnf_net net;
-    int base_w[3], base_b[3], base_w0;      // LDS float offsets: forward images, biases, the time column (as sx_cnf_flow)
-    int base_t[3];                           // ... of the transposed images W1x^T, W2^T (two hidden layers), W_last^T
+typedef cnf_tile<1> ct_tile;             /* a state or a hidden layer: one tile either way */
+
+struct ct_args : cnf_dense_args {
+    int base_t[3];                           // LDS float offsets of the transposed images W1x^T, W2^T (two hidden layers), W_last^T
     int base_scr, scr_stride;                // ... of wave 0's scratch, floats per wave
     int off_w2, off_wl, off_lat, off_vec;    // float offsets inside a wave's partial (dW1x at 0)
     int part_floats, n_virtual;
@@ -45,48 +50,6 @@ struct ct_args {
     int solver, n_steps;
     float t0, t1, step_size;
 };
-
-template <int KT, int MT>
-__device__ __forceinline__ void ct_gemm(const cnf_tile<KT> &in, cnf_tile<MT> &out, const float *wb) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        f32x16 acc = {};
-        cnf_mma<KT>(acc, in, wb + m * KT * 1024);
-        out.v[m] = acc;
-    }
-}
-
-// act(v) of a whole tile (cnf_act's arithmetic): one wave-uniform switch around the sweep, not one per element
-__device__ __forceinline__ void ct_act_tile(f32x16 &v, int act) {
-    switch (act) {
-        case SX_ACT_TANH:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = cnf_act(v[r], SX_ACT_TANH);
-            break;
-        case SX_ACT_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = cnf_act(v[r], SX_ACT_RELU);
-            break;
-        case SX_ACT_SIGMOID:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = cnf_act(v[r], SX_ACT_SIGMOID);
-            break;
-        case SX_ACT_ELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = cnf_act(v[r], SX_ACT_ELU);
-            break;
-        case SX_ACT_SOFTPLUS:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = cnf_act(v[r], SX_ACT_SOFTPLUS);
-            break;
-        case SX_ACT_LEAKYRELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = cnf_act(v[r], SX_ACT_LEAKYRELU);
-            break;
-        default:
-            break;
-    }
-}
 
 // d = act'(v) of a whole tile from a = act(v): one wave-uniform switch around the sweep, not one per element
 __device__ __forceinline__ void ct_dact_tile(const f32x16 &a, f32x16 &d, int act) {
@@ -146,174 +109,63 @@ __device__ __forceinline__ void ct_d2act_tile(const f32x16 &a, const f32x16 &d, 
     }
 }
 
-// image of W^T: MT x KT tiles, tile (m, c) float g*256 + lane*4 + j holds W[32c + kmap(4g + j, lane >> 5)][col0 + 32m + (lane & 31)]
-__device__ __forceinline__ void ct_stage_t(const float *__restrict__ W, int out_dim, int in_dim, int ld, int col0, int MT, int KT, int base) {
-    const int n_w = MT * KT * 1024;
-    for (int e = threadIdx.x; e < n_w; e += SX_CNF_THREADS) {
-        const int tile = e >> 10, rem = e & 1023;
-        const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
-        const int m = tile / KT, c = tile - m * KT;
-        const int row = 32 * m + (lane & 31), col = 32 * c + cnf_kmap(4 * g + j, lane >> 5);
+// image of W^T, one tile: float g*256 + lane*4 + j holds W[kmap(4g + j, lane >> 5)][col0 + (lane & 31)]
+__device__ __forceinline__ void ct_stage_t(const float *__restrict__ W, int out_dim, int in_dim, int ld, int col0, int base) {
+    for (int e = threadIdx.x; e < 1024; e += SX_CNF_THREADS) {
+        const int g = e >> 8, lane = (e >> 2) & 63, j = e & 3;
+        const int row = lane & 31, col = cnf_kmap(4 * g + j, lane >> 5);
         cnf_smem[base + e] = (row < in_dim && col < out_dim) ? W[(int64_t)col * ld + col0 + row] : 0.f;
     }
 }
 
-template <int HT, int NH>
+template <int NH>
 __device__ __forceinline__ void ct_stage_all(const ct_args &a, bool backward) {
     const sx_cnf_net &net = a.net;
     const int D = net.dim, in_dim = 1 + D + net.latent_dim, H1 = net.layer[0].out_dim, Hl = net.layer[NH - 1].out_dim;
-    cnf_stage(net.layer[0].W, H1, D, in_dim, 1, HT, 1, a.base_w[0]);
-    cnf_stage_vec(net.layer[0].b, H1, 1, HT * 32, a.base_b[0]);
-    cnf_stage_vec(net.layer[0].W, H1, in_dim, HT * 32, a.base_w0);
-    if (NH == 2) {
-        cnf_stage(net.layer[1].W, Hl, H1, H1, 0, HT, HT, a.base_w[1]);
-        cnf_stage_vec(net.layer[1].b, Hl, 1, HT * 32, a.base_b[1]);
-    }
-    cnf_stage(net.layer[NH].W, D, Hl, Hl, 0, 1, HT, a.base_w[NH]);
-    cnf_stage_vec(net.layer[NH].b, D, 1, 32, a.base_b[NH]);
-    ct_stage_t(net.layer[NH].W, D, Hl, Hl, 0, HT, 1, a.base_t[NH]);
+    cnf_dense_stage<1, 1, NH>(a);
+    ct_stage_t(net.layer[NH].W, D, Hl, Hl, 0, a.base_t[NH]);
     if (backward) {
-        ct_stage_t(net.layer[0].W, H1, D, in_dim, 1, 1, HT, a.base_t[0]);
-        if (NH == 2) ct_stage_t(net.layer[1].W, Hl, H1, H1, 0, HT, HT, a.base_t[1]);
+        ct_stage_t(net.layer[0].W, H1, D, in_dim, 1, a.base_t[0]);
+        if (NH == 2) ct_stage_t(net.layer[1].W, Hl, H1, H1, 0, a.base_t[1]);
     }
-}
-
-// rows [row, f] of a [n, D] array as a state tile (0 beyond the live rows and features)
-__device__ __forceinline__ void ct_load(f32x16 &v, const float *__restrict__ p, int64_t row, int D, bool live, int h) {
-    const float *pr = p + (live ? row : 0) * D;          // (every lane loads: a dead row reads row 0, a dead feature reads feature 0)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int f = cnf_kmap(r, h);
-        const float t = pr[f < D ? f : 0];
-        v[r] = (live && f < D) ? t : 0.f;
-    }
-}
-
-__device__ __forceinline__ void ct_store(float *__restrict__ p, const f32x16 &v, int64_t row, int D, bool live, int h) {
-    if (!live) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int f = cnf_kmap(r, h);
-        if (f < D) p[row * D + f] = v[r];
-    }
-}
-
-// the latent share of the first layer, W1[:, 1 + D ..] . latent_row: sx_cnf_flow's sequence of operations
-template <int HT>
-__device__ __forceinline__ void ct_latent(const ct_args &a, cnf_tile<HT> &lat, int64_t row, bool live, int lane, const float *staged = nullptr) {
-    const sx_cnf_net &net = a.net;
-    const int D = net.dim, L = net.latent_dim, in_dim = 1 + D + L, H1 = net.layer[0].out_dim, h = lane >> 5;
-#pragma unroll
-    for (int m = 0; m < HT; ++m) lat.v[m] = f32x16{};
-    if (L > 0) {
-        const float *W1 = net.layer[0].W;
-        for (int c = 0; c < (L + 31) >> 5; ++c) {
-            f32x16 lb;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + cnf_kmap(r, h);
-                // (every lane loads, from a valid address; `staged`: the group's rows already in LDS)
-                const float t = staged != nullptr ? staged[(lane & 31) * L + (f < L ? f : 0)] : a.latent[(live ? row : 0) * L + (f < L ? f : 0)];
-                lb[r] = (live && f < L) ? t : 0.f;
-            }
-#pragma unroll
-            for (int m = 0; m < HT; ++m) {
-                const int wr = 32 * m + (lane & 31);
-                const float *wrow = W1 + (int64_t)(wr < H1 ? wr : 0) * in_dim + 1 + D;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int f = 32 * c + cnf_kmap(q, h);
-                    const float t = wrow[f < L ? f : 0];
-                    const float av = (wr < H1 && f < L) ? t : 0.f;
-                    lat.v[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, lb[q], lat.v[m], 0, 0, 0);
-                }
-            }
-        }
-    }
-}
-
-// the hidden activations at (t, xin): cn_eval's arithmetic, operation for operation
-template <int HT, int NH>
-__device__ __forceinline__ void ct_hidden(const ct_args &a, const cnf_tile<1> &xin, float t, const cnf_tile<HT> &lat, cnf_tile<HT> &h1,
-                                          cnf_tile<HT> &h2, int lane) {
-    const int h = lane >> 5, act = a.net.act;
-    asm volatile("" ::: "memory");          // (the weights in LDS never change: keep their loads inside the loops, as cn_eval does)
-    const float *b1 = cnf_smem + a.base_b[0] + 4 * h, *w0 = cnf_smem + a.base_w0 + 4 * h;
-    ct_gemm<1, HT>(xin, h1, cnf_smem + a.base_w[0] + lane * 4);
-#pragma unroll
-    for (int m = 0; m < HT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h1.v[m][r] = (h1.v[m][r] + lat.v[m][r]) + (cnf_vec(b1, m, r) + t * cnf_vec(w0, m, r));
-#pragma unroll
-    for (int m = 0; m < HT; ++m) ct_act_tile(h1.v[m], act);
-    if (NH == 2) {
-        ct_gemm<HT, HT>(h1, h2, cnf_smem + a.base_w[1] + lane * 4);
-        const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
-#pragma unroll
-        for (int m = 0; m < HT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) h2.v[m][r] += cnf_vec(b2, m, r);
-#pragma unroll
-        for (int m = 0; m < HT; ++m) ct_act_tile(h2.v[m], act);
-    }
-}
-
-// k = W_last h_last + b_last
-template <int HT, int NH>
-__device__ __forceinline__ void ct_value(const ct_args &a, const cnf_tile<HT> &hl, cnf_tile<1> &k, int lane) {
-    asm volatile("" ::: "memory");
-    ct_gemm<HT, 1>(hl, k, cnf_smem + a.base_w[NH] + lane * 4);
-    const float *bl = cnf_smem + a.base_b[NH] + 4 * (lane >> 5);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) k.v[0][r] += cnf_vec(bl, 0, r);
 }
 
 // the Hutchinson estimate e^T J e of a row from the hidden activations
-template <int HT, int NH>
-__device__ __forceinline__ float ct_estimate(const ct_args &a, const cnf_tile<HT> &h1, const cnf_tile<HT> &h2, const cnf_tile<HT> &u1,
-                                             const cnf_tile<HT> &v, int lane) {
+template <int NH>
+__device__ __forceinline__ float ct_estimate(const ct_args &a, const ct_tile &h1, const ct_tile &h2, const ct_tile &u1, const ct_tile &v, int lane) {
     const int act = a.net.act;
     float s = 0.f;
     if (NH == 1) {
+        f32x16 d1;
+        ct_dact_tile(h1.v[0], d1, act);
 #pragma unroll
-        for (int m = 0; m < HT; ++m) {
-            f32x16 d1;
-            ct_dact_tile(h1.v[m], d1, act);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += (d1[r] * u1.v[m][r]) * v.v[m][r];
-        }
+        for (int r = 0; r < 16; ++r) s += (d1[r] * u1.v[0][r]) * v.v[0][r];
     } else {
-        cnf_tile<HT> w, rr;
+        ct_tile w, rr;
+        ct_dact_tile(h1.v[0], w.v[0], act);
 #pragma unroll
-        for (int m = 0; m < HT; ++m) {
-            ct_dact_tile(h1.v[m], w.v[m], act);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) w.v[m][r] = w.v[m][r] * u1.v[m][r];
-        }
+        for (int r = 0; r < 16; ++r) w.v[0][r] = w.v[0][r] * u1.v[0][r];
         asm volatile("" ::: "memory");
-        ct_gemm<HT, HT>(w, rr, cnf_smem + a.base_w[1] + lane * 4);
+        cnf_gemm<1, 1>(w, rr, cnf_smem + a.base_w[1] + lane * 4);
+        f32x16 d2;
+        ct_dact_tile(h2.v[0], d2, act);
 #pragma unroll
-        for (int m = 0; m < HT; ++m) {
-            f32x16 d2;
-            ct_dact_tile(h2.v[m], d2, act);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += (v.v[m][r] * d2[r]) * rr.v[m][r];
-        }
+        for (int r = 0; r < 16; ++r) s += (v.v[0][r] * d2[r]) * rr.v[0][r];
     }
     return s + __shfl_xor(s, 32, 64);          // the two lane halves hold the two feature halves of a row
 }
 
 // the per-row constants of a solve: u1 = W1x e, v = W_last^T e
-template <int HT, int NH>
-__device__ __forceinline__ void ct_row_constants(const ct_args &a, const cnf_tile<1> &e, cnf_tile<HT> &u1, cnf_tile<HT> &v, int lane) {
+template <int NH>
+__device__ __forceinline__ void ct_row_constants(const ct_args &a, const ct_tile &e, ct_tile &u1, ct_tile &v, int lane) {
     asm volatile("" ::: "memory");
-    ct_gemm<1, HT>(e, u1, cnf_smem + a.base_w[0] + lane * 4);
-    ct_gemm<1, HT>(e, v, cnf_smem + a.base_t[NH] + lane * 4);
+    cnf_gemm<1, 1>(e, u1, cnf_smem + a.base_w[0] + lane * 4);
+    cnf_gemm<1, 1>(e, v, cnf_smem + a.base_t[NH] + lane * 4);
 }
 
-template <int HT, int NH>
+template <int NH>
 __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_args a) {
-    ct_stage_all<HT, NH>(a, false);
+    ct_stage_all<NH>(a, false);
     __syncthreads();
     const int D = a.net.dim;
     const int lane = threadIdx.x & 63, h = lane >> 5;
@@ -323,12 +175,11 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_
          grp += (int64_t)gridDim.x * SX_CNF_WAVES) {
         const int64_t row = grp * 32 + (lane & 31);
         const bool live = row < a.n_rows;
-        cnf_tile<1> y, e;
-        ct_load(y.v[0], a.x, row, D, live, h);
-        ct_load(e.v[0], a.e, row, D, live, h);
-        cnf_tile<HT> lat, u1, v;
-        ct_latent<HT>(a, lat, row, live, lane);
-        ct_row_constants<HT, NH>(a, e, u1, v, lane);
+        ct_tile y, e, lat, u1, v;
+        cnf_dense_load<1>(y, a.x, row, D, live, h);
+        cnf_dense_load<1>(e, a.e, row, D, live, h);
+        cnf_dense_latent<1>(a, lat, a.latent, row, live, lane);
+        ct_row_constants<NH>(a, e, u1, v, lane);
         float l = 0.f;
         const int n_stages = cnf_stages(a.solver);
         const float third = 1.f / 3.f, two_thirds = 2.f / 3.f;
@@ -336,19 +187,18 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_
             float ta, tb;
             cnf_grid(a, sgn, i, ta, tb);
             const float dt = tb - ta, half = 0.5f * dt;
-            if (a.ckpt != nullptr) ct_store(a.ckpt + (int64_t)i * a.n_rows * D, y.v[0], row, D, live, h);
-            cnf_tile<1> k1, k2, xs = y;
+            if (a.ckpt != nullptr) cnf_dense_store<1>(a.ckpt + (int64_t)i * a.n_rows * D, y, row, D, live, h);
+            ct_tile k1, k2, xs = y;
             float q1 = 0.f, q2 = 0.f, ts = ta;
             for (int st = 0; st < n_stages; ++st) {
-                cnf_tile<1> k;
-                cnf_tile<HT> h1, h2;
-                ct_hidden<HT, NH>(a, xs, ts, lat, h1, h2, lane);
-                const float q = ct_estimate<HT, NH>(a, h1, h2, u1, v, lane);
-                ct_value<HT, NH>(a, NH == 1 ? h1 : h2, k, lane);
+                ct_tile k, h1, h2;
+                cnf_dense_hidden<1, 1, NH, true>(a, xs, ts, lat, h1, h2, lane);
+                const float q = ct_estimate<NH>(a, h1, h2, u1, v, lane);
+                cnf_dense_out<1, 1, NH>(a, NH == 1 ? h1 : h2, k, lane);
                 cnf_tableau<1>(a.solver, st, ta, tb, dt, half, third, two_thirds, k, q, k1, k2, q1, q2, xs, ts, y, l);
             }
         }
-        ct_store(a.y, y.v[0], row, D, live, h);
+        cnf_dense_store<1>(a.y, y, row, D, live, h);
         if (live && h == 0) a.ldj[row] = l;
     }
 }
@@ -427,9 +277,9 @@ __device__ __forceinline__ float ct_stage_time(int solver, int st, float ta, flo
     return st == 1 ? ta + dt * third : st == 2 ? ta + dt * two_thirds : tb;
 }
 
-template <int HT, int NH, int SOLVER>
+template <int NH, int SOLVER>
 __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_args a) {
-    ct_stage_all<HT, NH>(a, true);
+    ct_stage_all<NH>(a, true);
     __syncthreads();
     const sx_cnf_net &net = a.net;
     const int D = net.dim, L = net.latent_dim, in_dim = 1 + D + L, H1 = net.layer[0].out_dim, act = net.act;
@@ -437,20 +287,16 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
     const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
     // the wave's scratch: two transposition slots, the stage inputs z_1 .. z_3 (also the staging area of the latent rows), e, gx
     float *sA = cnf_smem + a.base_scr + wave * a.scr_stride, *sB = sA + CT_SLOT, *zb = sB + CT_SLOT, *sE = zb + 3 * 1024, *sY = sE + 1024;
-    float *sL = sY + CT_SLOT + lane;          // sum a1b of the group's rows (read by the latent columns only), [tile][register][lane]
+    float *sL = sY + CT_SLOT + lane;          // sum a1b of the group's rows (read by the latent columns only), [register][lane]
     float *sP = zb + 2 * 1024 + lane, *sQ = zb + 1024 + lane;          // the tableau's two carried tiles, in the z slots their stages have left
     float *part = a.partial + ((int64_t)blockIdx.x * SX_CNF_WAVES + wave) * a.part_floats;
     const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
     const int n_stages = cnf_stages(SOLVER);
     const float third = 1.f / 3.f, two_thirds = 2.f / 3.f;
     // the accumulators of the whole pass loop
-    f32x16 gW1[HT], gWl[HT], gW2[NH == 2 ? HT * HT : 1];
-    float gb1[HT], gtc[HT], gb2[HT], gbl = 0.f;
-#pragma unroll
-    for (int m = 0; m < HT; ++m) { gW1[m] = f32x16{}; gWl[m] = f32x16{}; gb1[m] = gtc[m] = gb2[m] = 0.f; }
-#pragma unroll
-    for (int m = 0; m < (NH == 2 ? HT * HT : 1); ++m) gW2[m] = f32x16{};
-    for (int i = lane; i < HT * LT * 1024; i += 64) part[a.off_lat + i] = 0.f;
+    f32x16 gW1 = {}, gWl = {}, gW2 = {};
+    float gb1 = 0.f, gtc = 0.f, gb2 = 0.f, gbl = 0.f;
+    for (int i = lane; i < LT * 1024; i += 64) part[a.off_lat + i] = 0.f;
 
     const int64_t n_groups = (a.n_rows + 31) >> 5;
     for (int64_t grp = (int64_t)blockIdx.x * SX_CNF_WAVES + wave; grp < n_groups; grp += (int64_t)gridDim.x * SX_CNF_WAVES) {
@@ -463,13 +309,11 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
         ct_fetch(sY, a.gy, row0, n_live, D, lane);
         ct_fetch(sE, a.e, row0, n_live, D, lane);
         const float lb = a.gldj[live ? row : 0] * (live ? 1.f : 0.f);
-        cnf_tile<HT> lat;
+        ct_tile lat;
         if (L > 0) ct_fetch(zb, a.latent, row0, n_live, L, lane);
-        ct_latent<HT>(a, lat, row, live, lane, zb);
+        cnf_dense_latent<1>(a, lat, a.latent, row, live, lane, zb);
 #pragma unroll
-        for (int m = 0; m < HT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sL[m * 1024 + r * 64] = 0.f;
+        for (int r = 0; r < 16; ++r) sL[r * 64] = 0.f;
 
 #pragma unroll 1
         for (int i = a.n_steps - 1; i >= 0; --i) {
@@ -477,17 +321,16 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
             cnf_grid(a, sgn, i, ta, tb);
             const float dt = tb - ta, half = 0.5f * dt;
             if (n_stages > 1) {   // the stage inputs z_1 .. z_{S-1} (z_0 is the checkpoint): the forward's own tableau
-                cnf_tile<1> k1, k2, xs, yy;
+                ct_tile k1, k2, xs, yy;
                 ct_fetch(sA, a.ckpt_in + (int64_t)i * a.n_rows * D, row0, n_live, D, lane);
                 ct_take(yy.v[0], sA, D, 0, live, lane);
                 xs = yy;
                 float q1 = 0.f, q2 = 0.f, ts = ta, l = 0.f;
 #pragma unroll 1
                 for (int st = 0; st + 1 < n_stages; ++st) {
-                    cnf_tile<1> k;
-                    cnf_tile<HT> h1, h2;
-                    ct_hidden<HT, NH>(a, xs, ts, lat, h1, h2, lane);
-                    ct_value<HT, NH>(a, NH == 1 ? h1 : h2, k, lane);
+                    ct_tile k, h1, h2;
+                    cnf_dense_hidden<1, 1, NH, true>(a, xs, ts, lat, h1, h2, lane);
+                    cnf_dense_out<1, 1, NH>(a, NH == 1 ? h1 : h2, k, lane);
                     cnf_tableau<1>(SOLVER, st, ta, tb, dt, half, third, two_thirds, k, 0.f, k1, k2, q1, q2, xs, ts, yy, l);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) zb[st * 1024 + r * 64 + lane] = xs.v[0][r];
@@ -498,7 +341,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
             // stage 0 needs) and Q = zb_4 + zb_3 + zb_2; midpoint -- P = zb_2
 #pragma unroll 1
             for (int st = n_stages - 1; st >= 0; --st) {
-                cnf_tile<1> z, kb, zbar, yb, e;
+                ct_tile z, kb, zbar, yb, e;
                 ct_take(yb.v[0], sY, D, 0, live, lane);
                 if (st == 0) {
                     ct_fetch(sA, a.ckpt_in + (int64_t)i * a.n_rows * D, row0, n_live, D, lane);
@@ -528,135 +371,98 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                 }
 
                 // ---- one evaluation's adjoint at (t, z) -------------------------------------------------------------------------
-                cnf_tile<HT> h1, h2, a1;
-                ct_hidden<HT, NH>(a, z, t, lat, h1, h2, lane);
+                ct_tile h1, h2, a1;
+                cnf_dense_hidden<1, 1, NH, true>(a, z, t, lat, h1, h2, lane);
                 asm volatile("" ::: "memory");
                 if constexpr (NH == 1) {
-                    cnf_tile<HT> hb1;
-                    ct_gemm<1, HT>(kb, hb1, cnf_smem + a.base_t[1] + lane * 4);
+                    ct_tile hb1, u1, v;
+                    cnf_gemm<1, 1>(kb, hb1, cnf_smem + a.base_t[1] + lane * 4);
                     // dW2 += kb h1^T + e (qb d1 u1)^T, db2 += kb
                     ct_put(sA, kb.v[0], lane);
                     gbl += ct_rowsum(sA, lane);
-#pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        ct_put(sB, h1.v[m], lane);
-                        ct_outer(gWl[m], sA, sB, lane);
-                    }
-                    cnf_tile<HT> u1, v;
+                    ct_put(sB, h1.v[0], lane);
+                    ct_outer(gWl, sA, sB, lane);
                     ct_take(e.v[0], sE, D, 0, live, lane);
-                    ct_row_constants<HT, NH>(a, e, u1, v, lane);
+                    ct_row_constants<NH>(a, e, u1, v, lane);
                     ct_put(sA, e.v[0], lane);
+                    f32x16 pv, d1, s1;
+                    ct_dact_tile(h1.v[0], d1, act);
+                    ct_d2act_tile(h1.v[0], d1, s1, act);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        f32x16 pv, d1, s1;
-                        ct_dact_tile(h1.v[m], d1, act);
-                        ct_d2act_tile(h1.v[m], d1, s1, act);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            pv[r] = (qb * d1[r]) * u1.v[m][r];
-                            a1.v[m][r] = hb1.v[m][r] * d1[r] + ((qb * s1[r]) * u1.v[m][r]) * v.v[m][r];
-                            u1.v[m][r] = (qb * d1[r]) * v.v[m][r];          // (the adjoint of u1)
-                        }
-                        ct_put(sB, pv, lane);
-                        ct_outer(gWl[m], sA, sB, lane);
+                    for (int r = 0; r < 16; ++r) {
+                        pv[r] = (qb * d1[r]) * u1.v[0][r];
+                        a1.v[0][r] = hb1.v[0][r] * d1[r] + ((qb * s1[r]) * u1.v[0][r]) * v.v[0][r];
+                        u1.v[0][r] = (qb * d1[r]) * v.v[0][r];          // (the adjoint of u1)
                     }
+                    ct_put(sB, pv, lane);
+                    ct_outer(gWl, sA, sB, lane);
                     // the u1 adjoint's share of dW1x: (qb d1 v) e^T
                     ct_put(sB, e.v[0], lane);
-#pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        ct_put(sA, u1.v[m], lane);
-                        ct_outer(gW1[m], sA, sB, lane);
-                    }
+                    ct_put(sA, u1.v[0], lane);
+                    ct_outer(gW1, sA, sB, lane);
                 } else {
-                    cnf_tile<HT> w, rr, hb2, a2, rb, wb, hb1, u1, v;
+                    ct_tile w, rr, hb2, a2, rb, wb, hb1, u1, v;
                     ct_take(e.v[0], sE, D, 0, live, lane);
-                    ct_row_constants<HT, NH>(a, e, u1, v, lane);
+                    ct_row_constants<NH>(a, e, u1, v, lane);
+                    ct_dact_tile(h1.v[0], w.v[0], act);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        ct_dact_tile(h1.v[m], w.v[m], act);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) w.v[m][r] = w.v[m][r] * u1.v[m][r];
-                    }
-                    ct_gemm<HT, HT>(w, rr, cnf_smem + a.base_w[1] + lane * 4);
-                    ct_gemm<1, HT>(kb, hb2, cnf_smem + a.base_t[2] + lane * 4);
+                    for (int r = 0; r < 16; ++r) w.v[0][r] = w.v[0][r] * u1.v[0][r];
+                    cnf_gemm<1, 1>(w, rr, cnf_smem + a.base_w[1] + lane * 4);
+                    cnf_gemm<1, 1>(kb, hb2, cnf_smem + a.base_t[2] + lane * 4);
                     // dW3 += kb h2^T + e (qb d2 r)^T, db3 += kb
                     ct_put(sA, kb.v[0], lane);
                     gbl += ct_rowsum(sA, lane);
-#pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        ct_put(sB, h2.v[m], lane);
-                        ct_outer(gWl[m], sA, sB, lane);
-                    }
+                    ct_put(sB, h2.v[0], lane);
+                    ct_outer(gWl, sA, sB, lane);
                     ct_put(sA, e.v[0], lane);
+                    f32x16 pv, d2, s2;
+                    ct_dact_tile(h2.v[0], d2, act);
+                    ct_d2act_tile(h2.v[0], d2, s2, act);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        f32x16 pv, d2, s2;
-                        ct_dact_tile(h2.v[m], d2, act);
-                        ct_d2act_tile(h2.v[m], d2, s2, act);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            pv[r] = (qb * d2[r]) * rr.v[m][r];
-                            rb.v[m][r] = (qb * v.v[m][r]) * d2[r];
-                            a2.v[m][r] = hb2.v[m][r] * d2[r] + ((qb * s2[r]) * v.v[m][r]) * rr.v[m][r];
-                        }
-                        ct_put(sB, pv, lane);
-                        ct_outer(gWl[m], sA, sB, lane);
+                    for (int r = 0; r < 16; ++r) {
+                        pv[r] = (qb * d2[r]) * rr.v[0][r];
+                        rb.v[0][r] = (qb * v.v[0][r]) * d2[r];
+                        a2.v[0][r] = hb2.v[0][r] * d2[r] + ((qb * s2[r]) * v.v[0][r]) * rr.v[0][r];
                     }
+                    ct_put(sB, pv, lane);
+                    ct_outer(gWl, sA, sB, lane);
                     asm volatile("" ::: "memory");
                     // dW2 += a2b h1^T + rb w^T, db2 += a2b
-#pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        ct_put(sA, a2.v[m], lane);
-                        gb2[m] += ct_rowsum(sA, lane);
-#pragma unroll
-                        for (int n = 0; n < HT; ++n) {
-                            ct_put(sB, h1.v[n], lane);
-                            ct_outer(gW2[m * HT + n], sA, sB, lane);
-                        }
-                        ct_put(sA, rb.v[m], lane);
-#pragma unroll
-                        for (int n = 0; n < HT; ++n) {
-                            ct_put(sB, w.v[n], lane);
-                            ct_outer(gW2[m * HT + n], sA, sB, lane);
-                        }
-                    }
+                    ct_put(sA, a2.v[0], lane);
+                    gb2 += ct_rowsum(sA, lane);
+                    ct_put(sB, h1.v[0], lane);
+                    ct_outer(gW2, sA, sB, lane);
+                    ct_put(sA, rb.v[0], lane);
+                    ct_put(sB, w.v[0], lane);
+                    ct_outer(gW2, sA, sB, lane);
                     asm volatile("" ::: "memory");
-                    ct_gemm<HT, HT>(rb, wb, cnf_smem + a.base_t[1] + lane * 4);
-                    ct_gemm<HT, HT>(a2, hb1, cnf_smem + a.base_t[1] + lane * 4);
+                    cnf_gemm<1, 1>(rb, wb, cnf_smem + a.base_t[1] + lane * 4);
+                    cnf_gemm<1, 1>(a2, hb1, cnf_smem + a.base_t[1] + lane * 4);
+                    f32x16 d1, s1;
+                    ct_dact_tile(h1.v[0], d1, act);
+                    ct_d2act_tile(h1.v[0], d1, s1, act);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        f32x16 d1, s1;
-                        ct_dact_tile(h1.v[m], d1, act);
-                        ct_d2act_tile(h1.v[m], d1, s1, act);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            a1.v[m][r] = hb1.v[m][r] * d1[r] + (wb.v[m][r] * s1[r]) * u1.v[m][r];
-                            wb.v[m][r] = wb.v[m][r] * d1[r];          // (the adjoint of u1)
-                        }
+                    for (int r = 0; r < 16; ++r) {
+                        a1.v[0][r] = hb1.v[0][r] * d1[r] + (wb.v[0][r] * s1[r]) * u1.v[0][r];
+                        wb.v[0][r] = wb.v[0][r] * d1[r];          // (the adjoint of u1)
                     }
                     // the u1 adjoint's share of dW1x: (wb d1) e^T
                     ct_take(e.v[0], sE, D, 0, live, lane);
                     ct_put(sB, e.v[0], lane);
-#pragma unroll
-                    for (int m = 0; m < HT; ++m) {
-                        ct_put(sA, wb.v[m], lane);
-                        ct_outer(gW1[m], sA, sB, lane);
-                    }
+                    ct_put(sA, wb.v[0], lane);
+                    ct_outer(gW1, sA, sB, lane);
                 }
                 // dW1x += a1b z^T, db1 += a1b, the time column += t a1b, and sum a1b for the latent columns
                 ct_put(sB, z.v[0], lane);
+                ct_put(sA, a1.v[0], lane);
+                const float s = ct_rowsum(sA, lane);
+                gb1 += s;
+                gtc += t * s;
+                ct_outer(gW1, sA, sB, lane);
 #pragma unroll
-                for (int m = 0; m < HT; ++m) {
-                    ct_put(sA, a1.v[m], lane);
-                    const float s = ct_rowsum(sA, lane);
-                    gb1[m] += s;
-                    gtc[m] += t * s;
-                    ct_outer(gW1[m], sA, sB, lane);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sL[m * 1024 + r * 64] += a1.v[m][r];
-                }
+                for (int r = 0; r < 16; ++r) sL[r * 64] += a1.v[0][r];
                 asm volatile("" ::: "memory");
-                ct_gemm<HT, 1>(a1, zbar, cnf_smem + a.base_t[0] + lane * 4);
+                cnf_gemm<1, 1>(a1, zbar, cnf_smem + a.base_t[0] + lane * 4);
 
                 if (SOLVER == SX_CNF_EULER || st == 0) {
 #pragma unroll
@@ -683,25 +489,21 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
 
         if (L > 0) {
             const float *W1 = net.layer[0].W;
-            cnf_tile<HT> A1;
+            f32x16 A1;
 #pragma unroll
-            for (int m = 0; m < HT; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) A1.v[m][r] = sL[m * 1024 + r * 64];
+            for (int r = 0; r < 16; ++r) A1[r] = sL[r * 64];
             // g_latent = W1[:, latent]^T A1 (A fragments straight from global memory: once per group), gathered in LDS as rows
             if (a.glat != nullptr) {
                 for (int c = 0; c < LT; ++c) {
                     f32x16 g = {};
                     const int lc = 32 * c + (lane & 31);
 #pragma unroll
-                    for (int m = 0; m < HT; ++m)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) {
-                            const int j = 32 * m + cnf_kmap(q, h);
-                            const float t = W1[(int64_t)(j < H1 ? j : 0) * in_dim + 1 + D + (lc < L ? lc : 0)];
-                            const float av = (lc < L && j < H1) ? t : 0.f;
-                            g = __builtin_amdgcn_mfma_f32_32x32x2f32(av, A1.v[m][q], g, 0, 0, 0);
-                        }
+                    for (int q = 0; q < 16; ++q) {
+                        const int j = cnf_kmap(q, h);
+                        const float t = W1[(int64_t)(j < H1 ? j : 0) * in_dim + 1 + D + (lc < L ? lc : 0)];
+                        const float av = (lc < L && j < H1) ? t : 0.f;
+                        g = __builtin_amdgcn_mfma_f32_32x32x2f32(av, A1[q], g, 0, 0, 0);
+                    }
                     ct_give(zb, g, L, 32 * c, 2048, lane);
                 }
                 ct_flush(a.glat, zb, row0, n_live, L, lane);
@@ -709,43 +511,31 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
             // the latent columns of dW1 += A1 latent^T, into the wave's own partial
             ct_fetch(zb, a.latent, row0, n_live, L, lane);
             for (int c = 0; c < LT; ++c) {
-                f32x16 lt;
+                f32x16 lt, acc;
                 ct_take(lt, zb, L, 32 * c, live, lane);
                 ct_put(sB, lt, lane);
+                float *p = part + a.off_lat + c * 1024 + lane;
 #pragma unroll
-                for (int m = 0; m < HT; ++m) {
-                    float *p = part + a.off_lat + (m * LT + c) * 1024 + lane;
-                    f32x16 acc;
+                for (int r = 0; r < 16; ++r) acc[r] = p[r * 64];
+                ct_put(sA, A1, lane);
+                ct_outer(acc, sA, sB, lane);
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = p[r * 64];
-                    ct_put(sA, A1.v[m], lane);
-                    ct_outer(acc, sA, sB, lane);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) p[r * 64] = acc[r];
-                }
+                for (int r = 0; r < 16; ++r) p[r * 64] = acc[r];
             }
         }
     }
 
-    // one partial per wave
+    // one partial per wave: dW1x, dW_last (and dW2), then db1, the time column, db2 and db_last, 64 floats each
 #pragma unroll
-    for (int m = 0; m < HT; ++m) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            part[m * 1024 + r * 64 + lane] = gW1[m][r];
-            part[a.off_wl + m * 1024 + r * 64 + lane] = gWl[m][r];
-        }
-        part[a.off_vec + m * 64 + lane] = gb1[m];
-        part[a.off_vec + (HT + m) * 64 + lane] = gtc[m];
-        part[a.off_vec + (2 * HT + m) * 64 + lane] = gb2[m];
+    for (int r = 0; r < 16; ++r) {
+        part[r * 64 + lane] = gW1[r];
+        part[a.off_wl + r * 64 + lane] = gWl[r];
+        if constexpr (NH == 2) part[a.off_w2 + r * 64 + lane] = gW2[r];
     }
-    part[a.off_vec + 3 * HT * 64 + lane] = gbl;
-    if constexpr (NH == 2) {
-#pragma unroll
-        for (int m = 0; m < HT * HT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) part[a.off_w2 + m * 1024 + r * 64 + lane] = gW2[m][r];
-    }
+    part[a.off_vec + lane] = gb1;
+    part[a.off_vec + 64 + lane] = gtc;
+    part[a.off_vec + 128 + lane] = gb2;
+    part[a.off_vec + 192 + lane] = gbl;
     // the slots of the workgroups the launcher did not start hold zeros
     for (int64_t vb = (int64_t)blockIdx.x + gridDim.x; vb < a.n_virtual; vb += gridDim.x) {
         float *p = a.partial + (vb * SX_CNF_WAVES + wave) * a.part_floats;
@@ -757,7 +547,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
 struct ct_reduce_args {
     const float *partial;
     float *dW[3], *db[3];
-    int n_slots, part_floats, NH, HT, LT, D, L, H1, H2;
+    int n_slots, part_floats, NH, D, L, H1, H2;
     int off_w2, off_wl, off_lat, off_vec;
 };
 
@@ -773,21 +563,21 @@ __global__ void cnf_train_reduce_kernel(const ct_reduce_args a) {
     if (i < n0) {
         const int j = i / in_dim, c = i - j * in_dim;
         dst = a.dW[0];
-        if (c == 0) { off = a.off_vec + (a.HT + (j >> 5)) * 64 + (j & 31); pair = 1; }
-        else if (c <= a.D) off = (j >> 5) * 1024 + ct_tile_off(j & 31, c - 1);
-        else off = a.off_lat + ((j >> 5) * a.LT + ((c - 1 - a.D) >> 5)) * 1024 + ct_tile_off(j & 31, (c - 1 - a.D) & 31);
+        if (c == 0) { off = a.off_vec + 64 + j; pair = 1; }
+        else if (c <= a.D) off = ct_tile_off(j, c - 1);
+        else off = a.off_lat + ((c - 1 - a.D) >> 5) * 1024 + ct_tile_off(j, (c - 1 - a.D) & 31);
     } else if ((i -= n0) < n1) {
-        dst = a.db[0]; off = a.off_vec + (i >> 5) * 64 + (i & 31); pair = 1;
+        dst = a.db[0]; off = a.off_vec + i; pair = 1;
     } else if ((i -= n1) < n2) {
         const int k = i / a.H1, j = i - k * a.H1;
-        dst = a.dW[1]; off = a.off_w2 + ((k >> 5) * a.HT + (j >> 5)) * 1024 + ct_tile_off(k & 31, j & 31);
+        dst = a.dW[1]; off = a.off_w2 + ct_tile_off(k, j);
     } else if ((i -= n2) < n3) {
-        dst = a.db[1]; off = a.off_vec + (2 * a.HT + (i >> 5)) * 64 + (i & 31); pair = 1;
+        dst = a.db[1]; off = a.off_vec + 128 + i; pair = 1;
     } else if ((i -= n3) < n4) {
         const int d = i / Hl, j = i - d * Hl;
-        dst = a.dW[a.NH]; off = a.off_wl + (j >> 5) * 1024 + ct_tile_off(d, j & 31);
+        dst = a.dW[a.NH]; off = a.off_wl + ct_tile_off(d, j);
     } else if ((i -= n4) < n5) {
-        dst = a.db[a.NH]; off = a.off_vec + 3 * a.HT * 64 + i; pair = 1;
+        dst = a.db[a.NH]; off = a.off_vec + 192 + i; pair = 1;
     } else return;
     if (dst == nullptr) return;
     float s = 0.f;
@@ -798,57 +588,25 @@ __global__ void cnf_train_reduce_kernel(const ct_reduce_args a) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 int ct_check_net(const sx_cnf_net *net_host) {
-    SX_REQUIRE(net_host != nullptr, "sx_cnf_train: null network");
-    const sx_cnf_net &net = *net_host;
-    SX_REQUIRE(net.n_layers == 2 || net.n_layers == 3, "sx_cnf_train: one or two hidden layers (got %d Linear layers)", net.n_layers);
-    SX_REQUIRE(net.dim >= 1 && net.dim <= SX_CNF_TRAIN_MAX_DIM, "sx_cnf_train: dim must be in 1..%d (got %d)", SX_CNF_TRAIN_MAX_DIM, net.dim);
-    SX_REQUIRE(net.latent_dim >= 0 && 1 + net.dim + net.latent_dim <= SX_CNF_TRAIN_MAX_IN, "sx_cnf_train: 1 + dim + latent_dim must be <= %d",
-               SX_CNF_TRAIN_MAX_IN);
-    SX_REQUIRE(net.act >= SX_ACT_IDENTITY && net.act <= SX_ACT_LEAKYRELU, "sx_cnf_train: activation %d has no in-kernel derivatives", net.act);
-    for (int l = 0; l < net.n_layers; ++l) {
-        const sx_cnf_layer &L = net.layer[l];
-        SX_REQUIRE(L.W != nullptr, "sx_cnf_train: layer %d has no weight", l);
-        SX_REQUIRE(L.in_dim == (l == 0 ? 1 + net.dim + net.latent_dim : net.layer[l - 1].out_dim), "sx_cnf_train: layer %d input width", l);
-        SX_REQUIRE(L.out_dim >= 1 && L.out_dim <= SX_CNF_TRAIN_MAX_HIDDEN, "sx_cnf_train: layer %d width must be in 1..%d", l, SX_CNF_TRAIN_MAX_HIDDEN);
-    }
-    SX_REQUIRE(net.layer[net.n_layers - 1].out_dim == net.dim, "sx_cnf_train: the last layer must map back to dim");
-    return SX_OK;
+    return cnf_dense_check_net("sx_cnf_train", net_host, SX_CNF_TRAIN_MAX_DIM, SX_CNF_TRAIN_MAX_IN, SX_CNF_TRAIN_MAX_HIDDEN);
 }
 
-int ct_hidden_tiles(const sx_cnf_net &net) {
-    int HT = 1;
-    for (int l = 0; l + 1 < net.n_layers; ++l) HT = cnf_tiles(net.layer[l].out_dim) > HT ? cnf_tiles(net.layer[l].out_dim) : HT;
-    return HT;
-}
-
-// the LDS plan (floats) and the layout of a wave's partial
-size_t ct_plan(const sx_cnf_net &net, bool backward, ct_args *a) {
-    const int NH = net.n_layers - 1, HT = ct_hidden_tiles(net), LT = (net.latent_dim + 31) >> 5;
-    size_t off = 0;
-    int bw[3] = {0, 0, 0}, bb[3] = {0, 0, 0}, bt[3] = {0, 0, 0};
-    for (int l = 0; l <= NH; ++l) {
-        const int KT = l == 0 ? 1 : HT, MT = l == NH ? 1 : HT;
-        bw[l] = (int)off; off += (size_t)MT * KT * 1024;
-        bb[l] = (int)off; off += (size_t)MT * 32;
-    }
-    const int base_w0 = (int)off; off += (size_t)HT * 32;
-    bt[NH] = (int)off; off += (size_t)HT * 1024;
-    int base_scr = 0, scr_stride = 0;
+// the LDS plan (floats): the forward images, the transposed ones, the waves' scratch; and the layout of a wave's partial
+size_t ct_plan(const sx_cnf_net &net, bool backward, ct_args &a) {
+    const int NH = net.n_layers - 1, LT = (net.latent_dim + 31) >> 5;
+    size_t off = cnf_dense_plan(net, a);
+    a.base_t[NH] = (int)off; off += 1024;
     if (backward) {
-        bt[0] = (int)off; off += (size_t)HT * 1024;
-        if (NH == 2) { bt[1] = (int)off; off += (size_t)HT * HT * 1024; }
-        base_scr = (int)off; scr_stride = 3 * CT_SLOT + 4 * 1024 + HT * 1024;
-        off += (size_t)SX_CNF_WAVES * scr_stride;
+        a.base_t[0] = (int)off; off += 1024;
+        if (NH == 2) { a.base_t[1] = (int)off; off += 1024; }
+        a.base_scr = (int)off; a.scr_stride = 3 * CT_SLOT + 5 * 1024;
+        off += (size_t)SX_CNF_WAVES * a.scr_stride;
     }
-    if (a) {
-        for (int l = 0; l < 3; ++l) { a->base_w[l] = bw[l]; a->base_b[l] = bb[l]; a->base_t[l] = bt[l]; }
-        a->base_w0 = base_w0; a->base_scr = base_scr; a->scr_stride = scr_stride;
-        a->off_w2 = HT * 1024;
-        a->off_wl = a->off_w2 + (NH == 2 ? HT * HT * 1024 : 0);
-        a->off_lat = a->off_wl + HT * 1024;
-        a->off_vec = a->off_lat + HT * LT * 1024;
-        a->part_floats = a->off_vec + (3 * HT + 1) * 64;
-    }
+    a.off_w2 = 1024;
+    a.off_wl = a.off_w2 + (NH == 2 ? 1024 : 0);
+    a.off_lat = a.off_wl + 1024;
+    a.off_vec = a.off_lat + LT * 1024;
+    a.part_floats = a.off_vec + 4 * 64;
     return off;
 }
 
@@ -861,14 +619,15 @@ int64_t ct_virtual_blocks(int64_t n_rows) {
 
 extern "C" size_t sx_cnf_train_lds_bytes(const sx_cnf_net *net_host, int32_t backward) {
     if (ct_check_net(net_host) != SX_OK) return 0;
-    const size_t bytes = ct_plan(*net_host, backward != 0, nullptr) * 4;
+    ct_args a{};
+    const size_t bytes = ct_plan(*net_host, backward != 0, a) * 4;
     return bytes <= SX_CNF_LDS_BYTES ? bytes : 0;
 }
 
 extern "C" int64_t sx_cnf_train_partial_floats(const sx_cnf_net *net_host, int64_t n_rows) {
     if (ct_check_net(net_host) != SX_OK || n_rows < 0) return 0;
     ct_args a{};
-    ct_plan(*net_host, true, &a);
+    ct_plan(*net_host, true, a);
     const int64_t blocks = ct_virtual_blocks(n_rows);
     return (blocks < 1 ? 1 : blocks) * SX_CNF_WAVES * a.part_floats;
 }
@@ -885,17 +644,14 @@ extern "C" int sx_cnf_train_fwd(const sx_cnf_net *net_host, const float *x, cons
     SX_REQUIRE(e != nullptr && ldj != nullptr, "sx_cnf_train_fwd: null noise / ldj");
     ct_args a{};
     a.net = net;
-    const size_t lds = ct_plan(net, false, &a) * 4;
+    const size_t lds = ct_plan(net, false, a) * 4;
     SX_REQUIRE(lds <= SX_CNF_LDS_BYTES, "sx_cnf_train_fwd: the padded weights need %zu bytes of LDS (budget %d)", lds, SX_CNF_LDS_BYTES);
     if (n_rows == 0) return SX_OK;
     a.x = x; a.latent = latent; a.e = e; a.y = y; a.ldj = ldj; a.ckpt = checkpoints; a.n_rows = n_rows;
     a.solver = solver; a.n_steps = n_steps; a.t0 = t0; a.t1 = t1; a.step_size = step_size;
-    const int NH = net.n_layers - 1, HT = ct_hidden_tiles(net);
     const int64_t want = cnf_row_blocks(n_rows);
-    // (one hidden tile only: see sx_cnf_train_bwd)
-    SX_REQUIRE(HT == 1, "sx_cnf_train_fwd: no kernel for %d hidden tiles", HT);
-    if (NH == 1) return cnf_launch<cnf_train_fwd_kernel<1, 1>>("sx_cnf_train_fwd", a, lds, want, stream);
-    return cnf_launch<cnf_train_fwd_kernel<1, 2>>("sx_cnf_train_fwd", a, lds, want, stream);
+    if (net.n_layers == 2) return cnf_launch<cnf_train_fwd_kernel<1>>("sx_cnf_train_fwd", a, lds, want, stream);
+    return cnf_launch<cnf_train_fwd_kernel<2>>("sx_cnf_train_fwd", a, lds, want, stream);
 }
 
 extern "C" int sx_cnf_train_bwd(const sx_cnf_net *net_host, const float *checkpoints, const float *latent, const float *e, const float *gy,
@@ -912,14 +668,14 @@ extern "C" int sx_cnf_train_bwd(const sx_cnf_net *net_host, const float *checkpo
     SX_REQUIRE(n_rows == 0 || partial != nullptr, "sx_cnf_train_bwd: the partial buffer is missing (sx_cnf_train_partial_floats)");
     ct_args a{};
     a.net = net;
-    const size_t lds = ct_plan(net, true, &a) * 4;
+    const size_t lds = ct_plan(net, true, a) * 4;
     SX_REQUIRE(lds <= SX_CNF_LDS_BYTES, "sx_cnf_train_bwd: the images and scratch need %zu bytes of LDS (budget %d)", lds, SX_CNF_LDS_BYTES);
-    const int NH = net.n_layers - 1, HT = ct_hidden_tiles(net);
+    const int NH = net.n_layers - 1;
     const int64_t blocks = ct_virtual_blocks(n_rows);
     ct_reduce_args r{};
     r.partial = partial; r.n_slots = (int)(blocks * SX_CNF_WAVES); r.part_floats = a.part_floats;
     for (int l = 0; l < 3; ++l) { r.dW[l] = grads->dW[l]; r.db[l] = grads->db[l]; }
-    r.NH = NH; r.HT = HT; r.LT = (net.latent_dim + 31) >> 5; r.D = net.dim; r.L = net.latent_dim;
+    r.NH = NH; r.D = net.dim; r.L = net.latent_dim;
     r.H1 = net.layer[0].out_dim; r.H2 = net.layer[1].out_dim;
     r.off_w2 = a.off_w2; r.off_wl = a.off_wl; r.off_lat = a.off_lat; r.off_vec = a.off_vec;
     if (n_rows > 0) {
@@ -930,12 +686,12 @@ extern "C" int sx_cnf_train_bwd(const sx_cnf_net *net_host, const float *checkpo
         // The solver is a template argument: with a run-time tableau the adjoint sweep does not fit the register file.  Hidden layers
         // of two tiles (33..64 units) are not built: their sweep needs 216 .. 1308 bytes of scratch per lane and more LDS than a
         // workgroup has, so those networks train on the composition path (SX_CNF_TRAIN_MAX_HIDDEN).
-#define CT_CASE(H_, N_)                                                                                                                 \
-    if (HT == H_ && NH == N_)                                                                                                           \
-        rcl = solver == SX_CNF_EULER      ? cnf_launch<cnf_train_bwd_kernel<H_, N_, SX_CNF_EULER>>("sx_cnf_train_bwd", a, lds, blocks, stream)    \
-              : solver == SX_CNF_MIDPOINT ? cnf_launch<cnf_train_bwd_kernel<H_, N_, SX_CNF_MIDPOINT>>("sx_cnf_train_bwd", a, lds, blocks, stream) \
-                                          : cnf_launch<cnf_train_bwd_kernel<H_, N_, SX_CNF_RK4>>("sx_cnf_train_bwd", a, lds, blocks, stream);
-        CT_CASE(1, 1) CT_CASE(1, 2)
+#define CT_CASE(N_)                                                                                                                 \
+    if (NH == N_)                                                                                                                   \
+        rcl = solver == SX_CNF_EULER      ? cnf_launch<cnf_train_bwd_kernel<N_, SX_CNF_EULER>>("sx_cnf_train_bwd", a, lds, blocks, stream)    \
+              : solver == SX_CNF_MIDPOINT ? cnf_launch<cnf_train_bwd_kernel<N_, SX_CNF_MIDPOINT>>("sx_cnf_train_bwd", a, lds, blocks, stream) \
+                                          : cnf_launch<cnf_train_bwd_kernel<N_, SX_CNF_RK4>>("sx_cnf_train_bwd", a, lds, blocks, stream);
+        CT_CASE(1) CT_CASE(2)
 #undef CT_CASE
         if (rcl != SX_OK) return rcl;
     }

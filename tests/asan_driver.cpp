@@ -13,7 +13,10 @@
 //   3. a seeded random fuzz of whole sx_program structs through the validators (no launch: n_rows = 0 for sx_flow_run).
 //   4. the four CNF families (sx_cnf_*, sx_cnf_exact_*, sx_cnf_set_*, sx_cnf_exact_set_*): every range check of the network
 //      validators through both the LDS query (0) and the flow call (a status and a message), the per-call argument checks of the flow
-//      calls, and a valid network with n_rows = 0 (returns after every check, before any launch).
+//      calls, and a valid network with n_rows = 0 (returns after every check, before any launch); and the training pair of the
+//      dense family (sx_cnf_train_*), which shares the dense network validator: the same edges at its own limits through both
+//      queries and both calls, the per-call checks, and the forward with n_rows = 0 (the backward is only driven into its refusals:
+//      with valid arguments it launches its partial sum even for no rows).
 // GPU AddressSanitizer does not exist on this pool: this job covers the host side only (sanitizer row).
 #include "../include/stribor_hip.h"
 #include <limits.h>
@@ -223,6 +226,79 @@ static void drive_cnf() {
     n = ok1; n.trace = nullptr;
     EXPECT_BAD(cnf_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, g_cnf_buf, 0, SX_CNF_RK4, 1, 0.f, 1));      // want_ldj without the trace constants
     EXPECT_OK(cnf_flow(&n, g_cnf_buf, g_cnf_buf, g_cnf_buf, nullptr, 0, SX_CNF_RK4, 1, 0.f, 0));
+}
+
+// training of the dense family: the same sx_cnf_net inside SX_CNF_TRAIN_MAX_*; `trace` is not read
+static int cnft_fwd(const sx_cnf_net *n, const float *x, const float *lat, const float *e, float *y, float *ldj, int64_t rows, int solver,
+                    int steps, float step) {
+    return sx_cnf_train_fwd(n, x, lat, e, y, ldj, nullptr, rows, solver, steps, 0.f, 1.f, step, nullptr);
+}
+static int cnft_bwd(const sx_cnf_net *n, const float *lat, const float *e, const float *gy, const float *gldj, float *gx,
+                    const sx_cnf_train_grads *g, int64_t rows, int solver, int steps, float step) {
+    return sx_cnf_train_bwd(n, g_cnf_buf, lat, e, gy, gldj, gx, g_cnf_buf, g_cnf_buf, g, rows, solver, steps, 0.f, 1.f, step, nullptr);
+}
+static void cnft_bad_net(const sx_cnf_net &n) {
+    sx_cnf_train_grads g;
+    memset(&g, 0, sizeof(g));
+    float *b = g_cnf_buf;
+    EXPECT_TRUE(sx_cnf_train_lds_bytes(&n, 0) == 0 && sx_cnf_train_lds_bytes(&n, 1) == 0 && sx_cnf_train_partial_floats(&n, 0) == 0);
+    EXPECT_BAD(cnft_fwd(&n, b, b, b, b, b, 0, SX_CNF_RK4, 1, 0.f));
+    EXPECT_BAD(cnft_bwd(&n, b, b, b, b, b, &g, 0, SX_CNF_RK4, 1, 0.f));
+}
+static void drive_cnf_train() {
+    const sx_cnf_net ok1 = cnf_net(3, 2, 8, 0), ok2 = cnf_net(5, 58, 32, 32);
+    sx_cnf_net n;
+    sx_cnf_train_grads g;
+    memset(&g, 0, sizeof(g));
+    float *b = g_cnf_buf;
+    EXPECT_TRUE(sx_cnf_train_lds_bytes(nullptr, 1) == 0 && sx_cnf_train_partial_floats(nullptr, 0) == 0);
+    EXPECT_BAD(cnft_fwd(nullptr, b, b, b, b, b, 0, SX_CNF_RK4, 1, 0.f));
+    EXPECT_BAD(cnft_bwd(nullptr, b, b, b, b, b, &g, 0, SX_CNF_RK4, 1, 0.f));
+    n = ok1; n.n_layers = 1; cnft_bad_net(n);
+    n = ok2; n.n_layers = 4; cnft_bad_net(n);
+    n = ok1; n.dim = 0; cnft_bad_net(n);
+    n = cnf_net(SX_CNF_TRAIN_MAX_DIM + 1, 0, 8, 0); cnft_bad_net(n);
+    n = cnf_net(3, 0, SX_CNF_TRAIN_MAX_HIDDEN + 1, 0); cnft_bad_net(n);
+    n = cnf_net(3, 0, 8, SX_CNF_TRAIN_MAX_HIDDEN + 1); cnft_bad_net(n);
+    n = ok1; n.latent_dim = -1; cnft_bad_net(n);
+    n = cnf_net(5, SX_CNF_TRAIN_MAX_IN - 5, 8, 0); cnft_bad_net(n);             // 1 + dim + latent_dim = 65
+    n = ok1; n.act = -1; cnft_bad_net(n);
+    n = ok1; n.act = SX_ACT_SILU; cnft_bad_net(n);
+    n = ok2; n.layer[2].W = nullptr; cnft_bad_net(n);
+    n = ok1; n.layer[0].in_dim = 5; cnft_bad_net(n);                            // layer widths that do not chain
+    n = ok2; n.layer[2].in_dim = 8; cnft_bad_net(n);
+    n = ok1; n.layer[1].out_dim = 4; cnft_bad_net(n);                           // the last layer maps back to dim
+    EXPECT_TRUE(sx_cnf_train_lds_bytes(&ok1, 0) != 0 && sx_cnf_train_lds_bytes(&ok1, 1) > sx_cnf_train_lds_bytes(&ok1, 0));
+    EXPECT_TRUE(sx_cnf_train_lds_bytes(&ok2, 1) != 0 && sx_cnf_train_lds_bytes(&ok2, 1) <= SX_CNF_LDS_BYTES);
+    EXPECT_TRUE(sx_cnf_train_partial_floats(&ok2, -1) == 0 && sx_cnf_train_partial_floats(&ok2, 0) > 0 &&
+                sx_cnf_train_partial_floats(&ok2, 130) == 2 * sx_cnf_train_partial_floats(&ok2, 128));
+    const sx_cnf_net *nets[2] = {&ok1, &ok2};
+    for (int i = 0; i < 2; ++i) {
+        const sx_cnf_net *net = nets[i];
+        EXPECT_BAD(cnft_fwd(net, b, b, b, b, b, 0, -1, 1, 0.f));                            /* solver */
+        EXPECT_BAD(cnft_fwd(net, b, b, b, b, b, 0, SX_CNF_RK4 + 1, 1, 0.f));
+        EXPECT_BAD(cnft_fwd(net, b, b, b, b, b, -1, SX_CNF_RK4, 1, 0.f));                   /* n_rows < 0 */
+        EXPECT_BAD(cnft_fwd(net, b, b, b, b, b, 0, SX_CNF_RK4, -1, 0.f));                   /* n_steps < 0 */
+        EXPECT_BAD(cnft_fwd(net, b, b, b, b, b, 0, SX_CNF_EULER, 2, 0.f));                  /* a grid without a step */
+        EXPECT_BAD(cnft_fwd(net, nullptr, b, b, b, b, 0, SX_CNF_MIDPOINT, 1, 0.f));         /* null x */
+        EXPECT_BAD(cnft_fwd(net, b, b, b, nullptr, b, 0, SX_CNF_MIDPOINT, 1, 0.f));         /* null y */
+        EXPECT_BAD(cnft_fwd(net, b, nullptr, b, b, b, 0, SX_CNF_MIDPOINT, 1, 0.f));         /* latent rows missing */
+        EXPECT_BAD(cnft_fwd(net, b, b, nullptr, b, b, 0, SX_CNF_MIDPOINT, 1, 0.f));         /* null noise */
+        EXPECT_BAD(cnft_fwd(net, b, b, b, b, nullptr, 0, SX_CNF_MIDPOINT, 1, 0.f));         /* null ldj */
+        EXPECT_OK(cnft_fwd(net, b, b, b, b, b, 0, SX_CNF_EULER, 0, 0.f));
+        EXPECT_OK(cnft_fwd(net, b, b, b, b, b, 0, SX_CNF_RK4, 3, 0.3f));
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, b, &g, 0, -1, 1, 0.f));                        /* solver */
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, b, &g, 0, SX_CNF_RK4 + 1, 1, 0.f));
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, b, &g, -1, SX_CNF_RK4, 1, 0.f));               /* n_rows < 0 */
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, b, &g, 0, SX_CNF_RK4, -1, 0.f));               /* n_steps < 0 */
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, b, &g, 0, SX_CNF_EULER, 2, 0.f));              /* a grid without a step */
+        EXPECT_BAD(cnft_bwd(net, b, b, nullptr, b, b, &g, 0, SX_CNF_MIDPOINT, 1, 0.f));     /* null gy */
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, nullptr, &g, 0, SX_CNF_MIDPOINT, 1, 0.f));     /* null gx */
+        EXPECT_BAD(cnft_bwd(net, nullptr, b, b, b, b, &g, 0, SX_CNF_MIDPOINT, 1, 0.f));     /* latent rows missing */
+        EXPECT_BAD(cnft_bwd(net, b, nullptr, b, b, b, &g, 0, SX_CNF_MIDPOINT, 1, 0.f));     /* null noise */
+        EXPECT_BAD(cnft_bwd(net, b, b, b, nullptr, b, &g, 0, SX_CNF_MIDPOINT, 1, 0.f));     /* null gldj */
+        EXPECT_BAD(cnft_bwd(net, b, b, b, b, b, nullptr, 0, SX_CNF_MIDPOINT, 1, 0.f));      /* null grads */
+    }
 }
 
 // exact trace: two MADEs + the dimwise net; the image's size comes from the library's own query
@@ -594,6 +670,7 @@ int main() {
 
     // ---- 4. the CNF families: network validators, per-call checks, n_rows = 0 -------------------------------------------------------
     drive_cnf();
+    drive_cnf_train();
     drive_cnf_exact();
     drive_cnf_set();
     drive_cnf_exact_set();

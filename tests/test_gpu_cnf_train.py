@@ -68,10 +68,11 @@ def test_rademacher_noise():
     assert set(f.odefunc._e.unique().tolist()) <= {-1.0, 1.0}
 
 
-@pytest.mark.parametrize('net', [(3, [5], 0), (5, [32, 32], 58)])
-def test_forward_value_is_the_eval_kernels(net):
+@pytest.mark.parametrize('solver', ['euler', 'midpoint', 'rk4'])
+@pytest.mark.parametrize('net', [(3, [5], 0), (6, [32, 24], 2), (5, [32, 32], 58)])
+def test_forward_value_is_the_eval_kernels(net, solver):
     dim, hidden, latent = net
-    f = th.make(dim, hidden, latent, seed=8).to(DEV)
+    f = th.make(dim, hidden, latent, solver=solver, seed=8).to(DEV)
     x = torch.randn(130, dim, device=DEV)
     lat = torch.randn(130, latent, device=DEV) if latent else None
     y = f(x, latent=lat)
