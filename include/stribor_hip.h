@@ -311,6 +311,38 @@ int sx_absmax2(const float *a, int64_t na, const float *b, int64_t nb, float *ou
 int sx_unit_normal_logprob(const void *x, const float *ldj, float *out, int64_t n_rows, int32_t dim,
                            int32_t dtype, void *stream);
 
+/* Normal(loc, scale) / Uniform(low, high) with vector parameters of the row's width (stribor/dist/normal.py:8-37,
+ * dist/uniform.py:8-36: Independent(td.Normal | td.Uniform, 1)) + log-det accumulator (flow.py:128-129).  p0, p1 fp32 [dim]:
+ *   SX_BASE_NORMAL   p0 = loc, p1 = 1 / scale:  out[n] = -sum_d ((x[n,d] - loc_d) p1_d)^2 / 2 + log_norm + (ldj ? ldj[n] : 0)
+ *   SX_BASE_UNIFORM  p0 = low, p1 = high:       out[n] = (all d: low_d <= x[n,d] < high_d ? log_norm : -inf) + (ldj ? ldj[n] : 0);
+ *                    a NaN in a row gives NaN in that row
+ * log_norm: the caller's fp64 constant rounded once, -sum log scale - dim log sqrt(2 pi), respectively -sum log(high - low).
+ * One pass over x; any dim >= 1 and any alignment of x. */
+#define SX_BASE_NORMAL  0
+#define SX_BASE_UNIFORM 1
+int sx_base_logprob(const void *x, const float *p0, const float *p1, float log_norm, const float *ldj, float *out,
+                    int64_t n_rows, int32_t dim, int32_t dtype, int32_t kind, void *stream);
+
+/* Backward of SX_BASE_NORMAL (autograd through stribor/dist/normal.py:37) from g[n] = dL/dout[n], x fp32 [n_rows, dim]:
+ *   gx[n,d] = -g_n (x - loc) / scale^2,  g_loc[d] = sum_n g_n (x - loc) / scale^2,  g_scale[d] = sum_n g_n ((x - loc)^2 / scale^3 - 1 / scale)
+ * each output nullable.  No [n_rows, dim] temporary and no atomics: per-block column sums go to `partial`
+ * (>= the floats the size function below returns for these sizes; needed iff g_loc or g_scale is wanted) and are added in slot
+ * order -- two calls on the same inputs return the same bits.  dL/dldj is the identity and needs no kernel. */
+size_t sx_normal_bwd_partial_floats(int64_t n_rows, int32_t dim);
+int sx_normal_logprob_bwd(const float *x, const float *g, const float *loc, const float *inv_scale, float *gx, float *g_loc,
+                          float *g_scale, float *partial, int64_t n_rows, int32_t dim, void *stream);
+
+/* MultivariateNormal(loc, scale_tril = L) (stribor/dist/normal.py:57-68) + log-det accumulator: linv = L^-1 [dim, dim] row-major
+ * fp32 (lower triangular; entries above the diagonal are not read), z = linv (x - loc),
+ *   out[n] = -|z|^2 / 2 + log_norm + (ldj ? ldj[n] : 0),  log_norm = -sum log L_ii - dim log sqrt(2 pi).
+ * Exact fp32 (v_mfma_f32_32x32x2_f32) in every set_gemm_precision mode; one wave owns 32 rows, the lower 32 x 32 tiles of linv
+ * are staged in LDS once per workgroup (the LDS size function below gives the bytes; 0 beyond SX_MVN_MAX_DIM) and z never
+ * reaches HBM.  x: SX_F32 or SX_BF16 rows, any alignment. */
+#define SX_MVN_MAX_DIM 128
+size_t sx_mvn_lds_bytes(int32_t dim);
+int sx_mvn_logprob(const void *x, const float *loc, const float *linv, float log_norm, const float *ldj, float *out,
+                   int64_t n_rows, int32_t dim, int32_t dtype, void *stream);
+
 /* sum of an fp32 vector into ONE fp64 (block partials in fp64, one atomic per block);
  * `*out` must be zeroed by the caller (or hold a running total). */
 int sx_sum_f64(const float *v, int64_t n, double *out, void *stream);

@@ -62,7 +62,12 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
            'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
            'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow',
-           'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd']
+           'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd',
+           'sx_base_logprob', 'sx_normal_bwd_partial_floats', 'sx_normal_logprob_bwd', 'sx_mvn_lds_bytes', 'sx_mvn_logprob']
+
+# base densities (include/stribor_hip.h: sx_base_logprob / sx_mvn_logprob)
+BASE_NORMAL, BASE_UNIFORM = 0, 1
+MVN_MAX_DIM = 128
 
 # invertible ResNet flows (include/stribor_hip.h: sx_resnet_flow / sx_spectral_sigma)
 RESNET_MAX_LAYERS = 4
@@ -238,6 +243,16 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_unit_normal_logprob.argtypes = [vp, vp, vp, i64, i32, i32, vp]
     lib.sx_sum_f64.restype = i32
     lib.sx_sum_f64.argtypes = [vp, i64, vp, vp]
+    lib.sx_base_logprob.restype = i32
+    lib.sx_base_logprob.argtypes = [vp, vp, vp, f32, vp, vp, i64, i32, i32, i32, vp]
+    lib.sx_normal_bwd_partial_floats.restype = C.c_size_t
+    lib.sx_normal_bwd_partial_floats.argtypes = [i64, i32]
+    lib.sx_normal_logprob_bwd.restype = i32
+    lib.sx_normal_logprob_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]
+    lib.sx_mvn_lds_bytes.restype = C.c_size_t
+    lib.sx_mvn_lds_bytes.argtypes = [i32]
+    lib.sx_mvn_logprob.restype = i32
+    lib.sx_mvn_logprob.argtypes = [vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.sx_packed_linear_floats.restype = C.c_size_t
     lib.sx_packed_linear_floats.argtypes = [i32, i32]
     lib.sx_pack_linear.restype = i32

@@ -419,7 +419,17 @@ class NormalizingFlow(Transform):
         key = (reverse, dim, latent_dim, str(device), t_kind)
         return self._cached(key, lambda: self._build_fused(reverse, dim, latent_dim, device, t_kind))
 
-    def _build_fused(self, reverse, dim, latent_dim, device, t_kind=None) -> Optional[CompiledProgram]:
+    def _base_program(self, dim: int, latent_dim: int, device, t_kind=None) -> Optional[CompiledProgram]:
+        """log_prob under a Normal / MultivariateNormal base as ONE program of its own: the transforms' steps of the inverse pass, then
+        the base as a trailing step (densities.py `_plan`) in front of the kernel's unit-normal epilogue.  Its own cache key; the
+        base's parameters join the guards.  None when the builder refuses (then: `_log_prob_param_base`'s two launches)."""
+        base = self.base_dist
+        key = ('with-base', dim, latent_dim, str(device), t_kind)
+        return self._fused.get(key, lambda: self._build_fused(True, dim, latent_dim, device, t_kind, base=base),
+                               lambda: self._plan_guards() + base._plan_guards(),
+                               (self._fingerprint(), id(base), tuple(map(id, base._plan_guards()))))
+
+    def _build_fused(self, reverse, dim, latent_dim, device, t_kind=None, base=None) -> Optional[CompiledProgram]:
         order = list(reversed(self.transforms)) if reverse else list(self.transforms)
         try:
             hw = max([f._plan_hidden_width() for f in order] + [1])
@@ -436,9 +446,12 @@ class NormalizingFlow(Transform):
             for f in order:
                 if not f._plan(b, reverse, scale):
                     return None
+            if base is not None and not base._plan(b):
+                return None
             return b.build(device)
         except ProgramTooLong:
-            self._too_long.add((reverse, dim, latent_dim, str(device), t_kind))         # plans, but needs segments
+            if base is None:
+                self._too_long.add((reverse, dim, latent_dim, str(device), t_kind))         # plans, but needs segments
             return None
         except NotImplementedError:
             return None
@@ -710,9 +723,9 @@ class NormalizingFlow(Transform):
                           f'torch.no_grad() to silence this -- see INTEGRATION.md "Differentiable surface"',
                           RuntimeWarning, stacklevel=4)
 
-    def _run(self, x, reverse: bool, latent, want_y, want_ldj, want_logp, sum_out=None, **kwargs):
+    def _run(self, x, reverse: bool, latent, want_y, want_ldj, want_logp, sum_out=None, base=None, **kwargs):
         """Returns (y, ldj[..., 1], logp[..., 1]) (None where not requested) via the fused kernel, or None
-        when the flow cannot be fused."""
+        when the flow cannot be fused.  base: the program is `_base_program` (one launch or None: no segments)."""
         _hip.require_device(x, 'x')
         t = kwargs.pop('t', None)
         if kwargs:          # unknown keyword: let the per-layer path hand it to every transform
@@ -725,10 +738,13 @@ class NormalizingFlow(Transform):
         ld = 0 if lat2 is None else lat2.shape[1]
         row_t = t.reshape(-1) if t_kind == 'tensor' else None
         shp = lambda t, d: None if t is None else t.reshape(*lead, d)
-        prog = self._fused_program(reverse, x2.shape[1], ld, x.device, t_kind)
+        prog = self._fused_program(reverse, x2.shape[1], ld, x.device, t_kind) if base is None else \
+            self._base_program(x2.shape[1], ld, x.device, t_kind)
         if prog is not None:
             y, ldj, logp = prog.run(x2, lat2, want_y, want_ldj, want_logp, sum_out, row_t=row_t)
             return shp(y, x2.shape[1]), shp(ldj, 1), shp(logp, 1)
+        if base is not None:
+            return None
         segs = self._fused_segments(reverse, x2.shape[1], ld, x.device, t_kind)
         if segs is None:
             return None
@@ -818,6 +834,8 @@ class NormalizingFlow(Transform):
     def log_prob(self, y, latent=None, **kwargs):
         """[..., D] -> [..., 1]   (flow.py:127-130)."""
         from .dist.normal import UnitNormal
+        if self._param_base() and not self._wants_grad(y):
+            return self._log_prob_param_base(y, latent, None, kwargs)
         if isinstance(self.base_dist, UnitNormal):
             _hip.require_device(y, 'y')
             if self._wants_grad(y) and latent is None and not kwargs and self._can_backward(y):
@@ -847,6 +865,37 @@ class NormalizingFlow(Transform):
             return out.reshape(*lead, 1)
         return self.base_dist.log_prob(x).unsqueeze(-1) + acc      # foreign base density: torch ops
 
+    def _param_base(self) -> bool:
+        """Is the base a Normal / MultivariateNormal / Uniform of this package in its row-summing form?"""
+        from .densities import _ParamDist
+        return isinstance(self.base_dist, _ParamDist) and not getattr(self.base_dist, 'elementwise', False)
+
+    def _log_prob_param_base(self, y, latent, sum_out, kwargs):
+        """log_prob [..., 1] under a Normal / MultivariateNormal / Uniform base for a call that builds no graph.  One launch where
+        `_base_program` plans (Normal, MultivariateNormal).  Otherwise two: the flow's own inverse pass leaves (z, log-det) and ONE
+        launch of the base's kernel reads z once and adds the log-det (parameters outside the kernels' coverage: the closed form as
+        torch ops).  sum_out: the fp64 batch sum is accumulated there as well (log_prob_sum)."""
+        from .densities import log_prob_closed_form
+        _hip.require_device(y, 'y')
+        base = self.base_dist
+        if hasattr(base, '_plan'):
+            r = self._run(y, True, latent, False, False, True, sum_out=sum_out, base=base, **kwargs)
+            if r is not None:
+                return r[2]
+        # (bf16 storage: the latent stays fp32 up to the base density, as in the fused kernel)
+        x, acc = self.inverse_and_log_det_jacobian(y.to(torch.float32) if y.dtype == torch.bfloat16 else y, latent=latent, **kwargs)
+        x2, lead = flatten_rows(x)
+        ldj = acc.reshape(-1).to(torch.float32).contiguous() if torch.is_tensor(acc) else None
+        lp = base._kernel_rows(x2.contiguous(), ldj) if x2.dtype in (torch.float32, torch.bfloat16) and x2.numel() else None
+        if lp is None:          # (batch-shaped parameters broadcast against the sample as in the reference, flow.py:129)
+            lp = (log_prob_closed_form(base, x).unsqueeze(-1) + acc).to(torch.float32)
+        else:
+            lp = lp.reshape(*lead, 1)
+        if sum_out is not None:
+            flat = lp.reshape(-1).contiguous()
+            _hip.call('sx_sum_f64', flat, flat.data_ptr(), flat.numel(), sum_out.data_ptr())
+        return lp
+
     def log_prob_sum(self, y, out: Optional[torch.Tensor] = None, latent=None) -> torch.Tensor:
         """Sum over the batch of log_prob as ONE fp64 scalar accumulated on the device (the operand of the multi-GPU
         all-reduce).  The per-sample log_prob [N] is still written (fp32, 4 B per row: `CompiledProgram.run` allocates it and the
@@ -854,6 +903,9 @@ class NormalizingFlow(Transform):
         if out is None:
             out = torch.zeros(1, dtype=torch.float64, device=y.device)
         from .dist.normal import UnitNormal
+        if self._param_base() and not self._wants_grad(y):
+            self._log_prob_param_base(y, latent, out, {})
+            return out
         if isinstance(self.base_dist, UnitNormal):
             r = self._run(y, True, latent, False, False, True, sum_out=out)
             if r is not None:

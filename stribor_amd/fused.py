@@ -255,20 +255,37 @@ class _ConstJob:
         self.gather_host, self.dst_off = gather.astype(np.int64), dst_off
         self.gather = None
 
-    def run(self, blobs: torch.Tensor, prec: int = 0) -> None:
-        dev = blobs.device
-        if self.gather is None:
-            self.gather = torch.from_numpy(self.gather_host).to(dev)
+    def _values(self, dev):
+        """-> (ls [dim], sh [dim]) fp32 on dev"""
         ls = self.log_scale.detach().to(dev, torch.float32).reshape(-1).expand(self.dim) \
             if self.log_scale.numel() == 1 else self.log_scale.detach().to(dev, torch.float32).reshape(-1)
         sh = self.shift.detach().to(dev, torch.float32).reshape(-1).expand(self.dim) \
             if self.shift.numel() == 1 else self.shift.detach().to(dev, torch.float32).reshape(-1)
+        return ls, sh
+
+    def run(self, blobs: torch.Tensor, prec: int = 0) -> None:
+        dev = blobs.device
+        if self.gather is None:
+            self.gather = torch.from_numpy(self.gather_host).to(dev)
+        ls, sh = self._values(dev)
         src = torch.cat([ls, sh, torch.zeros(1, device=dev)])
         n = self.gather.numel()
         blobs[self.dst_off:self.dst_off + n] = src[self.gather]
 
     def params(self):
         return [self.log_scale, self.shift]
+
+
+class _DerivedConstJob(_ConstJob):
+    """Per-slot constants DERIVED from parameters (a Normal base density as a trailing step, densities.py: log scale and loc from
+    scale and loc): `derive(device)` -> (ls [dim], sh [dim]) fp32; the two tensors given are the sources the program tracks."""
+
+    def __init__(self, sources, derive, dim: int, gather: np.ndarray, dst_off: int):
+        super().__init__(sources[0], sources[1], dim, gather, dst_off)
+        self.derive = derive
+
+    def _values(self, dev):
+        return self.derive(dev)
 
 
 class _ScalarsJob:
@@ -1046,7 +1063,8 @@ class ProgramBuilder:
             self._step(_hip.STEP_LINEAR_BWD, off, n, c0=c0, ct=XT, t0=t0, tt=layer_slot, reverse=rev)
         return dict(kind='dense', slot_cols=col, side_width=256)
 
-    def add_affine_const(self, log_scale, shift, reverse: bool, ldj_scale: float) -> None:
+    def add_affine_const(self, log_scale, shift, reverse: bool, ldj_scale: float, derive=None) -> None:
+        """derive: see _DerivedConstJob (log_scale / shift are then the source parameters, not the values)."""
         self._freeze_input()
         D, T = self.dim, self.tiles
         off, n = self._alloc(2 * 32 * T)
@@ -1055,7 +1073,8 @@ class ProgramBuilder:
             if c >= 0:
                 gather[i] = c
                 gather[32 * T + i] = D + c
-        self.jobs.append(_ConstJob(log_scale, shift, D, gather, off))
+        self.jobs.append(_ConstJob(log_scale, shift, D, gather, off) if derive is None else
+                         _DerivedConstJob((log_scale, shift), derive, D, gather, off))
         self._step(_hip.STEP_AFFINE_CONST, off, n, tt=T, reverse=reverse, ldj_scale=ldj_scale)
 
     def add_coupling_time(self, W1, b1, W2, b2, mask: np.ndarray, act: int, reverse: bool, ldj_scale: float, hidden: int,
