@@ -1,6 +1,8 @@
 """Host (no GPU): the attention nets' surface (stribor/net/attention.py:8-147, util/safe_softmax.py) -- constructor signatures,
 state_dict keys, the default init under every F15 seed against the reference's sha256 (tests/golden/make_golden_attention.py),
-the flow-description conditioner kinds, safe_softmax, and that CPU tensors raise (there is no CPU fallback)."""
+the flow-description conditioner kinds, safe_softmax, and that CPU tensors raise (there is no CPU fallback); the fp64 oracle of
+test_gpu_attention_core.py (attncorehelp.oracle) against the fp64 composition on every case of that module, and the conditions on
+those cases."""
 import hashlib
 import inspect
 
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import attncorehelp as ach
 import flowdesc as fd
 from goldens import Golden
 
@@ -110,6 +113,79 @@ def test_safe_softmax():
     y = st.util.safe_softmax(x, -1)
     assert torch.equal(y[1], torch.zeros(3))
     assert torch.allclose(y[0], torch.softmax(x[0], -1))
+
+
+def _heads_scores(q, k, H):
+    """[..., H, Nq, Nk] fp64 logits, written apart from attncorehelp.oracle's per-head loop."""
+    dh = q.shape[-1] // H
+    qh = q.double().reshape(*q.shape[:-1], H, dh).transpose(-2, -3)
+    kh = k.double().reshape(*k.shape[:-1], H, dh).transpose(-2, -3)
+    return qh @ kh.transpose(-1, -2) / dh ** 0.5
+
+
+def _oracle_against_composition(c, t, masked, diag, tag):
+    """y, dq, dk, dv of attncorehelp's oracle against fp64 _attention_composed to 1e-12, its lse against fp64 logsumexp over the
+    live keys; the fp32 composition (the GPU tests' error yardstick) is finite."""
+    from stribor_amd.net.attention import _attention_composed
+    mask = c['mask'] if masked else None
+    q, k, v = (c[n].double().requires_grad_() for n in 'qkv')
+    y = _attention_composed(q, k, v, c['n_heads'], diag, None if mask is None else mask.double())
+    grads = torch.autograd.grad(y, (q, k, v), c['gy'].double())
+    for n, want in zip(('y', 'dq', 'dk', 'dv'), (y.detach(),) + grads):
+        assert t[n].dtype == torch.float64 and t[n].shape == want.shape
+        err = (t[n] - want).abs().max().item()
+        assert err <= 1e-12, (tag, n, err)
+    s = _heads_scores(c['q'], c['k'], c['n_heads'])
+    if mask is not None:
+        s = s.masked_fill((mask[..., 0] != 1)[:, None, None, :], -float('inf'))
+    if diag:
+        s = s.masked_fill(torch.eye(s.shape[-1], dtype=torch.bool), -float('inf'))
+    want = torch.logsumexp(s, -1)
+    dead = torch.isinf(want)                                   # (-inf: no live key)
+    assert torch.equal(torch.isinf(t['lse']) & (t['lse'] > 0), dead), tag
+    assert (t['lse'][~dead] - want[~dead]).abs().max().item() <= 1e-12, tag
+    y32 = _attention_composed(c['q'], c['k'], c['v'], c['n_heads'], diag, mask)
+    assert y32.dtype == torch.float32 and torch.isfinite(y32).all(), tag
+
+
+@pytest.mark.parametrize('name', sorted(ach.CASES))
+def test_core_oracle_matches_the_fp64_composition(name):
+    """Every case of test_gpu_attention_core.py's sweep: the independent oracle against the composition, and the conditions that
+    keep the sweep from being trivial (attncorehelp.check_conditions)."""
+    ach.check_conditions(name)
+    for masked, diag in ach.runs(name):
+        _oracle_against_composition(ach.case(name), ach.truth(name, masked, diag), masked, diag, (name, masked, diag))
+
+
+@pytest.mark.parametrize('shape', sorted(ach.LOGIT_SHAPES))
+@pytest.mark.parametrize('variant', ach.LOGIT_VARIANTS)
+def test_core_oracle_on_large_and_shifted_logits(shape, variant):
+    """The large-logit cases: their construction holds (tile maxima monotone, shift of order 300), the oracle still agrees with the
+    fp64 composition, the fp32 composition stays finite, and the shift leaves the fp64 result where it was."""
+    ach.check_logit_conditions(shape, variant)
+    c = ach.logit_case(shape, variant)
+    for masked in (False, True):
+        _oracle_against_composition(c, ach.logit_truth(shape, variant, masked), masked, False, (shape, variant, masked))
+    if variant == 'shift300':
+        y0, _ = ach.oracle(c['q'], c['k'].double() - c['shift'].double(), c['v'], c['n_heads'], False, None)
+        assert (ach.logit_truth(shape, variant, False)['y'] - y0).abs().max().item() <= 1e-9
+
+
+def test_core_oracle_edges():
+    """The oracle's own edges: a query without a live key gives y = 0 and lse = +inf, 0.5 is dead, the output mask is the raw value,
+    no key at all."""
+    q, k, v = torch.randn(2, 3, 4), torch.randn(2, 3, 4), torch.randn(2, 3, 4)
+    mask = torch.tensor([[1., 0.5, 0.], [0., 0., 0.5]]).unsqueeze(-1)
+    y, lse = ach.oracle(q, k, v, 2, False, mask)
+    assert torch.equal(y[1], torch.zeros(3, 4, dtype=torch.float64)) and torch.equal(lse[1], torch.full((2, 3), float('inf')).double())
+    assert torch.allclose(y[0, 0], v[0, 0].double()) and torch.allclose(y[0, 1], 0.5 * v[0, 0].double())
+    assert torch.equal(y[0, 2], torch.zeros(4, dtype=torch.float64))
+    s = _heads_scores(q, k, 2)
+    assert torch.allclose(lse[0], s[0, :, :, 0])
+    y, lse = ach.oracle(q, k, v, 1, True, mask)
+    assert torch.equal(y[0, 0], torch.zeros(4, dtype=torch.float64)) and torch.isinf(lse[0, 0, 0]) and torch.isfinite(lse[0, 0, 1:]).all()
+    y, lse = ach.oracle(q, k[:, :0], v[:, :0], 2, False, None)
+    assert torch.equal(y, torch.zeros(2, 3, 4, dtype=torch.float64)) and torch.isinf(lse).all() and (lse > 0).all()
 
 
 def test_cpu_tensors_raise():
