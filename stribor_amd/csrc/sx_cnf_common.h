@@ -9,7 +9,8 @@
 //   * the launcher and the per-call argument checks.
 // sx_cnf.hip and sx_cnf_train.hip take it through sx_cnf_dense.h, which adds what the two dense files share with each other alone;
 // they use all of it but cnf_act_all (sx_cnf_dense.h's sweep keeps the widest dense kernel free of spills) and cnf_latent_packed.
-// Everything here has internal linkage: six translation units include it.
+// sx_cnf_exact.hip and sx_cnf_exact_set.hip take it through sx_cnf_exact_common.h, which does the same for the two exact-trace files.
+// Everything here has internal linkage: seven translation units include it (the six above, and sx_base.hip for the MFMA layout).
 #pragma once
 #include "sx_common.h"
 

@@ -589,61 +589,47 @@ class ContinuousTransform(Transform):
             return None
         return d, [t.detach() for t in tensors]
 
-    def _exact_kernel_net(self, latent_dim: int, device):
-        """(sx_cnf_exact_net, keep-alive list) for sx_cnf_exact_flow, or None when the ODE function is outside its coverage."""
-        s = exact_trace.kernel_coverage(self.odefunc.diffeq, self.dim, latent_dim)
+    def _exact_plan(self, s, latent_dim: int, device, set_size=None):
+        """(net descriptor, keep-alive list) of an exact-trace structure dict `s` (exact_trace.kernel_coverage / kernel_coverage_set; None:
+        not covered) for sx_cnf_exact_flow or -- with a `set_size` -- sx_cnf_exact_set_flow, or None outside the kernel's coverage."""
         if s is None:
             return None
         # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
         if any(_ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True for m in s['activations']):
             return None
-        guards = exact_trace.kernel_tensors(s)
-        if any(g.dtype != torch.float32 or g.device != device for g in guards):
+        is_set = set_size is not None
+        guards = (exact_trace.kernel_tensors_set if is_set else exact_trace.kernel_tensors)(s)
+        if any(g.dtype != torch.float32 or not g.is_contiguous() or g.device != device for g in guards):
             return None
 
         def build():
-            image, w_latent = exact_trace.kernel_image(s)
+            image, w_latent = (exact_trace.kernel_image_set if is_set else exact_trace.kernel_image)(s)
             image = torch.from_numpy(image).to(device)
             return image, (None if w_latent is None else torch.from_numpy(w_latent).contiguous().to(device))
-        image, w_latent = self._trace.get(('exact', str(device)), build, guards=guards)
-        d = _hip.sx_cnf_exact_net()
+        image, w_latent = self._trace.get(('exact_set' if is_set else 'exact', str(device)), build, guards=guards)
+        d = _hip.sx_cnf_exact_set_net() if is_set else _hip.sx_cnf_exact_net()
         d.image, d.w_latent, d.image_floats = image.data_ptr(), (0 if w_latent is None else w_latent.data_ptr()), image.numel()
         d.dim, d.d_h, d.latent_dim, d.n_hidden, d.act = self.dim, s['d_h'], latent_dim, len(s['hidden']), _hip.ACT_CODES[s['act']]
         for i, w in enumerate(s['hidden']):
             d.hidden[i] = w
-        lds = _hip.lib().sx_cnf_exact_lds_bytes(d)
-        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * image.numel():
+        floats = image.numel()
+        if is_set:
+            d.set_size, d.pooling = set_size, exact_trace.POOLINGS[s['pooling']]
+            floats += exact_trace.SET_EXCHANGE_FLOATS
+        lds = (_hip.lib().sx_cnf_exact_set_lds_bytes if is_set else _hip.lib().sx_cnf_exact_lds_bytes)(d)
+        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * floats:
             return None
         return d, [image, w_latent]
+
+    def _exact_kernel_net(self, latent_dim: int, device):
+        """(sx_cnf_exact_net, keep-alive list) for sx_cnf_exact_flow, or None when the ODE function is outside its coverage."""
+        return self._exact_plan(exact_trace.kernel_coverage(self.odefunc.diffeq, self.dim, latent_dim), latent_dim, device)
 
     def _exact_set_kernel_net(self, set_size: int, latent_dim: int, device):
         """(sx_cnf_exact_set_net, keep-alive list) for sx_cnf_exact_set_flow over sets of `set_size` elements, or None when the ODE
         function is outside its coverage."""
         s = exact_trace.kernel_coverage_set(self.odefunc.diffeq, self.dim, latent_dim, set_size)
-        if s is None:
-            return None
-        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
-        if any(_ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True for m in s['activations']):
-            return None
-        guards = exact_trace.kernel_tensors_set(s)
-        if any(g.dtype != torch.float32 or not g.is_contiguous() or g.device != device for g in guards):
-            return None
-
-        def build():
-            image, w_latent = exact_trace.kernel_image_set(s)
-            image = torch.from_numpy(image).to(device)
-            return image, (None if w_latent is None else torch.from_numpy(w_latent).contiguous().to(device))
-        image, w_latent = self._trace.get(('exact_set', str(device)), build, guards=guards)
-        d = _hip.sx_cnf_exact_set_net()
-        d.image, d.w_latent, d.image_floats = image.data_ptr(), (0 if w_latent is None else w_latent.data_ptr()), image.numel()
-        d.dim, d.d_h, d.latent_dim, d.n_hidden, d.act = self.dim, s['d_h'], latent_dim, len(s['hidden']), _hip.ACT_CODES[s['act']]
-        d.set_size, d.pooling = set_size, exact_trace.POOLINGS[s['pooling']]
-        for i, w in enumerate(s['hidden']):
-            d.hidden[i] = w
-        lds = _hip.lib().sx_cnf_exact_set_lds_bytes(d)
-        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * (image.numel() + exact_trace.SET_EXCHANGE_FLOATS):
-            return None
-        return d, [image, w_latent]
+        return self._exact_plan(s, latent_dim, device, set_size)
 
     # ---- the two paths ----------------------------------------------------------------------------------------------------------
     def _solve_kernel(self, plan, x2, lat2, name, step, grid, want_ldj, entry='sx_cnf_flow'):

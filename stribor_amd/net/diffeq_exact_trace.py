@@ -205,13 +205,9 @@ def _fragment_image(Wp: np.ndarray) -> np.ndarray:
     return np.concatenate(tiles).astype(np.float32)
 
 
-def kernel_coverage(net, dim: int, latent_dim: int):
-    """The structure dict of `net` when sx_cnf_exact_flow covers it for rows of `dim` features and `latent_dim` latent columns, else
-    None."""
+def _covered(s, dim: int, latent_dim: int):
+    """A structure dict (or None) -> itself when it is inside the ranges the two exact-trace kernels share, else None."""
     from .. import _hip
-    if type(net) is not DiffeqExactTraceMLP or not net.return_log_det_jac:
-        return None
-    s = _structure(net)
     if s is None or s['D'] != dim or s['L'] != latent_dim:
         return None
     if not 1 <= dim <= MAX_DIM or not 1 <= s['d_h'] <= MAX_DH or latent_dim > MAX_LATENT:
@@ -221,6 +217,14 @@ def kernel_coverage(net, dim: int, latent_dim: int):
     if _hip.ACT_CODES.get(s['act'], 99) > 6:
         return None
     return s
+
+
+def kernel_coverage(net, dim: int, latent_dim: int):
+    """The structure dict of `net` when sx_cnf_exact_flow covers it for rows of `dim` features and `latent_dim` latent columns, else
+    None."""
+    if type(net) is not DiffeqExactTraceMLP or not net.return_log_det_jac:
+        return None
+    return _covered(_structure(net), dim, latent_dim)
 
 
 def kernel_tensors(s):
@@ -234,59 +238,86 @@ def kernel_tensors(s):
     return ts
 
 
-def kernel_image(s):
-    """-> (image [floats] fp32 numpy, w_latent [32 HT, 32 LT] fp32 numpy | None): the layout of include/stribor_hip.h
-    (sx_cnf_exact_net).  The masks are multiplied in HERE: a weight entry under a zero mask never reaches the kernel."""
-    D, d_h, L, hidden = s['D'], s['d_h'], s['L'], s['hidden']
-    HT, OT, NH = max(_tiles(w) for w in hidden), _out_tiles(d_h), len(hidden)
-    npy = lambda p: p.detach().cpu().numpy().astype(np.float32)
-    pos_x = _kmap(np.arange(D), 0)
-    cols = np.arange(d_h * D)
-    pos_raw = 32 * ((cols // D) >> 1) + _kmap(cols % D, (cols // D) & 1)
-    kk = np.arange(d_h)
-    pos_in = _kmap(1 + (kk >> 1), kk & 1)
-    parts = []
+class _Image:
+    """The parts of a kernel image in order, with the position tables and the blocks the two images share."""
 
-    def vec(n_tiles, pos, values):
+    def __init__(self, s):
+        D, d_h, hidden = s['D'], s['d_h'], s['hidden']
+        self.d_h, self.L = d_h, s['L']
+        self.HT, self.OT, self.NH = max(_tiles(w) for w in hidden), _out_tiles(d_h), len(hidden)
+        self.pos_x = _kmap(np.arange(D), 0)
+        cols = np.arange(d_h * D)
+        self.pos_raw = 32 * ((cols // D) >> 1) + _kmap(cols % D, (cols // D) & 1)
+        kk = np.arange(d_h)
+        self.pos_e = _kmap(kk >> 1, kk & 1)                           # slot kk of the set embedding: register kk >> 1, lane half kk & 1
+        self.pos_in = _kmap(1 + (kk >> 1), kk & 1)
+        self.parts = []
+
+    @staticmethod
+    def npy(p):
+        return p.detach().cpu().numpy().astype(np.float32)
+
+    def vec(self, n_tiles, pos, values):
         v = np.zeros(32 * n_tiles, np.float32)
         if values is not None:
             v[pos] = values
-        parts.append(v)
+        self.parts.append(v)
 
-    def mat(mt, kt, rpos, cpos, W):
+    def bias(self, n_tiles, pos, layer):
+        self.vec(n_tiles, pos, None if layer.bias is None else self.npy(layer.bias))
+
+    def mat(self, mt, kt, rpos, cpos, W):
         Wp = np.zeros((32 * mt, 32 * kt), np.float32)
         Wp[np.ix_(rpos, cpos)] = W
-        parts.append(_fragment_image(Wp))
+        self.parts.append(_fragment_image(Wp))
 
-    for lins in s['made']:
-        in_pos = pos_x
+    def stage_made(self, lins):
+        """A MADE: mask * weight and the bias per layer, the last layer at the MADE output's positions."""
+        in_pos = self.pos_x
         for i, l in enumerate(lins):
             last = i + 1 == len(lins)
-            out_pos = pos_raw if last else np.arange(l.out_features)
-            W = npy(l.mask) * npy(l.weight)
-            W = np.where(npy(l.mask) != 0, W, np.float32(0))          # (0 * inf is not 0)
-            mat(OT if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W)
-            vec(OT if last else HT, out_pos, None if l.bias is None else npy(l.bias))
+            out_pos = self.pos_raw if last else np.arange(l.out_features)
+            mask = self.npy(l.mask)
+            with np.errstate(invalid='ignore'):
+                W = np.where(mask != 0, mask * self.npy(l.weight), np.float32(0))          # (0 * inf is not 0)
+            self.mat(self.OT if last else self.HT, 1 if i == 0 else self.HT, out_pos, in_pos, W)
+            self.bias(self.OT if last else self.HT, out_pos, l)
             in_pos = out_pos
-    dw = s['dimwise']
-    W1 = npy(dw[0].weight)
-    h1 = np.arange(W1.shape[0])
-    mat(HT, 1, h1, np.concatenate([[0], pos_in]), W1[:, 1:2 + d_h])
-    vec(HT, h1, None if dw[0].bias is None else npy(dw[0].bias))
-    vec(HT, h1, W1[:, 0])
-    vec(HT, h1, W1[:, 1])
-    if NH == 2:
-        W2 = npy(dw[1].weight)
-        mat(HT, HT, np.arange(W2.shape[0]), h1, W2)
-        vec(HT, np.arange(W2.shape[0]), None if dw[1].bias is None else npy(dw[1].bias))
-    wl = npy(dw[-1].weight)
-    vec(HT, np.arange(wl.shape[1]), wl[0])
-    vec(1, np.arange(1), None if dw[-1].bias is None else npy(dw[-1].bias))
-    w_latent = None
-    if L:
-        w_latent = np.zeros((32 * HT, 32 * ((L + 31) // 32)), np.float32)
-        w_latent[:W1.shape[0], :L] = W1[:, 2 + d_h:]
-    return np.concatenate(parts), w_latent
+
+    def stage_dimwise(self, dw):
+        """The dimwise net's block, which ends both images -> (image, w_latent)."""
+        HT, d_h = self.HT, self.d_h
+        W1 = self.npy(dw[0].weight)
+        h1 = np.arange(W1.shape[0])
+        self.mat(HT, 1, h1, np.concatenate([[0], self.pos_in]), W1[:, 1:2 + d_h])
+        self.bias(HT, h1, dw[0])
+        self.vec(HT, h1, W1[:, 0])
+        self.vec(HT, h1, W1[:, 1])
+        if self.NH == 2:
+            W2 = self.npy(dw[1].weight)
+            self.mat(HT, HT, np.arange(W2.shape[0]), h1, W2)
+            self.bias(HT, np.arange(W2.shape[0]), dw[1])
+        wl = self.npy(dw[-1].weight)
+        self.vec(HT, np.arange(wl.shape[1]), wl[0])
+        self.bias(1, np.arange(1), dw[-1])
+        return np.concatenate(self.parts), self.w_latent(W1)
+
+    def w_latent(self, W1):
+        """The latent columns of the dimwise first layer, zero-padded to whole tiles (None without latent columns)."""
+        if not self.L:
+            return None
+        w = np.zeros((32 * self.HT, 32 * ((self.L + 31) // 32)), np.float32)
+        w[:W1.shape[0], :self.L] = W1[:, 2 + self.d_h:]
+        return w
+
+
+def kernel_image(s):
+    """-> (image [floats] fp32 numpy, w_latent [32 HT, 32 LT] fp32 numpy | None): the layout of include/stribor_hip.h
+    (sx_cnf_exact_net).  The masks are multiplied in HERE: a weight entry under a zero mask never reaches the kernel."""
+    im = _Image(s)
+    for lins in s['made']:
+        im.stage_made(lins)
+    return im.stage_dimwise(s['dimwise'])
 
 
 # ---- the set instance -------------------------------------------------------------------------------------------------------------
@@ -384,19 +415,9 @@ def closed_form_set(net, t, x, latent=None, want_jac: bool = True, dtype=None):
 def kernel_coverage_set(net, dim: int, latent_dim: int, set_size: int):
     """The structure dict of `net` when sx_cnf_exact_set_flow covers it for sets of `set_size` elements of `dim` features and
     `latent_dim` latent columns, else None."""
-    from .. import _hip
-    if type(net) is not DiffeqExactTraceDeepSet or not net.return_log_det_jac:
+    if type(net) is not DiffeqExactTraceDeepSet or not net.return_log_det_jac or not 1 <= set_size <= MAX_SET_SIZE:
         return None
-    s = _structure_set(net)
-    if s is None or s['D'] != dim or s['L'] != latent_dim:
-        return None
-    if not 1 <= dim <= MAX_DIM or not 1 <= s['d_h'] <= MAX_DH or latent_dim > MAX_LATENT or not 1 <= set_size <= MAX_SET_SIZE:
-        return None
-    if len(s['hidden']) not in (1, 2) or any(not 1 <= w <= MAX_HIDDEN for w in s['hidden']):
-        return None
-    if _hip.ACT_CODES.get(s['act'], 99) > 6:
-        return None
-    return s
+    return _covered(_structure_set(net), dim, latent_dim)
 
 
 def kernel_tensors_set(s):
@@ -412,63 +433,16 @@ def kernel_tensors_set(s):
 def kernel_image_set(s):
     """-> (image [floats] fp32 numpy, w_latent [32 HT, 32 LT] fp32 numpy | None): the layout of include/stribor_hip.h
     (sx_cnf_exact_set_net).  The masks are multiplied in HERE: a weight entry under a zero mask never reaches the kernel."""
-    D, d_h, L, hidden = s['D'], s['d_h'], s['L'], s['hidden']
-    HT, OT, NH = max(_tiles(w) for w in hidden), _out_tiles(d_h), len(hidden)
-    npy = lambda p: p.detach().cpu().numpy().astype(np.float32)
-    pos_x = _kmap(np.arange(D), 0)
-    cols = np.arange(d_h * D)
-    pos_raw = 32 * ((cols // D) >> 1) + _kmap(cols % D, (cols // D) & 1)
-    kk = np.arange(d_h)
-    pos_e = _kmap(kk >> 1, kk & 1)                                    # slot kk of the embedding: register kk >> 1, lane half kk & 1
-    pos_in = _kmap(1 + (kk >> 1), kk & 1)
-    parts = []
-
-    def vec(n_tiles, pos, values):
-        v = np.zeros(32 * n_tiles, np.float32)
-        if values is not None:
-            v[pos] = values
-        parts.append(v)
-
-    def mat(mt, kt, rpos, cpos, W):
-        Wp = np.zeros((32 * mt, 32 * kt), np.float32)
-        Wp[np.ix_(rpos, cpos)] = W
-        parts.append(_fragment_image(Wp))
-
-    in_pos = pos_x
-    for i, l in enumerate(s['made']):
-        last = i + 1 == len(s['made'])
-        out_pos = pos_raw if last else np.arange(l.out_features)
-        with np.errstate(invalid='ignore'):
-            W = np.where(npy(l.mask) != 0, npy(l.mask) * npy(l.weight), np.float32(0))          # (0 * inf is not 0)
-        mat(OT if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W)
-        vec(OT if last else HT, out_pos, None if l.bias is None else npy(l.bias))
-        in_pos = out_pos
-    in_pos = pos_x
+    im = _Image(s)
+    im.stage_made(s['made'])
+    in_pos = im.pos_x
     for i, l in enumerate(s['emb']):
         last = i + 1 == len(s['emb'])
-        out_pos = pos_e if last else np.arange(l.out_features)
-        W = npy(l.weight)
-        mat(1 if last else HT, 1 if i == 0 else HT, out_pos, in_pos, W[:, 1:] if i == 0 else W)
-        vec(1 if last else HT, out_pos, None if l.bias is None else npy(l.bias))
+        out_pos = im.pos_e if last else np.arange(l.out_features)
+        W = im.npy(l.weight)
+        im.mat(1 if last else im.HT, 1 if i == 0 else im.HT, out_pos, in_pos, W[:, 1:] if i == 0 else W)
+        im.bias(1 if last else im.HT, out_pos, l)
         if i == 0:
-            vec(HT, out_pos, W[:, 0])
+            im.vec(im.HT, out_pos, W[:, 0])
         in_pos = out_pos
-    dw = s['dimwise']
-    W1 = npy(dw[0].weight)
-    h1 = np.arange(W1.shape[0])
-    mat(HT, 1, h1, np.concatenate([[0], pos_in]), W1[:, 1:2 + d_h])
-    vec(HT, h1, None if dw[0].bias is None else npy(dw[0].bias))
-    vec(HT, h1, W1[:, 0])
-    vec(HT, h1, W1[:, 1])
-    if NH == 2:
-        W2 = npy(dw[1].weight)
-        mat(HT, HT, np.arange(W2.shape[0]), h1, W2)
-        vec(HT, np.arange(W2.shape[0]), None if dw[1].bias is None else npy(dw[1].bias))
-    wl = npy(dw[-1].weight)
-    vec(HT, np.arange(wl.shape[1]), wl[0])
-    vec(1, np.arange(1), None if dw[-1].bias is None else npy(dw[-1].bias))
-    w_latent = None
-    if L:
-        w_latent = np.zeros((32 * HT, 32 * ((L + 31) // 32)), np.float32)
-        w_latent[:W1.shape[0], :L] = W1[:, 2 + d_h:]
-    return np.concatenate(parts), w_latent
+    return im.stage_dimwise(s['dimwise'])

@@ -38,6 +38,17 @@ def build_case(case):
     return f, g.t(f'{case}/x'), (g.t(f'{case}/latent') if g.has(f'{case}/latent') else None), m
 
 
+def set_activation(net, act):
+    """One of torch's activations by hand on the three nets of a DiffeqExactTraceMLP (the reference's constructors offer no argument
+    for it): the two MADEs and the dimwise MLP, as exactsethelp.set_activation does for the set net."""
+    made1, made2, dw = net.exclusive_net.net1, net.exclusive_net.net2, net.dimwise_net.net
+    made1.activation = made2.activation = dw.activation_name = act
+    for seq in (made1.net, made2.net, dw.net):
+        for i in range(1, len(seq), 2):
+            seq[i] = getattr(torch.nn, act)()
+    return net
+
+
 def net64(net, latent=None):
     """fp64 restatement of a DiffeqExactTraceMLP-shaped module (MADE + MADE, then the dimwise MLP over [t, x_i, h_i, latent]) as one
     differentiable function f(t, x) -> [..., D] on the CPU; `params`: substitute tensors keyed like net.named_parameters()."""

@@ -277,3 +277,27 @@ def test_kernel_coverage_set_gates():
     net = mk()
     net.exclusive_net.interaction.pooling = 'median'
     assert xt.kernel_coverage_set(net, 3, 0, 5) is None
+
+
+def test_kernel_image_set_stages_zeros_for_a_layer_without_bias():
+    """Every bias vector of the image comes from one builder branch: a layer with `bias = None` stages what a zero bias stages."""
+    torch.manual_seed(6)
+    D, hidden, d_h = 3, [20, 20], 3
+    net = st.net.DiffeqExactTraceDeepSet(D, hidden, D, d_h, latent_dim=2, pooling='max')
+    linears = [m for m in net.modules() if isinstance(m, nn.Linear)]
+    assert len(linears) == 9
+    with torch.no_grad():
+        for l in linears:
+            l.bias.normal_()
+    with_bias = xt.kernel_image_set(xt.kernel_coverage_set(net, D, 2, 4))
+    with torch.no_grad():
+        for l in linears:
+            l.bias.zero_()
+    zero_bias = xt.kernel_image_set(xt.kernel_coverage_set(net, D, 2, 4))
+    for l in linears:
+        l.bias = None
+    s = xt.kernel_coverage_set(net, D, 2, 4)
+    assert s is not None and all(t is not None for t in xt.kernel_tensors_set(s))
+    no_bias = xt.kernel_image_set(s)
+    assert np.array_equal(no_bias[0], zero_bias[0]) and np.array_equal(no_bias[1], zero_bias[1])
+    assert not np.array_equal(with_bias[0], zero_bias[0]) and np.array_equal(with_bias[1], zero_bias[1])

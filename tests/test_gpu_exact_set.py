@@ -110,6 +110,25 @@ def test_shape_edges(name, solver):
         _check(f, x, lat, 'kernel', reverse=reverse)
 
 
+TILE_TRIPLES = {
+    # the kernel instantiation (HT, NH, OT): (hidden, d_h) that selects it
+    (1, 1, 1): ([20], 1), (1, 1, 2): ([20], 3), (1, 1, 4): ([20], 5),
+    (1, 2, 1): ([20, 20], 1), (1, 2, 2): ([20, 20], 3), (1, 2, 4): ([20, 20], 5),
+    (2, 1, 1): ([33], 1), (2, 1, 2): ([33], 3), (2, 1, 4): ([33], 5),
+    (2, 2, 1): ([20, 33], 1), (2, 2, 2): ([33, 20], 3), (2, 2, 4): ([33, 33], 5),
+}
+assert set(TILE_TRIPLES) == {(ht, nh, ot) for ht in (1, 2) for nh in (1, 2) for ot in (1, 2, 4)}
+assert all((max(1 if w <= 32 else 2 for w in hidden), len(hidden), 1 if d_h <= 2 else 2 if d_h <= 4 else 4) == triple
+           for triple, (hidden, d_h) in TILE_TRIPLES.items())
+
+
+@pytest.mark.parametrize('triple', sorted(TILE_TRIPLES))
+def test_every_kernel_instantiation(triple):
+    hidden, d_h = TILE_TRIPLES[triple]
+    f = xh.make(3, hidden, d_h, pooling='max', seed=sum(triple) + 10 * len(hidden))
+    _check(f, torch.randn(3, 5, 3), None, 'kernel')
+
+
 @pytest.mark.parametrize('act', ['Identity', 'Tanh', 'ReLU', 'Sigmoid', 'ELU', 'Softplus', 'LeakyReLU'])
 def test_activations(act):
     f = xh.make(3, [24, 16], 3, latent=2, pooling='mean', seed=7)

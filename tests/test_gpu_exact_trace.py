@@ -105,10 +105,30 @@ def test_row_counts(n):
 
 
 KERNEL_SHAPES = {
-    # name: (dim, hidden, d_h, latent)
-    'dim1': (1, [32], 3, 0), 'dim15': (15, [40, 24], 2, 0), 'dim16': (16, [64], 4, 3), 'last_layer_128': (16, [64, 64], 8, 0),
-    'latent64': (4, [48], 5, 64), 'd_h1_h2': (3, [20, 33], 1, 33),
+    # name: (dim, hidden, d_h, latent)                                     the kernel instantiation (HT, NH, OT)
+    'dim1': (1, [32], 3, 0),                                             # (1, 1, 2)
+    'dim15': (15, [40, 24], 2, 0),                                       # (2, 2, 1)
+    'dim16': (16, [64], 4, 3),                                           # (2, 1, 2)
+    'last_layer_128': (16, [64, 64], 8, 0),                              # (2, 2, 4)
+    'latent64': (4, [48], 5, 64),                                        # (2, 1, 4)
+    'd_h1_h2': (3, [20, 33], 1, 33),                                     # (2, 2, 1)
+    'ht1_nh1_ot1': (3, [20], 1, 0),                                      # (1, 1, 1)
+    'ht1_nh1_ot4': (3, [20], 5, 2),                                      # (1, 1, 4)
+    'ht1_nh2_ot1': (3, [20, 20], 1, 0),                                  # (1, 2, 1)
+    'ht1_nh2_ot2': (3, [20, 20], 3, 2),                                  # (1, 2, 2)
+    'ht1_nh2_ot4': (3, [20, 20], 5, 0),                                  # (1, 2, 4)
+    'ht2_nh1_ot1': (3, [33], 1, 2),                                      # (2, 1, 1)
+    'ht2_nh2_ot2': (3, [33, 20], 3, 0),                                  # (2, 2, 2)
 }
+
+
+def _triple(hidden, d_h):
+    """(hidden tiles, hidden layers, output tiles): the template arguments of the kernel a net runs on."""
+    return max(1 if w <= 32 else 2 for w in hidden), len(hidden), 1 if d_h <= 2 else 2 if d_h <= 4 else 4
+
+
+ALL_TRIPLES = {(ht, nh, ot) for ht in (1, 2) for nh in (1, 2) for ot in (1, 2, 4)}
+assert {_triple(hidden, d_h) for _, hidden, d_h, _ in KERNEL_SHAPES.values()} == ALL_TRIPLES
 
 
 @pytest.mark.parametrize('name', sorted(KERNEL_SHAPES))
@@ -123,6 +143,13 @@ def test_kernel_shapes(name):
     with torch.no_grad():
         y_only = f.to(DEV)(x.to(DEV), **({} if lat is None else {'latent': lat.to(DEV)}))
     assert f._last_path == 'kernel' and torch.equal(y_only, y)           # (the call without a log-det skips the tangent)
+
+
+@pytest.mark.parametrize('act', ['Identity', 'Tanh', 'ReLU', 'Sigmoid', 'ELU', 'Softplus', 'LeakyReLU'])
+def test_activations(act):
+    f = _cnf(3, [24, 16], 3, latent=2, seed=7)
+    eh.set_activation(f.odefunc.diffeq, act)
+    _check_against_fp64(f, torch.randn(37, 3), torch.randn(37, 2), 'kernel')
 
 
 def test_mask_is_applied_at_staging():
