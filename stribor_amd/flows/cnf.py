@@ -35,9 +35,16 @@ Linear layers, hidden <= 64, embedding <= 32, 1, 2 or 4 heads, N <= 128, dim <= 
 ``sx_cnf_attn_flow``: keys and values meet in LDS once per evaluation, and the per-element divergence comes from a forward tangent per
 coordinate (``net.self_attention_closed_form`` states it in torch) -- 1 + dim attentions per evaluation where
 ``divergence_exact_for_sets`` makes N * dim reverse passes (DESIGN.md "CNF on sets with attention").
+
+How a call picks its kernel is ``ContinuousTransform._choose`` over the table ``_TIERS``, in the order dense, exact-trace sets,
+exact-trace, sets, attention sets, after the training pair and before the composition path; ``_solve`` has one tail for every route.
+One planner per kernel (``_kernel_net``, ``_train_kernel_net``, ``_set_kernel_net``, ``_attn_kernel_net``, ``_exact_kernel_net``,
+``_exact_set_kernel_net``) returns (net descriptor, keep-alive list) or None; the conditions they share -- the activation, the
+tensors, the ``Linear (act Linear)*`` stack, the tile count -- and the activations' derivatives are ``net.cover``'s.  ``Grid`` carries
+a solve's (solver, step, points) and yields the launches' common argument tail.
 """
 import ctypes
-from typing import Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -46,7 +53,7 @@ import torch.nn as nn
 from .. import _hip
 from ..flow import Transform, flatten_rows, graph_wanted
 from ..fused import ProgramCache
-from ..net import diffeq_exact_trace as exact_trace
+from ..net import cover, diffeq_exact_trace as exact_trace
 from ..net.attention import SelfAttention
 from ..net.diffeq import DiffeqDeepset, DiffeqMLP, DiffeqSelfAttention
 from ..net.diffeq_zero_trace import DiffeqZeroTraceDeepSet
@@ -58,9 +65,18 @@ __all__ = ['ContinuousTransform']
 
 FIXED_SOLVERS = ('euler', 'midpoint', 'rk4')
 STAGES = {'euler': 1, 'midpoint': 2, 'rk4': 4}
-_ACT_DEFAULTS = {nn.LeakyReLU: lambda m: m.negative_slope == 0.01, nn.ELU: lambda m: m.alpha == 1.0,
-                 nn.Softplus: lambda m: m.beta == 1 and m.threshold == 20}
 _DIVERGENCES = ('compute', 'compute_set', 'approximate', 'exact', 'none')
+
+
+class Grid(NamedTuple):
+    """The fixed grid of one solve: the solver's name, the step size (None: the single step) and the fp32 points of `fixed_grid`."""
+    name: str
+    step: Optional[float]
+    points: np.ndarray
+
+    def c_args(self, n: int):
+        """The arguments every launch ends its solve with: rows, solver code, steps, t0, t1 and the step size (0: one step)."""
+        return n, _hip.CNF_SOLVERS[self.name], len(self.points) - 1, float(self.points[0]), float(self.points[-1]), float(self.step or 0.0)
 
 
 def fixed_grid(t0: float, t1: float, step_size: Optional[float] = None) -> np.ndarray:
@@ -115,31 +131,12 @@ def set_trace_constants(weights, dim: int, n: int):
 
 def _act_and_derivatives(name: str, a):
     """(act(a), act'(a), act''(a)) with both derivatives taken from the activation's OUTPUT, as the kernels take them."""
-    one = torch.ones_like(a)
-    if name == 'Identity':
-        return a, one, torch.zeros_like(a)
-    if name == 'Tanh':
-        h = torch.tanh(a)
-        d = 1 - h * h
-        return h, d, -2 * h * d
-    if name == 'ReLU':
-        h = torch.relu(a)
-        return h, (h > 0).to(a.dtype), torch.zeros_like(a)
-    if name == 'Sigmoid':
-        h = torch.sigmoid(a)
-        d = h * (1 - h)
-        return h, d, d * (1 - 2 * h)
-    if name == 'ELU':
-        h = nn.functional.elu(a)
-        return h, torch.where(h > 0, one, h + 1), torch.where(h > 0, torch.zeros_like(a), h + 1)
-    if name == 'Softplus':
-        h = nn.functional.softplus(a)
-        d = 1 - torch.exp(-h)
-        return h, d, d * (1 - d)
-    if name == 'LeakyReLU':
-        h = nn.functional.leaky_relu(a)
-        return h, torch.where(h > 0, one, 0.01 * one), torch.zeros_like(a)
-    raise ValueError(f'no closed form for activation {name!r}')
+    if name not in cover.ACTS:
+        raise ValueError(f'no closed form for activation {name!r}')
+    act, first, second = cover.ACTS[name]
+    h = act(a)
+    d = first(h)
+    return h, d, second(h, d)
 
 
 def hutchinson_closed_form(weights, biases, activation: str, t, z, e, latent=None, k_bar=None, q_bar=None):
@@ -205,7 +202,7 @@ class _CNFTrain(torch.autograd.Function):
         n_steps = len(grid) - 1
         ckpt = torch.empty(n_steps, *x2.shape, dtype=torch.float32, device=x2.device)
         y, ldj = module._train_forward(x2, lat2, e2, name, step, grid, ckpt)
-        ctx.module, ctx.solve = module, (name, step, grid)
+        ctx.module, ctx.grid = module, Grid(name, step, grid)
         ctx.has_latent = lat2 is not None
         ctx.save_for_backward(ckpt, e2, *( [lat2] if lat2 is not None else []), *[p for p in params if p is not None])
         ctx.bias_mask = [p is not None for p in params]
@@ -214,7 +211,7 @@ class _CNFTrain(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy, gldj):
-        module, (name, step, grid) = ctx.module, ctx.solve
+        module = ctx.module
         saved = list(ctx.saved_tensors)
         ckpt, e2 = saved[0], saved[1]
         lat2 = saved[2] if ctx.has_latent else None
@@ -238,8 +235,7 @@ class _CNFTrain(torch.autograd.Function):
             grads.dW[i], grads.db[i] = _hip.ptr(gW), _hip.ptr(gb)
             out += [gW, gb]
         _hip.call('sx_cnf_train_bwd', e2, ctypes.byref(d), ckpt.data_ptr(), _hip.ptr(lat2), e2.data_ptr(), gy.data_ptr(), gldj.data_ptr(),
-                  gx.data_ptr(), _hip.ptr(glat), partial.data_ptr(), ctypes.byref(grads), n, _hip.CNF_SOLVERS[name], len(grid) - 1,
-                  float(grid[0]), float(grid[-1]), float(step or 0.0))
+                  gx.data_ptr(), _hip.ptr(glat), partial.data_ptr(), ctypes.byref(grads), *ctx.grid.c_args(n))
         del keep
         return (None, None, None, None, gx if need[4] else None, glat, None, *out)
 
@@ -334,6 +330,18 @@ def _rk_step(func, solver: str, t, t_next, y):
     return tuple((((k + (b + c) * 3.0) + d) * h) * 0.125 for k, b, c, d in zip(k1, k2, k3, k4))
 
 
+class _Tier(NamedTuple):
+    """One inference kernel in ContinuousTransform's order of preference."""
+    entry: str                 # the library's entry point
+    applies: Callable          # (ODEfunc, x.dim()) -> does this setting ask for what the kernel computes?
+    plan: Callable             # (transform, x.shape, latent_dim, trace, device) -> (net descriptor, keep-alive list) | None
+
+
+def _set_setting(func, nd: int) -> bool:
+    """Sets (..., N, dim) under no divergence or the exact divergence of a set net."""
+    return nd >= 2 and (func.divergence == 'none' or func.exact_set_trace())
+
+
 class ContinuousTransform(Transform):
     """Continuous normalizing flow dx/dt = net(t, x, latent) from 0 to T (cnf.py:102-262).
 
@@ -381,41 +389,33 @@ class ContinuousTransform(Transform):
     def _grid(self, reverse: bool):
         name, step = self._solver()
         t0, t1 = (self.T, 0.0) if reverse else (0.0, self.T)
-        return name, step, fixed_grid(t0, t1, step)
+        return Grid(name, step, fixed_grid(t0, t1, step))
 
-    # ---- the kernel plan --------------------------------------------------------------------------------------------------------
+    # ---- the kernel plans: (net descriptor, keep-alive list), or None outside the kernel's coverage -----------------------------
     def _kernel_net(self, latent_dim: int, want_ldj: bool, device):
-        """(sx_cnf_net, keep-alive list) for sx_cnf_flow, or None when the ODE function is outside its coverage."""
+        """(sx_cnf_net, keep-alive list [W1, b1, W2, b2, ...(, trace constants)]) for sx_cnf_flow, or None when the ODE function is
+        outside its coverage."""
         diffeq = self.odefunc.diffeq
         if type(diffeq) is not DiffeqMLP or type(diffeq.net) is not MLP:
             return None
         mlp = diffeq.net
-        if mlp._wrapped or mlp.final_activation_name is not None or _hip.ACT_CODES.get(mlp.activation_name, 99) > 6:
+        lins = cover.linear_stack(mlp.net)
+        if mlp._wrapped or mlp.final_activation_name is not None or lins is None or len(lins) not in (2, 3):
             return None
-        layers = list(mlp.net)
-        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters (MLP also takes an instance)
-        for m in layers[1::2]:
-            if type(m) is not getattr(nn, mlp.activation_name) or _ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True:
-                return None
-        lins = [m for m in layers if isinstance(m, nn.Linear)]
-        if len(lins) not in (2, 3) or len(layers) != 2 * len(lins) - 1 or any(isinstance(m, nn.Linear) != (i % 2 == 0)
-                                                                              for i, m in enumerate(layers)):
+        # (MLP also takes an activation instance)
+        if not cover.kernel_activation(mlp.activation_name, list(mlp.net)[1::2]):
             return None
         if not 1 <= self.dim <= _hip.CNF_MAX_DIM or lins[0].in_features != 1 + self.dim + latent_dim or lins[0].in_features > 128:
             return None
         if lins[-1].out_features != self.dim or any(l.out_features > 128 for l in lins[:-1]):
             return None
+        keep = [p for lin in lins for p in (lin.weight, lin.bias)]
+        if not cover.kernel_tensors([p for p in keep if p is not None], device):
+            return None
         d = _hip.sx_cnf_net()
-        keep = []
         for i, lin in enumerate(lins):
-            W, b = lin.weight.detach(), (None if lin.bias is None else lin.bias.detach())
-            if W.dtype != torch.float32 or not W.is_contiguous() or W.device != device:
-                return None
-            if b is not None and (b.dtype != torch.float32 or not b.is_contiguous()):
-                return None
-            keep += [W, b]
-            d.layer[i].W, d.layer[i].b = W.data_ptr(), (0 if b is None else b.data_ptr())
-            d.layer[i].out_dim, d.layer[i].in_dim = W.shape
+            d.layer[i].W, d.layer[i].b = lin.weight.data_ptr(), (0 if lin.bias is None else lin.bias.data_ptr())
+            d.layer[i].out_dim, d.layer[i].in_dim = lin.weight.shape
         d.n_layers, d.dim, d.latent_dim, d.act = len(lins), self.dim, latent_dim, _hip.ACT_CODES[mlp.activation_name]
         if want_ldj:
             tc = self._trace_constants([l.weight for l in lins], device)
@@ -442,7 +442,7 @@ class ContinuousTransform(Transform):
         ldj = torch.empty(n, dtype=torch.float32, device=x2.device)
         if n:
             _hip.call('sx_cnf_train_fwd', x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), e2.data_ptr(), y.data_ptr(), ldj.data_ptr(),
-                      _hip.ptr(ckpt), n, _hip.CNF_SOLVERS[name], len(grid) - 1, float(grid[0]), float(grid[-1]), float(step or 0.0))
+                      _hip.ptr(ckpt), *Grid(name, step, grid).c_args(n))
         del keep
         return y, ldj
 
@@ -465,8 +465,7 @@ class ContinuousTransform(Transform):
             with torch.no_grad():
                 tc = trace_constants([w.detach().to(torch.float64) for w in weights], self.dim)
                 if tc.dim() == 2:
-                    tiles = lambda n: 1 if n <= 32 else 2 if n <= 64 else 4
-                    P = 32 * max(tiles(tc.shape[0]), tiles(tc.shape[1]))
+                    P = 32 * max(cover.tiles(tc.shape[0]), cover.tiles(tc.shape[1]))
                     full = torch.zeros(P, P, dtype=torch.float64, device=device)
                     full[:tc.shape[0], :tc.shape[1]] = tc
                     tc = full
@@ -480,9 +479,7 @@ class ContinuousTransform(Transform):
             return None
         net = diffeq.net
         act = type(net.activation).__name__
-        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
-        if type(net.final_activation) is not nn.Identity or type(net.activation) is not getattr(nn, act, None) \
-                or _hip.ACT_CODES.get(act, 99) > 6 or _ACT_DEFAULTS.get(type(net.activation), lambda m: True)(net.activation) is not True:
+        if type(net.final_activation) is not nn.Identity or not cover.kernel_activation(act, [net.activation]):
             return None
         layers = list(net.layers)
         if len(layers) not in (2, 3) or any(type(l) is not EquivariantLayer or type(l.l1) is not nn.Linear or type(l.l2) is not nn.Linear
@@ -496,7 +493,7 @@ class ContinuousTransform(Transform):
         if any(l.l1.in_features != w or l.l2.in_features != w or l.l2.out_features != l.l1.out_features for l, w in zip(layers, widths)):
             return None
         tensors = [t for l in layers for t in (l.l1.weight, l.l2.weight, l.l1.bias, l.l2.bias)]
-        if any(t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device for t in tensors):
+        if not cover.kernel_tensors(tensors, device):
             return None
         image, offsets = self._set_constants(layers, set_size, device)
         d = _hip.sx_cnf_set_net()
@@ -526,7 +523,7 @@ class ContinuousTransform(Transform):
                 parts['w0'] = f64(layers[0].l1.weight)[:, 0] + f64(layers[0].l2.weight)[:, 0]
                 tc = set_trace_constants([(f64(l.l1.weight), f64(l.l2.weight)) for l in layers], self.dim, set_size)
                 if tc.dim() == 3:
-                    P = 32 * max((tc.shape[1] + 31) // 32, (tc.shape[2] + 31) // 32)
+                    P = 32 * max(cover.tiles(tc.shape[1]), cover.tiles(tc.shape[2]))
                     full = torch.zeros(5, P, P, dtype=torch.float64, device=device)
                     full[:, :tc.shape[1], :tc.shape[2]] = tc
                     tc = full
@@ -552,21 +549,15 @@ class ContinuousTransform(Transform):
         if any(type(m) is not MLP or m._wrapped or m.final_activation_name is not None for m in embeds):
             return None
         act = embeds[0].activation_name
-        lins = []
-        for m in embeds:
-            layers = list(m.net)
-            if len(layers) not in (1, 3) or any(type(l) is not type(layers[0]) for l in layers[0::2]) or not isinstance(layers[0], nn.Linear):
-                return None
-            if len(layers) == 3:
-                # the in-kernel activations and derivatives are those of torch's DEFAULT parameters, the same in the three embeddings
-                a = layers[1]
-                if m.activation_name != act or type(a) is not getattr(nn, act, None) or _hip.ACT_CODES.get(act, 99) > 6 \
-                        or _ACT_DEFAULTS.get(type(a), lambda m: True)(a) is not True:
-                    return None
-            lins.append(layers[0::2])
+        lins = [cover.linear_stack(m.net) for m in embeds]
+        if lins[0] is None or len(lins[0]) not in (1, 2) or any(l is None or len(l) != len(lins[0]) for l in lins):
+            return None
         n_hidden = len(lins[0]) - 1
+        # (one activation, the same in the three embeddings)
+        if n_hidden and not all(m.activation_name == act and cover.kernel_activation(act, [m.net[1]]) for m in embeds):
+            return None
         proj = net.proj
-        if any(len(l) != n_hidden + 1 for l in lins) or not isinstance(proj, nn.Linear):
+        if not isinstance(proj, nn.Linear):
             return None
         E, in_dim = lins[0][-1].out_features, 1 + self.dim + latent_dim
         H1 = lins[0][0].out_features
@@ -574,7 +565,7 @@ class ContinuousTransform(Transform):
                for l in lins) or proj.in_features != E or proj.out_features != self.dim:
             return None
         tensors = [t for l in lins for lin in l for t in (lin.weight, lin.bias)] + [proj.weight, proj.bias]
-        if any(t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device for t in tensors):
+        if not cover.kernel_tensors(tensors, device):
             return None
         d = _hip.sx_cnf_attn_net()
         for i, l in enumerate(lins):
@@ -594,12 +585,9 @@ class ContinuousTransform(Transform):
         not covered) for sx_cnf_exact_flow or -- with a `set_size` -- sx_cnf_exact_set_flow, or None outside the kernel's coverage."""
         if s is None:
             return None
-        # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
-        if any(_ACT_DEFAULTS.get(type(m), lambda m: True)(m) is not True for m in s['activations']):
-            return None
         is_set = set_size is not None
         guards = (exact_trace.kernel_tensors_set if is_set else exact_trace.kernel_tensors)(s)
-        if any(g.dtype != torch.float32 or not g.is_contiguous() or g.device != device for g in guards):
+        if not cover.kernel_tensors(guards, device):
             return None
 
         def build():
@@ -632,14 +620,14 @@ class ContinuousTransform(Transform):
         return self._exact_plan(s, latent_dim, device, set_size)
 
     # ---- the two paths ----------------------------------------------------------------------------------------------------------
-    def _solve_kernel(self, plan, x2, lat2, name, step, grid, want_ldj, entry='sx_cnf_flow'):
+    def _solve_kernel(self, entry, plan, x2, lat2, grid, want_ldj):
+        """One launch of an inference tier's entry point on rows -> (y, ldj [n] | None without `want_ldj`)."""
         d, keep = plan
         n = x2.shape[0]
         y = torch.empty_like(x2)
         ldj = torch.empty(n, dtype=torch.float32, device=x2.device) if want_ldj else None
         if n:
-            _hip.call(entry, x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), y.data_ptr(), _hip.ptr(ldj), n,
-                      _hip.CNF_SOLVERS[name], len(grid) - 1, float(grid[0]), float(grid[-1]), float(step or 0.0), int(want_ldj))
+            _hip.call(entry, x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), y.data_ptr(), _hip.ptr(ldj), *grid.c_args(n), int(want_ldj))
         del keep
         return y, ldj
 
@@ -665,72 +653,78 @@ class ContinuousTransform(Transform):
         with torch.no_grad():
             return self._solve_composed(x.to(torch.float32), latent, mask, name, grid, False)
 
+    # ---- how a call picks its kernel --------------------------------------------------------------------------------------------
+    # The inference tiers in order of preference: the first whose setting holds and whose planner returns a plan runs.  Exact-trace sets
+    # come before exact-trace because the set type is the narrower match; sets come before attention because the two planners key on
+    # disjoint module types.  `applies` sees the ODEfunc and x.dim(); `plan` the transform, x.shape, the latent width, whether the kernel
+    # accumulates the log-det, and the device.
+    _TIERS = (
+        _Tier('sx_cnf_flow', lambda func, nd: func.divergence == 'none' or func.exact_trace(),
+              lambda f, shape, ld, trace, dev: f._kernel_net(ld, trace, dev)),
+        # (the choice does not depend on set_data: ODEfunc ignores it under 'exact')
+        _Tier('sx_cnf_exact_set_flow',
+              lambda func, nd: func.divergence == 'exact' and nd >= 2 and type(func.diffeq) is exact_trace.DiffeqExactTraceDeepSet,
+              lambda f, shape, ld, trace, dev: f._exact_set_kernel_net(shape[-2], ld, dev)),
+        _Tier('sx_cnf_exact_flow', lambda func, nd: func.divergence == 'exact' and not func.set_data,
+              lambda f, shape, ld, trace, dev: f._exact_kernel_net(ld, dev)),
+        _Tier('sx_cnf_set_flow', _set_setting, lambda f, shape, ld, trace, dev: f._set_kernel_net(shape[-2], ld, dev)),
+        _Tier('sx_cnf_attn_flow', _set_setting, lambda f, shape, ld, trace, dev: f._attn_kernel_net(shape[-2], ld, dev)),
+    )
+
+    def _choose(self, shape, latent_dim: int, masked: bool, graph: bool, want_ldj: bool, device):
+        """What runs a call on x of `shape` -> (route, plan, trace).  route: 'train' (the Hutchinson pair, asked first: it also serves
+        calls that want a graph), a tier's entry point (no graph), or 'composed' (plan None; every masked call).  trace: does the kernel
+        accumulate the log-det.  Host code only: `device` may be the CPU."""
+        func = self.odefunc
+        trace = want_ldj and func.divergence != 'none'
+        if masked:
+            return 'composed', None, trace
+        if func.divergence == 'approximate' and self.training and not func.set_data:
+            plan = self._train_kernel_net(latent_dim, device)
+            if plan is not None:
+                return 'train', plan, trace
+        if not graph:
+            for tier in self._TIERS:
+                plan = tier.plan(self, shape, latent_dim, trace, device) if tier.applies(func, len(shape)) else None
+                if plan is not None:
+                    return tier.entry, plan, trace
+        return 'composed', None, trace
+
     def _solve(self, x, latent, mask, reverse: bool, want_ldj: bool):
         _hip.require_device(x, 'x')
-        name, step, grid = self._grid(reverse)
-        func = self.odefunc
+        grid = self._grid(reverse)
         out_dtype = x.dtype
         x = x.to(torch.float32)
+        latent_dim = 0 if latent is None else latent.shape[-1]
         if latent is not None:
-            latent = latent.to(device=x.device, dtype=torch.float32).expand(*x.shape[:-1], latent.shape[-1])
-        n_evals = (len(grid) - 1) * STAGES[name]
+            latent = latent.to(device=x.device, dtype=torch.float32).expand(*x.shape[:-1], latent_dim)
         graph = graph_wanted(self, x, latent)
-        plan, entry = None, 'sx_cnf_flow'
-        if func.divergence == 'approximate' and self.training and not func.set_data and mask is None \
-                and self._train_kernel_net(0 if latent is None else latent.shape[-1], x.device) is not None:
-            # training with the Hutchinson estimator: one forward launch (with checkpoints when a graph is wanted) and one adjoint
-            e = self._draw_noise(x)
-            x2, lead = flatten_rows(x)
-            lat2 = None if latent is None else flatten_rows(latent)[0].contiguous()
-            x2, e2 = x2.contiguous(), flatten_rows(e)[0].contiguous()
-            if graph:
-                lins = [m for m in func.diffeq.net.net if isinstance(m, nn.Linear)]
-                y2, ldj = _CNFTrain.apply(self, name, step, grid, x2, lat2, e2, *[p for l in lins for p in (l.weight, l.bias)])
-            else:
-                with torch.no_grad():
-                    y2, ldj = self._train_forward(x2, lat2, e2, name, step, grid)
-            y, ldj = y2.reshape(*lead, self.dim), (ldj.reshape(*lead, 1) if want_ldj else None)
-            self._last_path = 'kernel'
-            func._num_evals.fill_(n_evals)
-            return (y.to(out_dtype) if out_dtype == torch.bfloat16 else y), ldj
-        if not graph and mask is None and (func.divergence == 'none' or func.exact_trace()):
-            ld = 0 if latent is None else latent.shape[-1]
-            trace = want_ldj and func.divergence != 'none'
-            plan = self._kernel_net(ld, trace, x.device)
-        elif not graph and mask is None and func.divergence == 'exact' and type(func.diffeq) is exact_trace.DiffeqExactTraceDeepSet:
-            if x.dim() >= 2:                                          # (the choice does not depend on set_data: ODEfunc ignores it here)
-                trace, entry = want_ldj, 'sx_cnf_exact_set_flow'
-                plan = self._exact_set_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
-        elif not graph and mask is None and func.divergence == 'exact' and not func.set_data:
-            trace, entry = want_ldj, 'sx_cnf_exact_flow'
-            plan = self._exact_kernel_net(0 if latent is None else latent.shape[-1], x.device)
-        if plan is None and not graph and mask is None and x.dim() >= 2 and (func.divergence == 'none' or func.exact_set_trace()):
-            trace, entry = want_ldj and func.divergence != 'none', 'sx_cnf_set_flow'
-            plan = self._set_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
-            if plan is None:
-                entry = 'sx_cnf_attn_flow'
-                plan = self._attn_kernel_net(x.shape[-2], 0 if latent is None else latent.shape[-1], x.device)
-        if plan is not None:
+        route, plan, trace = self._choose(x.shape, latent_dim, mask is not None, graph, want_ldj, x.device)
+        if route == 'composed':
+            with torch.set_grad_enabled(graph):
+                y, ldj = self._solve_composed(x, latent, mask, grid.name, grid.points, graph)
+        else:
             x2, lead = flatten_rows(x)
             lat2 = None if latent is None else flatten_rows(latent)[0]
-            with torch.no_grad():
-                y2, ldj = self._solve_kernel(plan, x2, lat2, name, step, grid, trace, entry)
-                if want_ldj and ldj is None:
-                    ldj = torch.zeros(x2.shape[0], dtype=torch.float32, device=x.device)
-            y = y2.reshape(*lead, self.dim)
-            ldj = None if ldj is None else ldj.reshape(*lead, 1)
-            self._last_path = 'kernel'
-        else:
-            if graph:
-                y, ldj = self._solve_composed(x, latent, mask, name, grid, True)
-            else:
+            if route != 'train':
                 with torch.no_grad():
-                    y, ldj = self._solve_composed(x, latent, mask, name, grid, False)
-            self._last_path = 'composed'
-        func._num_evals.fill_(n_evals)
-        if out_dtype == torch.bfloat16:
-            y = y.to(out_dtype)
-        return y, ldj
+                    y2, ldj = self._solve_kernel(route, plan, x2, lat2, grid, trace)
+            else:
+                # training with the Hutchinson estimator: one forward launch (with checkpoints when a graph is wanted) and one adjoint
+                e2 = flatten_rows(self._draw_noise(x))[0]
+                if graph:
+                    y2, ldj = _CNFTrain.apply(self, *grid, x2, lat2, e2, *plan[1])         # (the keep-alive list: W1, b1, W2, b2, ...)
+                else:
+                    with torch.no_grad():
+                        y2, ldj = self._train_forward(x2, lat2, e2, *grid)
+            if not want_ldj:
+                ldj = None
+            elif ldj is None:                                           # (divergence 'none')
+                ldj = torch.zeros(x2.shape[0], dtype=torch.float32, device=x.device)
+            y, ldj = y2.reshape(*lead, self.dim), (None if ldj is None else ldj.reshape(*lead, 1))
+        self._last_path = 'composed' if route == 'composed' else 'kernel'
+        self.odefunc._num_evals.fill_((len(grid.points) - 1) * STAGES[grid.name])
+        return (y.to(out_dtype) if out_dtype == torch.bfloat16 else y), ldj
 
     # ---- reference method set ---------------------------------------------------------------------------------------------------
     def forward_and_log_det_jacobian(self, x, latent=None, mask=None, *, reverse=False, **kwargs):

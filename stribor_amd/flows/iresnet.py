@@ -21,6 +21,7 @@ from torch.nn.utils.spectral_norm import SpectralNorm
 
 from .. import _hip
 from ..flow import Transform, flatten_rows, graph_wanted
+from ..net.cover import linear_stack
 from ..net.mlp import MLP
 from ..net.time_net import TimeFourier, TimeIdentity, TimeLinear, TimeLog, TimeTanh
 
@@ -102,9 +103,6 @@ class _IResNetBase(Transform):
         self.net = MLP(dim, hidden_dims, dim, activation, final_activation, nn_linear_wrapper_func=wrapper)
 
     # ---- the pieces -----------------------------------------------------------------------------------------------------
-    def _linears(self):
-        return [m for m in self.net.net if isinstance(m, nn.Linear)]
-
     def _time(self):
         return getattr(self, 'time_net', None)
 
@@ -155,23 +153,9 @@ class _IResNetBase(Transform):
         fa = net.final_activation_name
         if fa is not None and fa not in _hip.ACT_CODES:
             return None
-        layers = list(net.net)
-        lins = self._linears()
-        if not 1 <= len(lins) <= _hip.RESNET_MAX_LAYERS:
+        lins = linear_stack(net.net, final_activation=fa is not None)
+        if lins is None or len(lins) > _hip.RESNET_MAX_LAYERS:
             return None
-        # the layer sequence must be exactly Linear (act Linear)* [final act]
-        expect = []
-        for i in range(len(lins)):
-            if i:
-                expect.append('act')
-            expect.append('lin')
-        if fa is not None:
-            expect.append('final')
-        if len(layers) != len(expect):
-            return None
-        for m, e in zip(layers, expect):
-            if (e == 'lin') != isinstance(m, nn.Linear):
-                return None
         d = _hip.sx_resnet_net()
         keep, wrapped = [], []
         for i, lin in enumerate(lins):

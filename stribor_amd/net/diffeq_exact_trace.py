@@ -23,6 +23,8 @@ import torch
 import torch.nn as nn
 
 from ..util.flatten_params import flatten_params
+from . import cover
+from .cover import tiles as _tiles
 from .diagjac import FuncAndDiagJac
 from .diffeq import DiffeqMLP
 from .diffeq_zero_trace import DiffeqZeroTraceDeepSet, DiffeqZeroTraceMLP, ZeroTraceEquivariantEncoder
@@ -78,15 +80,6 @@ class DiffeqExactTraceDeepSet(DiffeqExactTrace):
 
 
 # ---- the MLP instance, layer by layer ---------------------------------------------------------------------------------------------
-_ACTS = {'Identity': (lambda v: v, lambda a: torch.ones_like(a)),
-         'Tanh': (torch.tanh, lambda a: 1 - a * a),
-         'ReLU': (torch.relu, lambda a: (a > 0).to(a.dtype)),
-         'Sigmoid': (torch.sigmoid, lambda a: a * (1 - a)),
-         'ELU': (nn.functional.elu, lambda a: torch.where(a > 0, torch.ones_like(a), a + 1)),
-         'Softplus': (nn.functional.softplus, lambda a: 1 - torch.exp(-a)),
-         'LeakyReLU': (nn.functional.leaky_relu, lambda a: torch.where(a > 0, torch.ones_like(a), torch.full_like(a, 0.01)))}
-
-
 def _structure(net):
     """The layers of a DiffeqExactTraceMLP-shaped module -> dict, or None when it is not the plain instance: two MADEs without a final
     activation, a DiffeqMLP over a plain MLP without one, one activation name and the same hidden widths in all three."""
@@ -126,7 +119,7 @@ def _structure(net):
 def _dimwise(s, t, x2, h, lat2, want_jac, cast, dtype):
     """The dimwise net of a structure dict on rows x2 [R, D] with h [R, D, d_h] and lat2 [R, L] | None -> (f [R, D], jac [R, D] | None):
     value and tangent d/dx_i side by side."""
-    act, dact = _ACTS[s['act']]
+    act, dact, _ = cover.ACTS[s['act']]
     d_h = s['d_h']
     dw = s['dimwise']
     W1, b1 = cast(dw[0].weight), cast(dw[0].bias)
@@ -157,9 +150,9 @@ def closed_form(net, t, x, latent=None, want_jac: bool = True, dtype=None):
         f_i   = w_last . act(z_last) + b_last,                                                jac_i = w_last . tau_last
     (act' from the activation's OUTPUT, as the kernel takes it).  This is what sx_cnf_exact_flow evaluates per stage."""
     s = _structure(net)
-    if s is None or s['act'] not in _ACTS or not s['hidden']:
+    if s is None or s['act'] not in cover.ACTS or not s['hidden']:
         raise NotImplementedError('closed_form: a plain DiffeqExactTraceMLP with hidden layers and an activation of the kernel\'s set')
-    act, dact = _ACTS[s['act']]
+    act = cover.ACTS[s['act']][0]
     dtype = dtype or x.dtype
     D, d_h = s['D'], s['d_h']
     cast = lambda p: None if p is None else p.detach().to(device=x.device, dtype=dtype)
@@ -185,10 +178,6 @@ def _kmap(r, h):
     return (r & 3) + 8 * (r >> 2) + 4 * h
 
 
-def _tiles(n: int) -> int:
-    return 1 if n <= 32 else 2
-
-
 def _out_tiles(d_h: int) -> int:
     return 1 if d_h <= 2 else 2 if d_h <= 4 else 4
 
@@ -207,16 +196,14 @@ def _fragment_image(Wp: np.ndarray) -> np.ndarray:
 
 def _covered(s, dim: int, latent_dim: int):
     """A structure dict (or None) -> itself when it is inside the ranges the two exact-trace kernels share, else None."""
-    from .. import _hip
     if s is None or s['D'] != dim or s['L'] != latent_dim:
         return None
     if not 1 <= dim <= MAX_DIM or not 1 <= s['d_h'] <= MAX_DH or latent_dim > MAX_LATENT:
         return None
     if len(s['hidden']) not in (1, 2) or any(not 1 <= w <= MAX_HIDDEN for w in s['hidden']):
         return None
-    if _hip.ACT_CODES.get(s['act'], 99) > 6:
-        return None
-    return s
+    # the in-kernel activations and derivatives are those of torch's DEFAULT parameters
+    return s if cover.kernel_activation(s['act'], s['activations']) else None
 
 
 def kernel_coverage(net, dim: int, latent_dim: int):
@@ -370,9 +357,9 @@ def closed_form_set(net, t, x, latent=None, want_jac: bool = True, dtype=None):
         h_i[d, :] = MADE(x_i)[d, :] + p_i                       (mask * weight)
     then the dimwise net with its tangent, as `closed_form`.  This is what sx_cnf_exact_set_flow evaluates per stage."""
     s = _structure_set(net)
-    if s is None or s['act'] not in _ACTS or not s['hidden']:
+    if s is None or s['act'] not in cover.ACTS or not s['hidden']:
         raise NotImplementedError('closed_form_set: a plain DiffeqExactTraceDeepSet with hidden layers and an activation of the kernel\'s set')
-    act, _ = _ACTS[s['act']]
+    act = cover.ACTS[s['act']][0]
     dtype = dtype or x.dtype
     D, d_h = s['D'], s['d_h']
     cast = lambda p: None if p is None else p.detach().to(device=x.device, dtype=dtype)
