@@ -878,6 +878,54 @@ size_t sx_cnf_exact_set_lds_bytes(const sx_cnf_exact_set_net *net_host);
 int sx_cnf_exact_set_flow(const sx_cnf_exact_set_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                           int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- exact-trace continuous normalizing flow over sets with attention (ContinuousTransform with divergence='exact' over
+ * DiffeqExactTraceAttention: stribor/net/diffeq_exact_trace.py:104-130, diffeq_zero_trace.py:179-227) ----
+ * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  hidden = [E] or [H1, E]; E is the
+ * embedding, split over n_heads heads of width dh = E / n_heads.  For element i, dimension d: q_i[d, :] = MADE_q(x_i)[d, :] (E values,
+ * MADE column e * dim + d), k_j = K(x_j), v_j = V(x_j) (one Linear, or Linear - act - Linear; no time, no latent); per head s_ij =
+ * dh^-1/2 q_i[d] . k_j for j != i and -inf for j == i, p_i = softmax_j(s_ij) (a row without keys: zeros, so N == 1 gives o = 0),
+ * o_i[d] = sum_j p_ij v_j; h_i[d, :] = P o_i[d] + b (d_h values); f_i[d] = g(t, x_i[d], h_i[d, :], latent_i), jac_i[d] = dg/dx at fixed
+ * h, as sx_cnf_exact_flow.  A set with a non-finite k or v value comes back NaN in every element; no other set is affected.
+ * The image is sx_cnf_exact_net's in tiles, positions and vectors, with these parts, in this order (sizes in floats; KT = HT with two
+ * hidden layers, else 1 -- the last layers then read the state's positions; slot = 8, 16 or 32, the smallest that holds E; per = 32 /
+ * slot; QT = ceil(dim / per) <= 4):
+ *   q (MADE):  (two hidden layers: W1 [HT x 1 tiles], b1 [32 HT],) W_last [QT x KT tiles], b_last [32 QT]: mask * weight, column
+ *              e * dim + d at position 32 (d / per) + (d % per) slot + e
+ *   K, then V: (two hidden layers: W1 [HT x 1 tiles], b1 [32 HT],) W_last [1 x KT tiles], b_last [32]
+ *   proj:      P [1 x 1 tile], b [32]: output slot kk at position kmap(kk >> 1, kk & 1)
+ *   dimwise:   as sx_cnf_exact_net's
+ * The kernel keeps the k / v exchange (2 x 128 x 36 floats) and 128 set flags behind the image in LDS. */
+#define SX_CNF_EXACT_ATTN_MAX_DIM    8
+#define SX_CNF_EXACT_ATTN_MAX_DH     8
+#define SX_CNF_EXACT_ATTN_MAX_LATENT 64
+#define SX_CNF_EXACT_ATTN_MAX_HIDDEN 64
+#define SX_CNF_EXACT_ATTN_MAX_EMBED  32
+#define SX_CNF_EXACT_ATTN_MAX_SIZE   128
+typedef struct {
+    const float *image;     /* device, 16-byte aligned: the LDS image above                                             */
+    const float *w_latent;  /* device, 16-byte aligned: the dimwise W1[:, 2 + d_h ..], row-major [32 HT][32 ceil(latent_dim / 32)],
+                               zero-padded; NULL iff latent_dim == 0                                                     */
+    int32_t image_floats;   /* must equal sx_cnf_exact_attn_lds_bytes / 4 - (2 * 128 * 36 + 128)                        */
+    int32_t dim;            /* 1..SX_CNF_EXACT_ATTN_MAX_DIM, and QT <= 4                                                */
+    int32_t d_h;            /* 1..SX_CNF_EXACT_ATTN_MAX_DH                                                              */
+    int32_t latent_dim;     /* 0..SX_CNF_EXACT_ATTN_MAX_LATENT                                                          */
+    int32_t n_hidden;       /* 1 or 2: the dimwise net's hidden layers; q, K and V have one fewer                       */
+    int32_t hidden[2];      /* 1..SX_CNF_EXACT_ATTN_MAX_HIDDEN each; the last one is E <= SX_CNF_EXACT_ATTN_MAX_EMBED    */
+    int32_t act;            /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU, the same in q, K, V and the dimwise net             */
+    int32_t set_size;       /* 1..SX_CNF_EXACT_ATTN_MAX_SIZE                                                            */
+    int32_t n_heads;        /* 1, 2 or 4, dividing E                                                                    */
+} sx_cnf_exact_attn_net;
+
+/* Bytes of LDS of a launch for this network: the image plus the exchange; 0 for a network outside the coverage or one that does not
+ * fit SX_CNF_LDS_BYTES.  Reads the integer fields only. */
+size_t sx_cnf_exact_attn_lds_bytes(const sx_cnf_exact_attn_net *net_host);
+
+/* The arguments of sx_cnf_exact_set_flow; n_rows must be a multiple of set_size.  A workgroup takes 128 / S whole sets at a time, S the
+ * power of two that holds set_size (a set's block of row slots, aligned to S); a set's result does not depend, to the bit, on its
+ * position in the batch or on the other sets.  want_ldj == 0 skips the dimwise tangent (ldj may be NULL). */
+int sx_cnf_exact_attn_flow(const sx_cnf_exact_attn_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
+                           int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
+
 /* ---- continuous normalizing flow over sets (ContinuousTransform with set_data=True or divergence='compute_set' over DiffeqDeepset:
  * stribor/net/diffeq.py:78-94 around net/equivariant.py's EquivariantNet) ----
  * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  Equivariant layer l is

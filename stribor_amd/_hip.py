@@ -62,6 +62,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
            'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
            'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow',
+           'sx_cnf_exact_attn_lds_bytes', 'sx_cnf_exact_attn_flow',
            'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd',
            'sx_base_logprob', 'sx_normal_bwd_partial_floats', 'sx_normal_logprob_bwd', 'sx_mvn_lds_bytes', 'sx_mvn_logprob']
 
@@ -162,6 +163,12 @@ class sx_cnf_exact_set_net(C.Structure):
     _fields_ = [('image', C.c_void_p), ('w_latent', C.c_void_p), ('image_floats', C.c_int32), ('dim', C.c_int32), ('d_h', C.c_int32),
                 ('latent_dim', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 2), ('act', C.c_int32),
                 ('set_size', C.c_int32), ('pooling', C.c_int32)]
+
+
+class sx_cnf_exact_attn_net(C.Structure):
+    _fields_ = [('image', C.c_void_p), ('w_latent', C.c_void_p), ('image_floats', C.c_int32), ('dim', C.c_int32), ('d_h', C.c_int32),
+                ('latent_dim', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 2), ('act', C.c_int32),
+                ('set_size', C.c_int32), ('n_heads', C.c_int32)]
 
 
 class sx_attention_args(C.Structure):
@@ -320,6 +327,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_exact_set_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_set_net)]
     lib.sx_cnf_exact_set_flow.restype = i32
     lib.sx_cnf_exact_set_flow.argtypes = [C.POINTER(sx_cnf_exact_set_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_exact_attn_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_exact_attn_lds_bytes.argtypes = [C.POINTER(sx_cnf_exact_attn_net)]
+    lib.sx_cnf_exact_attn_flow.restype = i32
+    lib.sx_cnf_exact_attn_flow.argtypes = [C.POINTER(sx_cnf_exact_attn_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
     lib.sx_cnf_set_lds_bytes.restype = C.c_size_t
     lib.sx_cnf_set_lds_bytes.argtypes = [C.POINTER(sx_cnf_set_net), i32]
     lib.sx_cnf_set_flow.restype = i32

@@ -38,10 +38,7 @@
 //
 // Coverage: 1 <= N <= 128, dim <= 8, 1 + dim + latent_dim <= 33, embeddings [E] or [H1, E] with H1 <= 64 and E <= 32, 1, 2 or 4 heads
 // (dividing E), the seven activations of sx_cnf_common.h, biases present, no mask.
-#include "sx_cnf_common.h"
-
-#define CA_LD 36                                  /* row stride of the exchange areas (floats): 16-byte rows, conflict-free reads */
-#define CA_AREA (SX_CNF_ROWS * CA_LD)             /* one k (or v) area */
+#include "sx_cnf_attn_common.h"
 
 namespace {
 
@@ -61,53 +58,11 @@ struct ca_args {
     float t0, t1, step_size;
 };
 
-// where a lane stands in its workgroup's pass
-struct ca_pos {
-    int rho;            // row slot 0 .. SX_CNF_ROWS - 1
-    int first;          // the first slot of the row's set (a padding slot: itself)
-    int n;              // rows of that set (a padding slot: 1)
-    int kt_lo, kt_hi;   // the key tiles that hold rows of the wave's sets (wave-uniform)
-};
-
-// scores of the wave's queries (qm: zero outside the head's features [lo, hi)) against the 32 keys at `kb` (the tile's first row + (lane &
-// 31) rows + 4 h floats)
-__device__ __forceinline__ f32x16 ca_scores(const f32x16 &qm, const float *kb, int lo, int hi) {
-    f32x16 acc = {};
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (8 * g < hi && 8 * g + 8 > lo) {
-            const f32x4 k = *reinterpret_cast<const f32x4 *>(kb + 8 * g);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(k.x, qm[4 * g + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(k.y, qm[4 * g + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(k.z, qm[4 * g + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(k.w, qm[4 * g + 3], acc, 0, 0, 0);
-        }
-    }
-    return acc;
-}
-
-// acc += V^T w over the 32 keys of a tile: `vb` = the tile's first row + 4 h rows + (lane & 31) floats; e_in: the lane's feature is the head's
-__device__ __forceinline__ void ca_pv(f32x16 &acc, const f32x16 &w, const float *vb, bool e_in) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const float v = vb[((r & 3) + 8 * (r >> 2)) * CA_LD];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(e_in ? v : 0.f, w[r], acc, 0, 0, 0);
-    }
-}
-
 // element hd (uniform, 0..3) of four per-head scalars kept in registers
 __device__ __forceinline__ float ca_get(const float (&v)[4], int hd) { return hd == 0 ? v[0] : hd == 1 ? v[1] : hd == 2 ? v[2] : v[3]; }
 __device__ __forceinline__ void ca_put(float (&v)[4], int hd, float x) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = hd == i ? x : v[i];
-}
-
-__device__ __forceinline__ bool ca_valid(const ca_pos &p, int js, bool md) { return js >= p.first && js < p.first + p.n && !(md && js == p.rho); }
-
-__device__ __forceinline__ float ca_finite(float v, bool &bad) {
-    const bool ok = fabsf(v) < INFINITY;
-    bad = bad || !ok;
-    return ok ? v : 0.f;
 }
 
 // f(t, x) and -- when `want` -- tr = the row's share of the set's divergence, for the wave's 32 rows.  `area`: which exchange area

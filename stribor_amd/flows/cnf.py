@@ -28,7 +28,11 @@ dim <= 16, d_h <= 8, latent <= 64) is ONE launch of ``sx_cnf_exact_flow`` under 
 into the kernel's LDS image once (cached, guarded on weights and masks) and the Jacobian diagonal is a forward-mode tangent beside the
 value.  Over a ``net.DiffeqExactTraceDeepSet`` on sets (..., N, dim) (N <= 128, the same widths, sum / mean / max pooling) it is ONE
 launch of ``sx_cnf_exact_set_flow``: the same image scheme plus one ordered exchange through LDS per evaluation for the exclusive
-pooling.  Any other net under 'exact' runs the composition path over ``net.FuncAndDiagJac``.
+pooling.  Over a ``net.diffeq_exact_trace.DiffeqExactTraceAttention`` on sets (hidden_dims [E] or [H1, E] with H1 <= 64 and E <= 32, dim <= 8, at most four
+query tiles, 1, 2 or 4 heads, d_h <= 8, latent <= 64, N <= 128) it is ONE launch of ``sx_cnf_exact_attn_flow``: keys and values meet in
+LDS once per evaluation, dim attentions with the MADE's per-dimension queries run against them, and the trace is the dimwise net's
+tangent -- no tangent attention, where ``sx_cnf_attn_flow`` pays 1 + dim attentions for it.  Any other net under
+'exact' runs the composition path over ``net.FuncAndDiagJac``.
 
 Sets under ``set_data=True`` / ``divergence='compute_set'`` (or ``'none'``) over a ``net.DiffeqSelfAttention`` (embeddings of one or two
 Linear layers, hidden <= 64, embedding <= 32, 1, 2 or 4 heads, N <= 128, dim <= 8, dim + latent <= 32) are ONE launch of
@@ -37,9 +41,9 @@ coordinate (``net.self_attention_closed_form`` states it in torch) -- 1 + dim at
 ``divergence_exact_for_sets`` makes N * dim reverse passes (DESIGN.md "CNF on sets with attention").
 
 How a call picks its kernel is ``ContinuousTransform._choose`` over the table ``_TIERS``, in the order dense, exact-trace sets,
-exact-trace, sets, attention sets, after the training pair and before the composition path; ``_solve`` has one tail for every route.
+exact-trace attention sets, exact-trace, sets, attention sets, after the training pair and before the composition path; ``_solve`` has one tail for every route.
 One planner per kernel (``_kernel_net``, ``_train_kernel_net``, ``_set_kernel_net``, ``_attn_kernel_net``, ``_exact_kernel_net``,
-``_exact_set_kernel_net``) returns (net descriptor, keep-alive list) or None; the conditions they share -- the activation, the
+``_exact_set_kernel_net``, ``_exact_attn_kernel_net``) returns (net descriptor, keep-alive list) or None; the conditions they share -- the activation, the
 tensors, the ``Linear (act Linear)*`` stack, the tile count -- and the activations' derivatives are ``net.cover``'s.  ``Grid`` carries
 a solve's (solver, step, points) and yields the launches' common argument tail.
 """
@@ -56,7 +60,7 @@ from ..fused import ProgramCache
 from ..net import cover, diffeq_exact_trace as exact_trace
 from ..net.attention import SelfAttention
 from ..net.diffeq import DiffeqDeepset, DiffeqMLP, DiffeqSelfAttention
-from ..net.diffeq_zero_trace import DiffeqZeroTraceDeepSet
+from ..net.diffeq_zero_trace import DiffeqZeroTraceAttention, DiffeqZeroTraceDeepSet
 from ..net.equivariant import EquivariantLayer, EquivariantNet
 from ..net.mlp import MLP
 from ..util.divergence import divergence_approx, divergence_exact, divergence_exact_for_sets
@@ -580,32 +584,42 @@ class ContinuousTransform(Transform):
             return None
         return d, [t.detach() for t in tensors]
 
-    def _exact_plan(self, s, latent_dim: int, device, set_size=None):
-        """(net descriptor, keep-alive list) of an exact-trace structure dict `s` (exact_trace.kernel_coverage / kernel_coverage_set; None:
-        not covered) for sx_cnf_exact_flow or -- with a `set_size` -- sx_cnf_exact_set_flow, or None outside the kernel's coverage."""
+    # per kind of exact-trace kernel: (guards, image builder, descriptor, LDS size entry, floats of LDS behind the image, the net's own
+    # field <- the structure dict's key); the kind is also the cache key
+    _EXACT_KINDS = {
+        'exact': (exact_trace.kernel_tensors, exact_trace.kernel_image, 'sx_cnf_exact_net', 'sx_cnf_exact_lds_bytes', 0, None),
+        'exact_set': (exact_trace.kernel_tensors_set, exact_trace.kernel_image_set, 'sx_cnf_exact_set_net', 'sx_cnf_exact_set_lds_bytes',
+                      exact_trace.SET_EXCHANGE_FLOATS, ('pooling', lambda s: exact_trace.POOLINGS[s['pooling']])),
+        'exact_attn': (exact_trace.kernel_tensors_attn, exact_trace.kernel_image_attn, 'sx_cnf_exact_attn_net', 'sx_cnf_exact_attn_lds_bytes',
+                       exact_trace.ATTN_EXCHANGE_FLOATS, ('n_heads', lambda s: s['heads'])),
+    }
+
+    def _exact_plan(self, s, latent_dim: int, device, kind: str = 'exact', set_size=None):
+        """(net descriptor, keep-alive list) of an exact-trace structure dict `s` (exact_trace.kernel_coverage / kernel_coverage_set /
+        kernel_coverage_attn; None: not covered) for the kernel of `kind` ('exact': sx_cnf_exact_flow; 'exact_set' / 'exact_attn', with a
+        `set_size`: sx_cnf_exact_set_flow / sx_cnf_exact_attn_flow), or None outside the kernel's coverage."""
         if s is None:
             return None
-        is_set = set_size is not None
-        guards = (exact_trace.kernel_tensors_set if is_set else exact_trace.kernel_tensors)(s)
+        tensors, build_image, desc, lds_entry, behind, own = self._EXACT_KINDS[kind]
+        guards = tensors(s)
         if not cover.kernel_tensors(guards, device):
             return None
 
         def build():
-            image, w_latent = (exact_trace.kernel_image_set if is_set else exact_trace.kernel_image)(s)
+            image, w_latent = build_image(s)
             image = torch.from_numpy(image).to(device)
             return image, (None if w_latent is None else torch.from_numpy(w_latent).contiguous().to(device))
-        image, w_latent = self._trace.get(('exact_set' if is_set else 'exact', str(device)), build, guards=guards)
-        d = _hip.sx_cnf_exact_set_net() if is_set else _hip.sx_cnf_exact_net()
+        image, w_latent = self._trace.get((kind, str(device)), build, guards=guards)
+        d = getattr(_hip, desc)()
         d.image, d.w_latent, d.image_floats = image.data_ptr(), (0 if w_latent is None else w_latent.data_ptr()), image.numel()
         d.dim, d.d_h, d.latent_dim, d.n_hidden, d.act = self.dim, s['d_h'], latent_dim, len(s['hidden']), _hip.ACT_CODES[s['act']]
         for i, w in enumerate(s['hidden']):
             d.hidden[i] = w
-        floats = image.numel()
-        if is_set:
-            d.set_size, d.pooling = set_size, exact_trace.POOLINGS[s['pooling']]
-            floats += exact_trace.SET_EXCHANGE_FLOATS
-        lds = (_hip.lib().sx_cnf_exact_set_lds_bytes if is_set else _hip.lib().sx_cnf_exact_lds_bytes)(d)
-        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * floats:
+        if own is not None:
+            d.set_size = set_size
+            setattr(d, own[0], own[1](s))
+        lds = getattr(_hip.lib(), lds_entry)(d)
+        if lds == 0 or lds > _hip.CNF_LDS_BYTES or lds != 4 * (image.numel() + behind):
             return None
         return d, [image, w_latent]
 
@@ -617,7 +631,13 @@ class ContinuousTransform(Transform):
         """(sx_cnf_exact_set_net, keep-alive list) for sx_cnf_exact_set_flow over sets of `set_size` elements, or None when the ODE
         function is outside its coverage."""
         s = exact_trace.kernel_coverage_set(self.odefunc.diffeq, self.dim, latent_dim, set_size)
-        return self._exact_plan(s, latent_dim, device, set_size)
+        return self._exact_plan(s, latent_dim, device, 'exact_set', set_size)
+
+    def _exact_attn_kernel_net(self, set_size: int, latent_dim: int, device):
+        """(sx_cnf_exact_attn_net, keep-alive list) for sx_cnf_exact_attn_flow over sets of `set_size` elements, or None when the ODE
+        function is outside its coverage."""
+        s = exact_trace.kernel_coverage_attn(self.odefunc.diffeq, self.dim, latent_dim, set_size)
+        return self._exact_plan(s, latent_dim, device, 'exact_attn', set_size)
 
     # ---- the two paths ----------------------------------------------------------------------------------------------------------
     def _solve_kernel(self, entry, plan, x2, lat2, grid, want_ldj):
@@ -655,7 +675,7 @@ class ContinuousTransform(Transform):
 
     # ---- how a call picks its kernel --------------------------------------------------------------------------------------------
     # The inference tiers in order of preference: the first whose setting holds and whose planner returns a plan runs.  Exact-trace sets
-    # come before exact-trace because the set type is the narrower match; sets come before attention because the two planners key on
+    # (pooled, then attention) come before exact-trace because the set types are the narrower match; sets come before attention because the two planners key on
     # disjoint module types.  `applies` sees the ODEfunc and x.dim(); `plan` the transform, x.shape, the latent width, whether the kernel
     # accumulates the log-det, and the device.
     _TIERS = (
@@ -665,6 +685,9 @@ class ContinuousTransform(Transform):
         _Tier('sx_cnf_exact_set_flow',
               lambda func, nd: func.divergence == 'exact' and nd >= 2 and type(func.diffeq) is exact_trace.DiffeqExactTraceDeepSet,
               lambda f, shape, ld, trace, dev: f._exact_set_kernel_net(shape[-2], ld, dev)),
+        _Tier('sx_cnf_exact_attn_flow',
+              lambda func, nd: func.divergence == 'exact' and nd >= 2 and type(func.diffeq) is exact_trace.DiffeqExactTraceAttention,
+              lambda f, shape, ld, trace, dev: f._exact_attn_kernel_net(shape[-2], ld, dev)),
         _Tier('sx_cnf_exact_flow', lambda func, nd: func.divergence == 'exact' and not func.set_data,
               lambda f, shape, ld, trace, dev: f._exact_kernel_net(ld, dev)),
         _Tier('sx_cnf_set_flow', _set_setting, lambda f, shape, ld, trace, dev: f._set_kernel_net(shape[-2], ld, dev)),
@@ -761,7 +784,8 @@ class ContinuousTransform(Transform):
     def set_data(self) -> bool:
         """Does the ODE function read its input as sets (..., N, dim)?  (NormalizingFlow keeps the set axis for such layers.)"""
         return bool(self.odefunc.set_data or self.odefunc.divergence == 'compute_set'
-                    or type(self.odefunc.diffeq) in (DiffeqZeroTraceDeepSet, exact_trace.DiffeqExactTraceDeepSet))
+                    or type(self.odefunc.diffeq) in (DiffeqZeroTraceDeepSet, exact_trace.DiffeqExactTraceDeepSet, DiffeqZeroTraceAttention,
+                                                     exact_trace.DiffeqExactTraceAttention))
 
     def _autograd_set(self, x2, lat2, set_size: int, reverse: bool):
         lat = None if lat2 is None else lat2.reshape(-1, set_size, lat2.shape[-1])

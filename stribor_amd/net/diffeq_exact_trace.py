@@ -12,6 +12,12 @@ mask}``, ``dimwise_net.net.net.0.weight``), construction order net1, net2, dimwi
 ``exclusive_net.interaction.set_emb.net.net.<i>.{weight,bias}``), the same dimwise net; construction order MADE, set embedding,
 dimwise net.  ``closed_form_set`` / ``kernel_image_set`` are its counterparts of the functions below, for ``sx_cnf_exact_set_flow``.
 
+``DiffeqExactTraceAttention`` is the attention instance over (..., N, dim) (diffeq_exact_trace.py:104-130): exclusive net
+``DiffeqZeroTraceAttention`` (keys ``exclusive_net.q.net.<i>.{weight,bias,mask}``, ``exclusive_net.{k,v}.net.<i>.{weight,bias}``,
+``exclusive_net.proj.net.0.{weight,bias}``), the same dimwise net; construction order q, k, v, proj, dimwise net.
+``closed_form_attn`` / ``kernel_image_attn`` are its counterparts of the functions below, for ``sx_cnf_exact_attn_flow``.  The class is
+exported here and not by the package namespace ``stribor_amd.net``.
+
 For the MLP instance this module also holds what ``sx_cnf_exact_flow`` consumes: ``kernel_image`` stages ``mask * weight`` and the
 dimwise weights into the kernel's LDS image (include/stribor_hip.h), and ``closed_form`` is the same arithmetic as torch ops --
 value and forward-mode tangent side by side, no autograd -- in any dtype (tests hold it to ``autograd.functional.jacobian``).
@@ -27,16 +33,20 @@ from . import cover
 from .cover import tiles as _tiles
 from .diagjac import FuncAndDiagJac
 from .diffeq import DiffeqMLP
-from .diffeq_zero_trace import DiffeqZeroTraceDeepSet, DiffeqZeroTraceMLP, ZeroTraceEquivariantEncoder
+from .diffeq_zero_trace import DiffeqZeroTraceAttention, DiffeqZeroTraceDeepSet, DiffeqZeroTraceMLP, ZeroTraceEquivariantEncoder
 from .made import MADE, MaskedLinear
 from .mlp import MLP
 
-__all__ = ['DiffeqExactTrace', 'DiffeqExactTraceMLP', 'DiffeqExactTraceDeepSet']
+__all__ = ['DiffeqExactTrace', 'DiffeqExactTraceMLP', 'DiffeqExactTraceDeepSet', 'DiffeqExactTraceAttention']
 
 MAX_DIM, MAX_DH, MAX_LATENT, MAX_HIDDEN = 16, 8, 64, 64          # sx_cnf_exact_flow's coverage (SX_CNF_EXACT_MAX_*)
 MAX_SET_SIZE = 128                                               # sx_cnf_exact_set_flow's (SX_CNF_EXACT_SET_MAX_*: the four above too)
 POOLINGS = {'sum': 0, 'mean': 1, 'max': 2}                       # SX_POOL_*
 SET_EXCHANGE_FLOATS = 128 * 16                                   # the kernel's LDS exchange buffer, after the image
+# sx_cnf_exact_attn_flow's coverage (SX_CNF_EXACT_ATTN_MAX_*; d_h, latent, hidden and the set size as above) and its exchange: the k and v
+# areas of 128 rows x 36 floats and 128 set flags
+ATTN_MAX_DIM, ATTN_MAX_EMBED, ATTN_MAX_QUERY_TILES, ATTN_HEADS = 8, 32, 4, (1, 2, 4)
+ATTN_EXCHANGE_FLOATS = 2 * 128 * 36 + 128
 
 
 class DiffeqExactTrace(nn.Module):
@@ -75,6 +85,18 @@ class DiffeqExactTraceDeepSet(DiffeqExactTrace):
     def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, d_h: int, latent_dim: int = 0, pooling: str = 'max',
                  return_log_det_jac: bool = True, **kwargs):
         exclusive_net = DiffeqZeroTraceDeepSet(in_dim, hidden_dims, d_h * out_dim, pooling=pooling, return_log_det_jac=False)
+        dimwise_net = DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1)
+        super().__init__(exclusive_net, dimwise_net, return_log_det_jac)
+
+
+class DiffeqExactTraceAttention(DiffeqExactTrace):
+    """``DiffeqExactTraceAttention(dim, hidden_dims, dim, d_h, latent_dim, n_heads)`` over sets (..., N, dim): exclusive net
+    DiffeqZeroTraceAttention(dim, hidden_dims, d_h * dim, n_heads), dimwise net DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1) over
+    the columns [t, x_i[d], h_i[d], latent_i].  `mask` is not passed on (``DiffeqExactTrace.forward``), so every element counts."""
+
+    def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, d_h: int, latent_dim: int = 0, n_heads: int = 1,
+                 return_log_det_jac: bool = True, **kwargs):
+        exclusive_net = DiffeqZeroTraceAttention(in_dim, hidden_dims, d_h * out_dim, n_heads, return_log_det_jac=False)
         dimwise_net = DiffeqMLP(d_h + latent_dim + 2, hidden_dims, 1)
         super().__init__(exclusive_net, dimwise_net, return_log_det_jac)
 
@@ -258,18 +280,30 @@ class _Image:
         Wp[np.ix_(rpos, cpos)] = W
         self.parts.append(_fragment_image(Wp))
 
-    def stage_made(self, lins):
-        """A MADE: mask * weight and the bias per layer, the last layer at the MADE output's positions."""
+    def stage_made(self, lins, out_pos=None, out_tiles=None):
+        """A MADE: mask * weight and the bias per layer, the last layer at the MADE output's positions (`out_pos` in `out_tiles`
+        tiles: another layout of the last layer than the d_h slots')."""
         in_pos = self.pos_x
+        pos_last, tiles_last = (self.pos_raw, self.OT) if out_pos is None else (out_pos, out_tiles)
         for i, l in enumerate(lins):
             last = i + 1 == len(lins)
-            out_pos = self.pos_raw if last else np.arange(l.out_features)
+            out_pos = pos_last if last else np.arange(l.out_features)
             mask = self.npy(l.mask)
             with np.errstate(invalid='ignore'):
                 W = np.where(mask != 0, mask * self.npy(l.weight), np.float32(0))          # (0 * inf is not 0)
-            self.mat(self.OT if last else self.HT, 1 if i == 0 else self.HT, out_pos, in_pos, W)
-            self.bias(self.OT if last else self.HT, out_pos, l)
+            self.mat(tiles_last if last else self.HT, 1 if i == 0 else self.HT, out_pos, in_pos, W)
+            self.bias(tiles_last if last else self.HT, out_pos, l)
             in_pos = out_pos
+
+    def stage_mlp(self, lins, out_pos):
+        """A plain MLP on the state (no time column): weight and bias per layer, the last layer's outputs at `out_pos` of one tile."""
+        in_pos = self.pos_x
+        for i, l in enumerate(lins):
+            last = i + 1 == len(lins)
+            pos = out_pos if last else np.arange(l.out_features)
+            self.mat(1 if last else self.HT, 1 if i == 0 else self.HT, pos, in_pos, self.npy(l.weight))
+            self.bias(1 if last else self.HT, pos, l)
+            in_pos = pos
 
     def stage_dimwise(self, dw):
         """The dimwise net's block, which ends both images -> (image, w_latent)."""
@@ -432,4 +466,145 @@ def kernel_image_set(s):
         if i == 0:
             im.vec(im.HT, out_pos, W[:, 0])
         in_pos = out_pos
+    return im.stage_dimwise(s['dimwise'])
+
+
+# ---- the attention instance -------------------------------------------------------------------------------------------------------
+def _structure_attn(net):
+    """The layers of a DiffeqExactTraceAttention-shaped module -> dict, or None when it is not the plain instance: a MADE q, plain MLPs
+    k, v and a one-Linear proj, a DiffeqMLP over a plain MLP, none with a final activation, one activation name, hidden widths
+    hidden[:-1] in q, k, v and E = hidden[-1] their output width."""
+    ex, dim_net = net.exclusive_net, net.dimwise_net
+    if type(ex) is not DiffeqZeroTraceAttention or type(dim_net) is not DiffeqMLP:
+        return None
+    q, mlps = ex.q, (ex.k, ex.v, ex.proj, dim_net.net)
+    if type(q) is not MADE or q.final_activation is not None or not q.return_per_dim:
+        return None
+    if any(type(m) is not MLP or m._wrapped or m.final_activation_name is not None for m in mlps):
+        return None
+    act = dim_net.net.activation_name
+    if q.activation != act or any(m.activation_name != act for m in mlps[:2]):
+        return None
+    stacks = [list(q.net)] + [list(m.net) for m in mlps]
+    for stack, kind in zip(stacks, (MaskedLinear, nn.Linear, nn.Linear, nn.Linear, nn.Linear)):
+        if len(stack) % 2 != 1 or any(not isinstance(l, kind) for l in stack[0::2]):
+            return None
+        if any(type(a) is not getattr(nn, act, None) for a in stack[1::2]):
+            return None
+    lq, lk, lv, lp, ld = [stack[0::2] for stack in stacks]
+    hidden = [l.out_features for l in ld[:-1]]
+    if not hidden or len(lp) != 1 or any([l.out_features for l in ls[:-1]] != hidden[:-1] for ls in (lq, lk, lv)):
+        return None
+    D, E, d_h = lq[0].in_features, hidden[-1], lp[0].out_features
+    if lq[-1].out_features != E * D or any(ls[0].in_features != D or ls[-1].out_features != E for ls in (lk, lv)):
+        return None
+    if lp[0].in_features != E or ld[-1].out_features != 1 or not isinstance(ex.n_heads, int) or ex.n_heads < 1 or E % ex.n_heads:
+        return None
+    L = ld[0].in_features - 2 - d_h
+    if L < 0:
+        return None
+    return {'D': D, 'd_h': d_h, 'L': L, 'hidden': hidden, 'act': act, 'E': E, 'heads': ex.n_heads, 'q': lq, 'k': lk, 'v': lv, 'proj': lp[0],
+            'dimwise': ld, 'activations': [a for stack in stacks for a in stack[1::2]]}
+
+
+def closed_form_attn(net, t, x, latent=None, want_jac: bool = True, dtype=None):
+    """(f, jac) of a plain DiffeqExactTraceAttention over sets x [..., N, D] (a 2-D x is one set) by its closed form, as torch ops
+    without autograd, in `dtype` (default: x's), H heads of width dh = E / H:
+        q_i[d, :] = MADE_q(x_i)[d, :]                           (mask * weight; column e * D + d)
+        k_j = K(x_j),  v_j = V(x_j)
+        s_ij  = dh^-1/2 q_i[d] . k_j per head, s_ii = -inf      p_i = softmax_j(s_ij), a row without keys (N = 1): zeros
+        o_i[d] = sum_j p_ij v_j,   h_i[d, :] = P o_i[d] + b
+    then the dimwise net with its tangent, as `closed_form`.  This is what sx_cnf_exact_attn_flow evaluates per stage."""
+    s = _structure_attn(net)
+    if s is None or s['act'] not in cover.ACTS:
+        raise NotImplementedError('closed_form_attn: a plain DiffeqExactTraceAttention with an activation of the kernel\'s set')
+    dtype = dtype or x.dtype
+    return _attn_value(s, t, x.detach().to(dtype), None if latent is None else latent.detach().to(dtype), want_jac, dtype)
+
+
+def _attn_exclusive(s, x, dtype):
+    """The exclusive net of closed_form_attn on a structure dict: x [..., N, D] in `dtype`, not detached -> h [R, D, d_h]."""
+    act = cover.ACTS[s['act']][0]
+    D, E, H = s['D'], s['E'], s['heads']
+    cast = lambda p: None if p is None else p.detach().to(device=x.device, dtype=dtype)
+    N = x.shape[-2]
+    x2 = x.reshape(-1, D)
+
+    def stack(lins, masked=False):
+        a = x2
+        for i, l in enumerate(lins):
+            a = nn.functional.linear(a, cast(l.mask) * cast(l.weight) if masked else cast(l.weight), cast(l.bias))
+            if i + 1 < len(lins):
+                a = act(a)
+        return a
+    q = stack(s['q'], True).reshape(-1, N, E, D).transpose(-1, -2).reshape(-1, N, D, H, E // H)          # column e * D + d -> [d, e]
+    k, v = (stack(s[n]).reshape(-1, N, H, E // H) for n in ('k', 'v'))
+    sc = torch.einsum('bidhe,bjhe->bhdij', q, k) * (1 / (E // H)) ** 0.5
+    sc = sc.masked_fill(torch.eye(N, dtype=torch.bool, device=x.device), -float('inf'))
+    m = sc.max(-1, keepdim=True).values
+    ex = torch.exp(sc - torch.where(torch.isinf(m), torch.zeros_like(m), m))
+    tot = ex.sum(-1, keepdim=True)
+    p = torch.where(tot > 0, ex / torch.where(tot > 0, tot, torch.ones_like(tot)), torch.zeros_like(ex))
+    o = torch.einsum('bhdij,bjhe->bidhe', p, v).reshape(-1, D, E)
+    return nn.functional.linear(o, cast(s['proj'].weight), cast(s['proj'].bias))
+
+
+def _attn_value(s, t, x, latent, want_jac, dtype):
+    """closed_form_attn's arithmetic on a structure dict; x and latent in `dtype`, not detached (the tests differentiate it)."""
+    D = s['D']
+    cast = lambda p: None if p is None else p.detach().to(device=x.device, dtype=dtype)
+    lead = x.shape[:-1]
+    h = _attn_exclusive(s, x, dtype)
+    lat2 = None if latent is None else latent.expand(*lead, latent.shape[-1]).reshape(-1, latent.shape[-1])
+    f, jac = _dimwise(s, t, x.reshape(-1, D), h, lat2, want_jac, cast, dtype)
+    return f.reshape(*lead, D), (jac.reshape(*lead, D) if want_jac else None)
+
+
+def _attn_slot(E: int) -> int:
+    """Positions a dimension's query takes in a 32-position tile: 8, 16 or 32, the smallest that holds E."""
+    return 8 if E <= 8 else 16 if E <= 16 else 32
+
+
+def attn_query_tiles(E: int, dim: int) -> int:
+    """Tiles of the q MADE's output in the kernel's layout: 32 // slot dimensions a tile."""
+    per = 32 // _attn_slot(E)
+    return (dim + per - 1) // per
+
+
+def kernel_coverage_attn(net, dim: int, latent_dim: int, set_size: int):
+    """The structure dict of `net` when sx_cnf_exact_attn_flow covers it for sets of `set_size` elements of `dim` features and
+    `latent_dim` latent columns, else None.  Beyond the exact-trace kernels' shared ranges: dim <= 8, E <= 32, E * dim <= 128 with at
+    most four query tiles (slot(E) * dim <= 128), 1, 2 or 4 heads."""
+    if type(net) is not DiffeqExactTraceAttention or not net.return_log_det_jac or not 1 <= set_size <= MAX_SET_SIZE:
+        return None
+    s = _covered(_structure_attn(net), dim, latent_dim)
+    if s is None or dim > ATTN_MAX_DIM or s['E'] > ATTN_MAX_EMBED or s['heads'] not in ATTN_HEADS:
+        return None
+    return s if attn_query_tiles(s['E'], dim) <= ATTN_MAX_QUERY_TILES else None
+
+
+def kernel_tensors_attn(s):
+    """Every tensor the image is made of: the cache guards (weights, biases AND the q MADE's masks)."""
+    ts = []
+    for l in s['q']:
+        ts += [l.weight, l.mask] + ([] if l.bias is None else [l.bias])
+    for l in s['k'] + s['v'] + [s['proj']] + s['dimwise']:
+        ts += [l.weight] + ([] if l.bias is None else [l.bias])
+    return ts
+
+
+def kernel_image_attn(s):
+    """-> (image [floats] fp32 numpy, w_latent [32 HT, 32 LT] fp32 numpy | None): the layout of include/stribor_hip.h
+    (sx_cnf_exact_attn_net).  The masks are multiplied in HERE: a weight entry under a zero mask never reaches the kernel."""
+    im = _Image(s)
+    D, E = s['D'], s['E']
+    slot = _attn_slot(E)
+    per = 32 // slot
+    cols = np.arange(E * D)
+    d, e = cols % D, cols // D
+    im.stage_made(s['q'], 32 * (d // per) + (d % per) * slot + e, attn_query_tiles(E, D))
+    im.stage_mlp(s['k'], np.arange(E))
+    im.stage_mlp(s['v'], np.arange(E))
+    im.mat(1, 1, im.pos_e, np.arange(E), im.npy(s['proj'].weight))
+    im.bias(1, im.pos_e, s['proj'])
     return im.stage_dimwise(s['dimwise'])

@@ -9,16 +9,23 @@ coordinates plus, the same for every dimension, a pooling of the OTHER elements'
 sum / mean / max below.  Output (i, d) depends neither on x_i[d] (the MADE) nor on any coordinate of x_i (the pooling), so the
 diagonal blocks d y[i, d, :] / d x[i, d] vanish.  Keys ``elementwise.net.<i>.{weight,bias,mask}``,
 ``interaction.set_emb.net.net.<i>.{weight,bias}``; the MADE is built (and draws) first.
+
+``DiffeqZeroTraceAttention`` (diffeq_zero_trace.py:179-227) is the attention instance over (..., N, dim): per dimension d a query from
+a MADE of the element's own coordinates (it does not depend on x_i[d]) attends, diagonal masked, to keys and values of the OTHER
+elements, and a Linear projects the result to out_dim / dim slots.  Keys ``q.net.<i>.{weight,bias,mask}``, ``k.net.<i>.*``,
+``v.net.<i>.*``, ``proj.net.0.*``; construction order q, k, v, proj.
 """
 from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
+from .attention import attention
 from .diffeq import DiffeqMLP, DiffeqNet
 from .made import MADE
+from .mlp import MLP
 
-__all__ = ['DiffeqZeroTraceMLP', 'DiffeqZeroTraceDeepSet', 'ZeroTraceEquivariantEncoder', 'exclusive_sum_pooling',
+__all__ = ['DiffeqZeroTraceMLP', 'DiffeqZeroTraceDeepSet', 'DiffeqZeroTraceAttention', 'ZeroTraceEquivariantEncoder', 'exclusive_sum_pooling',
            'exclusive_mean_pooling', 'exclusive_max_pooling']
 
 
@@ -113,3 +120,37 @@ class DiffeqZeroTraceDeepSet(DiffeqNet):
         y = y * mask.unsqueeze(-1)
         y = y.reshape(*y.shape[:-2], -1)
         return (y, div) if self.return_log_det_jac else y
+
+
+class DiffeqZeroTraceAttention(DiffeqNet):
+    """``DiffeqZeroTraceAttention(dim, hidden_dims, k * dim, n_heads=1)`` over sets (..., N, dim), E = hidden_dims[-1]: q =
+    MADE(dim, hidden_dims[:-1], E * dim) per dimension, k and v = MLP(dim, hidden_dims[:-1], E), proj = MLP(E, [], k); dim attentions
+    with the diagonal masked against the same keys and values -> [..., N, dim * k] dimension-major, and with ``return_log_det_jac`` (the
+    default) zeros like x beside it.  Ignores t and `latent`.  Runs on the HIP attention core with the (..., dim) leading dimensions
+    flattened; differentiable.
+
+    mask: None only.  (The reference's forward fails on a shape error for a mask of either shape its signature names; inside
+    ``DiffeqExactTrace`` the exclusive net never receives one: DESIGN.md 4.14.)"""
+
+    def __init__(self, in_dim: int, hidden_dims: List[int], out_dim: int, n_heads: int = 1, return_log_det_jac: Optional[bool] = True,
+                 **kwargs):
+        super().__init__()
+        self.n_heads = n_heads
+        self.return_log_det_jac = return_log_det_jac
+        self.q = MADE(in_dim, hidden_dims[:-1], hidden_dims[-1] * in_dim, return_per_dim=True)
+        self.k = MLP(in_dim, hidden_dims[:-1], hidden_dims[-1])
+        self.v = MLP(in_dim, hidden_dims[:-1], hidden_dims[-1])
+        self.proj = MLP(hidden_dims[-1], [], out_dim // in_dim)
+
+    def forward(self, t, x, mask=None, latent=None, **kwargs):
+        if mask is not None:
+            raise NotImplementedError('DiffeqZeroTraceAttention: mask=None is the only supported call (the reference\'s forward raises a '
+                                      'shape error for a mask; ContinuousTransform runs masked calls without handing it here)')
+        D = x.shape[-1]
+        query = self.q(x).transpose(-2, -3)                                       # (..., N, D, E) -> (..., D, N, E)
+        key = self.k(x).unsqueeze(-3).expand(*x.shape[:-2], D, x.shape[-2], -1)   # the same keys and values for every dimension
+        value = self.v(x).unsqueeze(-3).expand(*x.shape[:-2], D, x.shape[-2], -1)
+        y = attention(query, key, value, self.n_heads, True, None).transpose(-2, -3)          # (..., N, D, E)
+        y = self.proj(y)
+        y = y.reshape(*y.shape[:-2], -1)
+        return (y, torch.zeros_like(x)) if self.return_log_det_jac else y

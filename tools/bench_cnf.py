@@ -29,13 +29,24 @@ line's (B, N, dim) and grid, against its composition path (divergence_exact_for_
 TF / fraction of peak are algorithmic work over CALL time (device events around whole calls: the launch, the output allocation and the
 kernel), not over kernel time.  --attention-only prints this line alone.
 
+The exact-attention line: divergence='exact' over DiffeqExactTraceAttention(2, [64, 32], 2, d_h = 4, n_heads = 4) on
+sx_cnf_exact_attn_flow, the set line's (B, N, dim) and grid, timed as the attention line (device events around whole calls, at least 50 of
+them after 2 warm-up calls), against its composition path (FuncAndDiagJac over the HIP attention core) timed at --set-fallback-sets sets
+and scaled, and beside sx_cnf_attn_flow's 'compute_set' call for a DiffeqSelfAttention of the same widths -- what the same user pays for
+the trace without the exact-trace construction.  FLOPs per element and evaluation: the q MADE 2 (D H1 + H1 E D), K and V 2 x 2 (D H1 +
+H1 E), and per dimension scores and P.V 2 x 2 N E, the projection 2 E d_h and the dimwise net over [H1, E]: 2 (1 + d_h) H1 + 2 H1 E +
+2 E for the value and 2 H1 E + 2 E for the tangent (padding and the exchange are not counted).  At the --set-fallback-sets sets it also
+checks two conditions and exits non-zero when one fails: the kernel is within 8 x the composition path's own error against an fp64 solve
+of the same grid over net.diffeq_exact_trace.closed_form_attn (floor 1e-6 max(1, |fp64|): the tests' bound), and the kernel call is
+faster than the composition path.  --exact-attention-only prints this line alone.
+
 The training lines: one step's -log_prob(x).mean().backward() including the zeroing of the gradients, divergence='approximate' in
 training mode, at dim 2 / [32] and dim 32 / [32, 32] (the widest hidden layers sx_cnf_train_fwd / sx_cnf_train_bwd cover; dim 2 / [64]
 and dim 32 / [64, 64] train on the composition path and are timed on it alone), --train-rows rows, rk4 x --steps: the kernel path, the
 composition path on the same build and rows (forced by hiding the kernel plan), and the checkpoint bytes n_steps x rows x dim x 4.
 --train-only prints these lines alone.
 
-    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only] [--train-only] [--train-rows 16384]
+    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only] [--exact-attention-only] [--train-only] [--train-rows 16384]
 """
 import argparse
 import json
@@ -92,6 +103,69 @@ def attention_line(a, results):
           f'{r["max_abs_ldj"]:.2e}')
 
 
+def exact_attention_line(a, results):
+    from stribor_amd.flows.cnf import _rk_step
+    from stribor_amd.net import diffeq_exact_trace as xt
+    from stribor_amd.net.diffeq_exact_trace import closed_form_attn
+    torch.manual_seed(0)
+    B, N, D, hidden, d_h, heads = a.sets, 32, 2, [64, 32], 4, 4
+    opts = dict(solver='rk4', solver_options={'step_size': 1.0 / a.steps})
+    f = st.ContinuousTransform(D, net=xt.DiffeqExactTraceAttention(D, hidden, D, d_h, n_heads=heads), divergence='exact',
+                               **opts).eval().to('cuda')
+    same_width = st.ContinuousTransform(D, net=st.net.DiffeqSelfAttention(D + 1, hidden, D, n_heads=heads), divergence='compute_set',
+                                        set_data=True, **opts).eval().to('cuda')
+    y = torch.randn(B, N, D, device='cuda')
+    ys = y[:a.set_fallback_sets]
+    H1, E = hidden
+    flop_eval = 2 * (D * H1 + H1 * E * D) + 4 * (D * H1 + H1 * E) + D * (4 * N * E + 2 * E * d_h + 2 * (1 + d_h) * H1 + 4 * H1 * E + 4 * E)
+    reps = max(a.reps, 50)
+
+    def solve64(x):
+        """The same grid and tableau (flows.cnf._rk_step) over the closed form in fp64 -> (x at 0, log-det)."""
+        net = f.odefunc.diffeq
+
+        def func(t, state):
+            dy, jac = closed_form_attn(net, float(t), state[0], dtype=torch.float64)
+            return dy, -jac
+        grid = f._grid(True).points
+        state = (x.double(), torch.zeros_like(x, dtype=torch.float64))
+        for i in range(len(grid) - 1):
+            state = tuple(s + d for s, d in zip(state, _rk_step(func, 'rk4', grid[i], grid[i + 1], state)))
+        return state[0], -state[1].sum(-1, keepdim=True)
+    with torch.no_grad():
+        ms = timed(lambda: f.inverse_and_log_det_jacobian(y), reps)
+        assert f._last_path == 'kernel'
+        ms_x = timed(lambda: f.inverse(y), reps)
+        ms_cs = timed(lambda: same_width.inverse_and_log_det_jacobian(y), reps)
+        assert same_width._last_path == 'kernel'
+        ms_small = timed(lambda: f.inverse_and_log_det_jacobian(ys), reps)
+        fb_small = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=1)
+        fb = fb_small * (B / ys.shape[0])
+        xk, lk = f.inverse_and_log_det_jacobian(ys)
+        xc, lc = f._composed_reference(ys, reverse=True)
+        x64, l64 = solve64(ys)
+    bound = lambda ref32, truth: max(8 * (ref32.double() - truth).abs().max().item(), 1e-6 * max(1.0, truth.abs().max().item()))
+    err_x, err_l = (xk.double() - x64).abs().max().item(), (lk.double() - l64).abs().max().item()
+    bound_x, bound_l = bound(xc, x64), bound(lc, l64)
+    fl = B * N * 4 * a.steps * flop_eval
+    r = results[f'exact_attention_b{B}_n{N}_dim{D}_dh{d_h}_h{"x".join(map(str, hidden))}_heads{heads}'] = {
+        'solve_ldj_ms': ms, 'solve_only_ms': ms_x, 'composed_ms_scaled': fb, 'rows_per_s': B * N / ms * 1e3, 'tflops': fl / ms / 1e9,
+        'frac_of_peak': fl / (ms * 1e-3) / PEAK_F32_MFMA, 'composed_over_kernel': fb / ms, 'reps': reps,
+        'compute_set_same_width_ms': ms_cs, 'compute_set_over_exact': ms_cs / ms,
+        'sets_small': ys.shape[0], 'kernel_small_ms': ms_small, 'composed_small_ms': fb_small, 'kernel_faster_at_small': ms_small < fb_small,
+        'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item(),
+        'kernel_err_x_vs_fp64': err_x, 'bound_x': bound_x, 'kernel_err_ldj_vs_fp64': err_l, 'bound_ldj': bound_l,
+        'within_bound': err_x <= bound_x and err_l <= bound_l}
+    print(f'exact-trace attention sets (B, N, dim) = ({B}, {N}, {D}) d_h {d_h} {hidden} heads {heads} rk4 x {a.steps}: solve + log-det '
+          f'{ms:.2f} ms per call over {reps} calls ({r["rows_per_s"]:.3g} elements/s, {r["tflops"]:.1f} TF of algorithmic work per call '
+          f'time = {r["frac_of_peak"]:.3f} of the fp32-MFMA peak), solve alone {ms_x:.2f} ms; composition path {fb:.0f} ms (timed at '
+          f'{ys.shape[0]} sets: {fb_small:.1f} ms against the kernel\'s {ms_small:.3f} ms there, scaled) = {r["composed_over_kernel"]:.0f} x; '
+          f'kernel vs composition max abs x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}; kernel vs fp64 x {err_x:.2e} (bound '
+          f'{bound_x:.2e}) ldj {err_l:.2e} (bound {bound_l:.2e}); sx_cnf_attn_flow under compute_set at the same widths {ms_cs:.2f} ms = '
+          f'{r["compute_set_over_exact"]:.2f} x this call')
+    return r['within_bound'] and r['kernel_faster_at_small']
+
+
 def training_lines(a, results):
     n = a.train_rows
     for dim, hidden in ((2, [32]), (32, [32, 32]), (2, [64]), (32, [64, 64])):
@@ -134,16 +208,21 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--json', default=None)
     ap.add_argument('--attention-only', action='store_true', help='print the attention line alone')
+    ap.add_argument('--exact-attention-only', action='store_true', help='print the exact-trace attention line alone')
     ap.add_argument('--train-only', action='store_true', help='print the training lines alone')
     ap.add_argument('--train-rows', type=int, default=1 << 14, help='rows of the training lines (the composition path finishes in seconds)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_cnf needs a GPU'
     results = {}
-    if not a.attention_only and not a.train_only:
+    only = a.attention_only or a.exact_attention_only or a.train_only
+    ok = True
+    if not only:
         earlier_lines(a, results)
-    if not a.train_only:
+    if a.attention_only or not only:
         attention_line(a, results)
-    if not a.attention_only:
+    if a.exact_attention_only or not only:
+        ok = exact_attention_line(a, results)
+    if a.train_only or not only:
         training_lines(a, results)
     results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows, 'sets': a.sets,
                          'set_fallback_sets': a.set_fallback_sets, 'train_rows': a.train_rows,
@@ -151,6 +230,8 @@ def main():
     if a.json:
         with open(a.json, 'w') as fh:
             json.dump(results, fh, indent=1)
+    if not ok:
+        sys.exit('bench_cnf: the exact-attention line misses one of its two conditions (within_bound, kernel_faster_at_small)')
 
 
 def earlier_lines(a, results):
