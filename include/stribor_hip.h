@@ -571,6 +571,23 @@ int sx_flow_run2(const sx_program *prog_host, const float *blobs, const float *b
                  const float *row_t, float *side, int64_t n_rows, int32_t dtype, int32_t precision,
                  uint32_t *work, uint32_t *err_flag, void *stream);
 
+/* sx_flow_run2 in OVERWRITE mode: the call leaves *sum_out EQUAL to the batch sum whatever it held, so no zero-fill has to be
+ * launched in front of it (sx_flow_run / sx_flow_run2 ADD to *sum_out).  A step of log_prob_sum is then two launches -- the flow
+ * kernel and the exact redo pass, which finds an empty list on ordinary data and ends without an atomic -- or one without `redo`.
+ *   sum_slot   caller-owned DEVICE scratch of one fp64 (8-byte aligned), zeroed once, private to one stream like `work`.  The
+ *              flow kernel's workgroups add their totals into it (that launch is handed the slot in place of sum_out: the
+ *              same kernel code as an accumulating call), the redo pass adds the named samples' rows there too, and the
+ *              workgroup that closes the pass -- workgroup 0 when the list is empty, else the last one out -- moves the total
+ *              to *sum_out and leaves the slot zeroed: calls need no memset and replay from HIP graphs.  After a failed
+ *              launch zero the slot again.  n_rows == 0: *sum_out is set to 0.  Without a redo list (redo = NULL) there is
+ *              no second launch to close the call: *sum_out is cleared by a memset on the stream and the launch adds to it.
+ * sum_slot = NULL: sx_flow_run2.  With a slot sum_out must not be NULL. */
+int sx_flow_run3(const sx_program *prog_host, const float *blobs, const float *blobs_exact, uint32_t *redo, const void *x,
+                 const float *latent, const int32_t *in_col, const int32_t *out_col, void *y, float *ldj_out,
+                 float *logp_out, double *sum_out, float *mlp_out, int64_t mlp_out_stride, int32_t mlp_out_dim,
+                 const float *row_t, float *side, int64_t n_rows, int32_t dtype, int32_t precision,
+                 uint32_t *work, uint32_t *err_flag, void *stream, double *sum_slot);
+
 /* Training backward of log_prob for flows of affine couplings, layer-major: one launch per layer (or pair) with the weight gradients
  * contracted inside the kernel (the single-launch program of SX_STEP_COUPLING_AFFINE_BWD steps run through sx_flow_run
  * writes 896 B of per-row factors per layer for sx_wgrad_layer to read back; here only the state crosses HBM between

@@ -281,8 +281,8 @@ extern "C" int sx_flow_run(const sx_program *prog_host, const float *blobs, cons
                            double *sum_out, float *mlp_out, int64_t mlp_out_stride, int32_t mlp_out_dim,
                            const float *row_t, float *side, int64_t n_rows, int32_t dtype, int32_t precision,
                            uint32_t *work, uint32_t *err_flag, void *stream) {
-    return sx_flow_run2(prog_host, blobs, nullptr, nullptr, x, latent, in_col, out_col, y, ldj_out, logp_out, sum_out, mlp_out, mlp_out_stride,
-                        mlp_out_dim, row_t, side, n_rows, dtype, precision, work, err_flag, stream);
+    return sx_flow_run3(prog_host, blobs, nullptr, nullptr, x, latent, in_col, out_col, y, ldj_out, logp_out, sum_out, mlp_out, mlp_out_stride,
+                        mlp_out_dim, row_t, side, n_rows, dtype, precision, work, err_flag, stream, nullptr);
 }
 
 extern "C" int sx_flow_run2(const sx_program *prog_host, const float *blobs, const float *blobs_exact, uint32_t *redo, const void *x,
@@ -290,6 +290,23 @@ extern "C" int sx_flow_run2(const sx_program *prog_host, const float *blobs, con
                             float *logp_out, double *sum_out, float *mlp_out, int64_t mlp_out_stride, int32_t mlp_out_dim,
                             const float *row_t, float *side, int64_t n_rows, int32_t dtype, int32_t precision,
                             uint32_t *work, uint32_t *err_flag, void *stream) {
+    return sx_flow_run3(prog_host, blobs, blobs_exact, redo, x, latent, in_col, out_col, y, ldj_out, logp_out, sum_out, mlp_out, mlp_out_stride,
+                        mlp_out_dim, row_t, side, n_rows, dtype, precision, work, err_flag, stream, nullptr);
+}
+
+// sx_flow_run2 with the SUM SLOT: sum_slot != NULL makes the call leave sum_out EQUAL to the batch sum whatever it held -- one launch
+// less per step than a zero-fill in front of an accumulating call.  The main launch is handed the SLOT as its sum_out (the same kernel,
+// the same code: its workgroups add their totals there), and the redo pass, which is launched behind it anyway, closes the call: it
+// adds the named samples' rows into the slot as well, and workgroup 0 (empty list) or the last workgroup out moves the total to
+// sum_out and leaves the slot zeroed (sx_flow_kernel.h, flow_kargs::sum_slot).  So a step of log_prob_sum is two launches, the flow
+// and the -- usually empty -- redo pass.  (Built first: the last workgroup of the MAIN launch stores the total.  Those forty
+// instructions behind the chunk loop cost cfg 2's <1,2,2,5>, which sits on its vector- and scalar-register budgets, +14 us per
+// launch: DESIGN 6.)  Without a redo list there is no second launch to close the call: sum_out is cleared by a memset node first.
+extern "C" int sx_flow_run3(const sx_program *prog_host, const float *blobs, const float *blobs_exact, uint32_t *redo, const void *x,
+                            const float *latent, const int32_t *in_col, const int32_t *out_col, void *y, float *ldj_out,
+                            float *logp_out, double *sum_out, float *mlp_out, int64_t mlp_out_stride, int32_t mlp_out_dim,
+                            const float *row_t, float *side, int64_t n_rows, int32_t dtype, int32_t precision,
+                            uint32_t *work, uint32_t *err_flag, void *stream, double *sum_slot) {
     dprog d; int bf; int mlp_mode; int sw;
     int rc = validate_and_convert(prog_host, &d, &bf, &mlp_mode, &sw);
     if (rc) return rc;
@@ -312,7 +329,15 @@ extern "C" int sx_flow_run2(const sx_program *prog_host, const float *blobs, con
     SX_REQUIRE(mlp_mode != 4 || (side != nullptr && row_t != nullptr && dtype == SX_F32 && prog_host->latent_dim == 0),
                "sx_flow_run: backward programs need side, row_t (dL/dlog_prob) and fp32 state");
     SX_REQUIRE(!prog_host->identity_cols || ((uintptr_t)x & 15) == 0, "sx_flow_run: x must be 16-byte aligned");
-    if (n_rows == 0) return SX_OK;
+    SX_REQUIRE(sum_slot == nullptr || (sum_out != nullptr && (((uintptr_t)sum_slot | (uintptr_t)sum_out) & 7) == 0),
+               "sx_flow_run3: a sum slot needs sum_out; both 8-byte aligned");
+    if (n_rows == 0) {      // nothing to launch; an overwriting call still owes its caller the (empty) sum
+        if (sum_slot != nullptr) {
+            hipError_t e = hipMemsetAsync(sum_out, 0, sizeof(double), sx_stream(stream));
+            if (e != hipSuccess) { sx_set_error("sx_flow_run3: hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
+        }
+        return SX_OK;
+    }
     sx_flow_args a;
     a.prog = d; a.blobs = blobs; a.x = x; a.latent = latent; a.in_col = in_col; a.out_col = out_col; a.y = y;
     a.ldj_out = ldj_out; a.logp_out = logp_out; a.sum_out = sum_out; a.mlp_out = mlp_out;
@@ -331,6 +356,15 @@ extern "C" int sx_flow_run2(const sx_program *prog_host, const float *blobs, con
     a.flags = err_flag;
     a.frag_in = nullptr; a.frag_out = nullptr; a.acc_out = nullptr;
     a.redo = redo; a.redo_pass = 0;
+    a.sum_slot = nullptr;
+    if (sum_slot != nullptr) {
+        if (redo != nullptr) {
+            a.sum_out = sum_slot;                  // (the redo pass hands the total over)
+        } else {
+            hipError_t e = hipMemsetAsync(sum_out, 0, sizeof(double), a.stream);
+            if (e != hipSuccess) { sx_set_error("sx_flow_run3: hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
+        }
+    }
     const int T = prog_host->tiles, H = prog_host->h_tiles;
     const int fam = SX_MODE_FAMILY(mlp_mode);       // one object per kernel-MODE family (sx_flow_types.h)
     // One launch -- or, with a redo list, two: the fp16 x 3 kernel names the samples whose operands left fp16's range (32-row group +
@@ -341,6 +375,7 @@ extern "C" int sx_flow_run2(const sx_program *prog_host, const float *blobs, con
         const int prec = pass == 0 ? precision : SX_GEMM_F32;
         if (pass == 1) {
             a.blobs = blobs_exact; a.redo_pass = 1; a.work = nullptr; a.flags = err_flag;
+            if (sum_slot != nullptr) { a.sum_out = sum_out; a.sum_slot = sum_slot; }
             if (a.grid > 256) a.grid = 256;        // (the list is short, or empty)
         }
         int rc2 = SX_E_UNSUPPORTED;
@@ -408,6 +443,7 @@ extern "C" int sx_flow_bwd_run(const sx_program *prog_host, const float *blobs, 
     a.stream = sx_stream(stream);
     a.row_t = g; a.side = nullptr; a.side_width = 0;
     a.redo = nullptr; a.redo_pass = 0;          // (the backward has no redo pass: an operand beyond fp16's range is flagged)
+    a.sum_slot = nullptr;
     const int rpb = 32 * SX_BLOCK_WAVES(prog_host->tiles, 11);
     const int64_t n_chunks = (n_rows + rpb - 1) / rpb;
     // single-step programs hand their chunks out statically: one workgroup per CU, every chunk the same work -- and without

@@ -92,6 +92,11 @@ __device__ __forceinline__ void rng_note(rng_t &rg, float m) {
     rg.bad |= __builtin_amdgcn_ballot_w64(m > rg.thr);              // v_cmp + s_or_b64
 #endif
 }
+// the redo pass closes an overwriting call (flow_kargs::sum_slot): the total leaves the slot for the caller's word, 0 stays behind
+__device__ __forceinline__ void redo_close_sum(double *slot, double *sum_out) {
+    *sum_out = __longlong_as_double((long long)atomicExch(reinterpret_cast<unsigned long long *>(slot), 0ull));
+}
+
 // one (32-row group, bad-sample mask) pair per sample tile of the wave onto the redo list (flow_kargs::redo)
 template <int NS>
 __device__ __forceinline__ void redo_push(uint32_t *redo, const rng_t &rg, int lane, uint32_t group0) {
@@ -1178,6 +1183,12 @@ struct flow_kargs {     // everything but the program, by value in the kernarg s
     // sums only the samples the mask names, and the last workgroup out empties the list.  NULL: rows are flagged as before.
     uint32_t *redo;
     int redo_pass;
+    // The SUM SLOT of the redo pass (sx_flow_run3): one fp64 accumulator, zero between calls.  The main launch has added its batch
+    // sum THERE (its sum_out points at the slot: that kernel is the same code whether it adds to the caller's word or to the slot);
+    // the redo pass adds the named samples' rows there too, and whoever closes the pass -- workgroup 0 when the list is empty, else
+    // the last workgroup out -- moves the total to sum_out and leaves 0 behind.  So the call leaves sum_out EQUAL to the batch sum
+    // whatever it held, with no zero-fill launched in front of it.  NULL: the pass adds into sum_out.
+    double *sum_slot;
 };
 
 // MODE 0: flow programs (coupling / affine-const steps); MODE 1: + persistent hidden state (MLP programs);
@@ -1202,9 +1213,20 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
 #endif
     const uint32_t redo_count = redo_pass ? k.redo[0] : 0u;
     if (redo_pass && (uint32_t)blockIdx.x * (uint32_t)(WB * NS) >= redo_count) {
-        if (threadIdx.x == 0) {      // (every workgroup reports, the last one out empties the list for the next call)
-            __threadfence();
-            if (atomicAdd(k.redo + 1, 1u) == gridDim.x - 1) { k.redo[0] = 0u; k.redo[1] = 0u; }
+        // (every workgroup reports, the last one out empties the list for the next call -- unless the list IS empty, the ordinary
+        //  case: word 1 is zero and stays zero, nobody counts, and workgroup 0 alone hands the main launch's sum over.  Word 0 is
+        //  written by the last workgroup out only, after every workgroup has read it: the whole grid takes the same branch.)
+        if (threadIdx.x == 0) {
+            if (redo_count == 0u) {
+                if (blockIdx.x == 0 && k.sum_slot != nullptr) redo_close_sum(k.sum_slot, k.sum_out);
+            } else {
+                __threadfence();
+                if (atomicAdd(k.redo + 1, 1u) == gridDim.x - 1) {
+                    __threadfence();
+                    if (k.sum_slot != nullptr) redo_close_sum(k.sum_slot, k.sum_out);
+                    k.redo[0] = 0u; k.redo[1] = 0u;
+                }
+            }
         }
         return;
     }
@@ -2138,10 +2160,6 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
         __threadfence();
         if (atomicAdd(k.work + 1, 1u) == gridDim.x - 1) { k.work[0] = 0u; k.work[1] = 0u; }
     }
-    if (redo_pass && threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(k.redo + 1, 1u) == gridDim.x - 1) { k.redo[0] = 0u; k.redo[1] = 0u; }
-    }
 #ifdef SX_F16X3
     if constexpr (MODE == 11) {
         // one partial per workgroup and layer, in wgrad_reduce_kernel's layout: [64 x 32 HT | 64] then [32 HT x 32 | 32 HT];
@@ -2205,7 +2223,16 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             double tot = 0.0;
 #pragma unroll
             for (int i = 0; i < WB; i += 4) tot += (part[i] + part[i + 1]) + (part[i + 2] + part[i + 3]);
-            atomicAdd(k.sum_out, tot);
+            atomicAdd(redo_pass && k.sum_slot != nullptr ? k.sum_slot : k.sum_out, tot);
+        }
+    }
+    // (the redo pass reports AFTER its rows' sum has gone out: whoever reports last sees every total)
+    if (redo_pass && threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(k.redo + 1, 1u) == gridDim.x - 1) {
+            __threadfence();
+            if (k.sum_slot != nullptr) redo_close_sum(k.sum_slot, k.sum_out);
+            k.redo[0] = 0u; k.redo[1] = 0u;
         }
     }
 }
@@ -2228,7 +2255,7 @@ static int sx_flow_launch_impl(const sx_flow_args &a) {
     k.mlp_out_stride = a.mlp_out_stride; k.n_rows = a.n_rows; k.mlp_out_dim = a.mlp_out_dim;
     k.buf_floats = a.buf_floats; k.bf16 = a.bf16; k.side_width = a.side_width; k.work = a.work; k.flags = a.flags;
     k.frag_in = a.frag_in; k.frag_out = a.frag_out; k.acc_out = a.acc_out;
-    k.redo = a.redo; k.redo_pass = a.redo_pass;
+    k.redo = a.redo; k.redo_pass = a.redo_pass; k.sum_slot = a.sum_slot;
 #define SX_FL(MD)                                                                                              \
     do {                                                                                                       \
         auto kern = flow_fused_kernel<NS, TX, HT, MD>;                                                         \

@@ -30,6 +30,7 @@ struct sx_flow_args {
     float *acc_out;
     uint32_t *redo;         // sx_flow_run2: the redo list (sx_flow_kernel.h, flow_kargs), or NULL
     int redo_pass;          // 1: this launch is the exact pass over the listed groups
+    double *sum_slot;       // sx_flow_run3: the redo pass's sum slot (sx_flow_kernel.h, flow_kargs), or NULL
 };
 
 

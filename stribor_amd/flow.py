@@ -723,9 +723,11 @@ class NormalizingFlow(Transform):
                           f'torch.no_grad() to silence this -- see INTEGRATION.md "Differentiable surface"',
                           RuntimeWarning, stacklevel=4)
 
-    def _run(self, x, reverse: bool, latent, want_y, want_ldj, want_logp, sum_out=None, base=None, **kwargs):
+    def _run(self, x, reverse: bool, latent, want_y, want_ldj, want_logp, sum_out=None, base=None, sum_overwrite=False, **kwargs):
         """Returns (y, ldj[..., 1], logp[..., 1]) (None where not requested) via the fused kernel, or None
-        when the flow cannot be fused.  base: the program is `_base_program` (one launch or None: no segments)."""
+        when the flow cannot be fused.  base: the program is `_base_program` (one launch or None: no segments).
+        sum_overwrite: sum_out ends up EQUAL to the batch sum (one launch: the kernel's overwrite mode; segments: zeroed first).
+        Where this returns None nothing was launched and sum_out is untouched."""
         _hip.require_device(x, 'x')
         t = kwargs.pop('t', None)
         if kwargs:          # unknown keyword: let the per-layer path hand it to every transform
@@ -741,7 +743,7 @@ class NormalizingFlow(Transform):
         prog = self._fused_program(reverse, x2.shape[1], ld, x.device, t_kind) if base is None else \
             self._base_program(x2.shape[1], ld, x.device, t_kind)
         if prog is not None:
-            y, ldj, logp = prog.run(x2, lat2, want_y, want_ldj, want_logp, sum_out, row_t=row_t)
+            y, ldj, logp = prog.run(x2, lat2, want_y, want_ldj, want_logp, sum_out, row_t=row_t, sum_overwrite=sum_overwrite)
             return shp(y, x2.shape[1]), shp(ldj, 1), shp(logp, 1)
         if base is not None:
             return None
@@ -753,6 +755,8 @@ class NormalizingFlow(Transform):
         cur = x2.to(torch.float32) if x2.dtype == torch.bfloat16 else x2
         need_l = want_ldj or want_logp
         acc = None
+        if sum_overwrite and sum_out is not None:
+            sum_out.zero_()                 # (every segment adds its part)
         for i, p in enumerate(segs):
             last = i == len(segs) - 1
             y, ldj, logp = p.run(cur, lat2, want_y or not last, need_l and not (last and want_logp and not want_ldj),
@@ -870,18 +874,20 @@ class NormalizingFlow(Transform):
         from .densities import _ParamDist
         return isinstance(self.base_dist, _ParamDist) and not getattr(self.base_dist, 'elementwise', False)
 
-    def _log_prob_param_base(self, y, latent, sum_out, kwargs):
+    def _log_prob_param_base(self, y, latent, sum_out, kwargs, sum_overwrite=False):
         """log_prob [..., 1] under a Normal / MultivariateNormal / Uniform base for a call that builds no graph.  One launch where
         `_base_program` plans (Normal, MultivariateNormal).  Otherwise two: the flow's own inverse pass leaves (z, log-det) and ONE
         launch of the base's kernel reads z once and adds the log-det (parameters outside the kernels' coverage: the closed form as
-        torch ops).  sum_out: the fp64 batch sum is accumulated there as well (log_prob_sum)."""
+        torch ops).  sum_out: the fp64 batch sum is accumulated there as well (log_prob_sum) -- or, with sum_overwrite, left there."""
         from .densities import log_prob_closed_form
         _hip.require_device(y, 'y')
         base = self.base_dist
         if hasattr(base, '_plan'):
-            r = self._run(y, True, latent, False, False, True, sum_out=sum_out, base=base, **kwargs)
+            r = self._run(y, True, latent, False, False, True, sum_out=sum_out, base=base, sum_overwrite=sum_overwrite, **kwargs)
             if r is not None:
                 return r[2]
+        if sum_overwrite and sum_out is not None:
+            sum_out.zero_()                 # (sx_sum_f64 below adds)
         # (bf16 storage: the latent stays fp32 up to the base density, as in the fused kernel)
         x, acc = self.inverse_and_log_det_jacobian(y.to(torch.float32) if y.dtype == torch.bfloat16 else y, latent=latent, **kwargs)
         x2, lead = flatten_rows(x)
@@ -896,20 +902,24 @@ class NormalizingFlow(Transform):
             _hip.call('sx_sum_f64', flat, flat.data_ptr(), flat.numel(), sum_out.data_ptr())
         return lp
 
-    def log_prob_sum(self, y, out: Optional[torch.Tensor] = None, latent=None) -> torch.Tensor:
+    def log_prob_sum(self, y, out: Optional[torch.Tensor] = None, latent=None, overwrite: bool = False) -> torch.Tensor:
         """Sum over the batch of log_prob as ONE fp64 scalar accumulated on the device (the operand of the multi-GPU
         all-reduce).  The per-sample log_prob [N] is still written (fp32, 4 B per row: `CompiledProgram.run` allocates it and the
-        kernel's epilogue stores it beside the fp64 block sums) -- the bench's algorithmic bytes count it."""
+        kernel's epilogue stores it beside the fp64 block sums) -- the bench's algorithmic bytes count it.
+        A caller's `out` is ADDED to; with overwrite=True it is left equal to the sum whatever it held.  In the one-launch fused
+        path that costs no fill: the redo pass behind the flow kernel hands the total over (sx_flow_run3).  out=None: a fresh buffer, overwritten."""
         if out is None:
-            out = torch.zeros(1, dtype=torch.float64, device=y.device)
+            out, overwrite = torch.empty(1, dtype=torch.float64, device=y.device), True
         from .dist.normal import UnitNormal
         if self._param_base() and not self._wants_grad(y):
-            self._log_prob_param_base(y, latent, out, {})
+            self._log_prob_param_base(y, latent, out, {}, sum_overwrite=overwrite)
             return out
         if isinstance(self.base_dist, UnitNormal):
-            r = self._run(y, True, latent, False, False, True, sum_out=out)
+            r = self._run(y, True, latent, False, False, True, sum_out=out, sum_overwrite=overwrite)
             if r is not None:
                 return out
+        if overwrite:
+            out.zero_()                     # (sx_sum_f64 below adds)
         lp = self.log_prob(y, latent=latent).reshape(-1).contiguous()
         _hip.call('sx_sum_f64', lp, lp.data_ptr(), lp.numel(), out.data_ptr())
         return out

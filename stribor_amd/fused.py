@@ -497,8 +497,9 @@ class CompiledProgram:
     def run(self, x: torch.Tensor, latent: Optional[torch.Tensor] = None, want_y: bool = False,
             want_ldj: bool = False, want_logp: bool = False, sum_out: Optional[torch.Tensor] = None,
             mlp_out: Optional[torch.Tensor] = None, row_t: Optional[torch.Tensor] = None,
-            side: Optional[torch.Tensor] = None, exact: bool = False):
+            side: Optional[torch.Tensor] = None, exact: bool = False, sum_overwrite: bool = False):
         """x: [N, dim] contiguous on the program's device.  Returns (y | None, ldj | None, logp | None).
+        sum_overwrite: the launch leaves sum_out EQUAL to the batch sum whatever it held (sx_flow_run3) instead of adding to it.
         exact: run on the exact-fp32 objects whatever the global arithmetic (HBM-bound single layers: net/mlp.py BatchLinear)."""
         _hip.require_device(x, 'x')
         assert x.dim() == 2 and x.shape[1] == (self.prog.pad_ or self.prog.dim), (x.shape, self.prog.dim, self.prog.pad_)
@@ -510,6 +511,8 @@ class CompiledProgram:
         n = x.shape[0]
         if n == 0:        # empty batch: nothing to launch (the reference returns empty tensors too)
             e = lambda *shape, dt=torch.float32: torch.empty(*shape, dtype=dt, device=x.device)
+            if sum_overwrite and sum_out is not None:
+                sum_out.zero_()
             return (e(0, x.shape[1], dt=x.dtype) if want_y else None, e(0) if want_ldj else None,
                     e(0) if want_logp else None)
         y = torch.empty_like(x) if want_y else None
@@ -532,21 +535,24 @@ class CompiledProgram:
         with _hip.device_of(x):                     # the library launches on the CURRENT device's stream
             work = _hip.work_counters(x.device)
             flag = _hip.err_flag(x.device)
+            slot = _hip.sum_slot(x.device) if (sum_overwrite and sum_out is not None) else None
 
             def launch(prec, redo=False):
                 # redo: the fp16 x 3 launch names the samples whose operands left fp16's range and the exact-fp32 kernel evaluates
                 # them in a second launch (sx_flow_run2) -- any finite fp32 row at fp32-grade error, no flag, no synchronisation
                 redo = redo and prec == _hip.GEMM_F16X3 and side is None and _hip.redo_allowed()
-                rc = _hip.lib().sx_flow_run2(C.byref(self.prog), self.blobs_for(prec).data_ptr(),
+                rc = _hip.lib().sx_flow_run3(C.byref(self.prog), self.blobs_for(prec).data_ptr(),
                                              self.blobs_for(_hip.GEMM_F32).data_ptr() if redo else None,
                                              _hip.redo_list(x.device, n).data_ptr() if redo else None, x.data_ptr(),
                                              _hip.ptr(latent), _hip.ptr(self.in_col), _hip.ptr(self.out_col), _hip.ptr(y),
                                              _hip.ptr(ldj), _hip.ptr(logp), _hip.ptr(sum_out),
                                              None if mlp_out is None else mlp_out.data_ptr() + 4 * self.mlp_col0, stride,
                                              mlp_dim, _hip.ptr(row_t), _hip.ptr(side), n, _hip.dtype_code(x),
-                                             prec, work.data_ptr(), flag, _hip.stream())
+                                             prec, work.data_ptr(), flag, _hip.stream(), _hip.ptr(slot))
                 if rc != 0:
                     work.zero_()                    # a failed launch may leave the ticket pair armed
+                    if slot is not None:
+                        slot.zero_()                # ... and the sum slot
                     if redo:
                         _hip.redo_list(x.device, n).zero_()      # ... and, where the second launch did not happen, a list that is not empty
                 _hip.check(rc, 'sx_flow_run')

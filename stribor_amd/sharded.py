@@ -36,14 +36,16 @@ class ShardedLogProb:
     """sum_n log p(y_n) over a batch sharded across the ranks of `group`.
 
     `local_sum(y_local, out)` must add the fp64 sum of the local rows' log-probs into `out` (a 1-element
-    fp64 tensor on y_local's device).  By default that is `flow.log_prob_sum` (fused HIP kernel)."""
+    fp64 tensor on y_local's device), which is zeroed for it.  By default that is `flow.log_prob_sum` (fused HIP
+    kernel) in its overwrite mode: the launches themselves leave the sum in `out`, so no zero-fill is launched."""
 
     def __init__(self, flow=None, group: Optional[dist.ProcessGroup] = None,
                  local_sum: Optional[Callable[[torch.Tensor, torch.Tensor], None]] = None):
+        self.overwrites = local_sum is None          # the flow's own sum leaves `out` equal to the sum whatever it held
         if local_sum is None:
             if flow is None:
                 raise ValueError('give a flow or a local_sum callable')
-            local_sum = lambda y, out: flow.log_prob_sum(y, out)
+            local_sum = lambda y, out: flow.log_prob_sum(y, out, overwrite=True)
         self.local_sum = local_sum
         self.group = group
 
@@ -62,7 +64,8 @@ class ShardedLogProb:
         """Enqueue the local sum and its all-reduce without making the compute stream wait for the collective: the
         8-byte exchange of batch i (latency-bound, ~tens of microseconds) then runs under the kernel of batch i+1.
         ``out`` must not be reused before ``.wait()`` of the handle that owns it."""
-        out.zero_()
+        if not self.overwrites:
+            out.zero_()
         self.local_sum(y_local, out)
         work = None
         if dist.is_initialized() and self.world > 1:
@@ -72,8 +75,8 @@ class ShardedLogProb:
     def log_prob_sum(self, y_local: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """All ranks return the global sum (fp64, 1 element)."""
         if out is None:
-            out = torch.zeros(1, dtype=torch.float64, device=y_local.device)
-        else:
+            out = torch.empty(1, dtype=torch.float64, device=y_local.device)
+        if not self.overwrites:
             out.zero_()
         self.local_sum(y_local, out)
         if dist.is_initialized() and self.world > 1:
