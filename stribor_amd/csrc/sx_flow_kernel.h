@@ -748,6 +748,192 @@ __device__ __forceinline__ void coupling_affine_pf(tile<NS> (&xs)[TX], const wpt
 #pragma unroll
     for (int n = 0; n < NS; ++n) ldj[n] += st.ldj_scale * (s[n].x + s[n].y);
 }
+// ---- the split step on 1 + 1 tiles, hidden 33..64 (MODE 5 / 6, cfg 2), scheduled at k16-step grain -----------------------------
+// The same instructions as coupling_affine<.., 2, 2, ..>, every accumulator fed in the same order (k-tile 0 then 1, step 0 then 1,
+// smallest term first), so each row's result is the same bits; what changes is where the vector work stands.  The unit is a GROUP:
+// the three MFMAs (al.bhi, ah.blo, ah.bhi) of one k16-step of one output tile, with a GAP behind each MFMA that takes riders of at
+// most 24 issue cycles (a transcendental 8, anything else 4: tools/gap_census.py counts them in the assembly).  Nothing new is live:
+// a group's two A fragments are requested behind the previous group's last MFMA, one set.
+//   [X 0-3]  H0.s0 H1.s0 {X 4-7}  H0.s1 {nop}  H1.s1 {S h0 ..}  [S h0 pairs ..3, P h0 0-3]
+//   LS.k0s0 SH.k0s0 {S h0 4-7}  [P h0 4-7]  LS.k0s1 SH.k0s1 {S h1 0-3}  [P h1 0-3]  LS.k1s0 SH.k1s0 {S h1 4-7}  [P h1 4-7]
+//   LS.k1s1 {nop}  SH.k1s1 {E ..}  [E, F]
+// X = tracked split of a source pair, S = exp2, add, rcp of a hidden pair, P = its split, E = log-det add + exp2 of a log-scale
+// pair, F = the affine map; {..} rides in the gaps, [..] is not covered by MFMAs of this wave.  Every rider's result passes
+// through `pinned` (see coupling_affine_pf) and a scheduling fence closes every gap.
+struct ks_frag { h8 ah, al; };
+__device__ __forceinline__ ks_frag ks_load(const char *wb, int a_off, int s) {
+    const u32x4 ahu = *reinterpret_cast<const u32x4 *>(wb + (a_off + (2 * s) * 256) * 4);       // ds_read_b128, imm offset
+    const u32x4 alu = *reinterpret_cast<const u32x4 *>(wb + (a_off + (2 * s + 1) * 256) * 4);
+    return ks_frag{__builtin_bit_cast(h8, ahu), __builtin_bit_cast(h8, alu)};
+}
+__device__ __forceinline__ uint32_t pinned_u(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
+template <int LO, int HI, class F>
+__device__ __forceinline__ void ks_ops(F &&f) {
+#pragma unroll
+    for (int j = LO; j < HI; ++j) f(j);
+}
+template <int NS, class R1, class R2, class R3>
+__device__ __forceinline__ void ks_group(tile<NS> &acc, const ks_frag &a, const u32x4 (&hi)[NS][2], const u32x4 (&lo)[NS][2], int s,
+                                         R1 &&r1, R2 &&r2, R3 &&r3) {
+#pragma unroll
+    for (int n = 0; n < NS; ++n) { acc.v[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.al, __builtin_bit_cast(h8, hi[n][s]), acc.v[n], 0, 0, 0); SX_PIN_ACC(acc.v[n]); }
+    __builtin_amdgcn_sched_barrier(0);          // (a rider is a pure instruction too: unfenced it rises above the MFMA it rides under)
+    r1();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int n = 0; n < NS; ++n) { acc.v[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.ah, __builtin_bit_cast(h8, lo[n][s]), acc.v[n], 0, 0, 0); SX_PIN_ACC(acc.v[n]); }
+    __builtin_amdgcn_sched_barrier(0);
+    r2();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int n = 0; n < NS; ++n) { acc.v[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.ah, __builtin_bit_cast(h8, hi[n][s]), acc.v[n], 0, 0, 0); SX_PIN_ACC(acc.v[n]); }
+    __builtin_amdgcn_sched_barrier(0);
+    r3();
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int NS, int C0, int T0, bool REV>
+__device__ __forceinline__ void coupling_affine_ks(tile<NS> (&xs)[2], const wptr w, const dstep &st, float (&ldj)[NS], rng_t &rg) {
+    constexpr int bias1 = 2 * 1024;                // pack_linear(W1: 2 m-tiles, 1 k-tile)
+    constexpr int a2 = bias1 + 2 * 32;             // pack_linear(W2: (ls, sh) m-tiles, 2 k-tiles): tile (r, k) at a2 + (2 r + k) * 1024
+    constexpr int b2 = a2 + 4 * 1024;
+    static_assert(NS == 1, "coupling_affine_ks: one sample tile per wave");
+    const tile<NS> &src = xs[C0];
+    tile<NS> &x = xs[T0];
+    float mx;
+    float t0[NS][4], t1[NS][4];                    // the residuals of the four pairs a split stream stands at
+    u32x4 xhi[NS][2], xlo[NS][2], phi[NS][2], plo[NS][2];
+    f32x2 sum[NS];
+#pragma unroll
+    for (int n = 0; n < NS; ++n) sum[n] = f32x2{0.f, 0.f};
+    // the two groups that have no rider: the wave stands aside for six cycles behind each of their MFMAs, so its SIMD partners' vector
+    // work gets the issue port (measured: profiles/ab_head_kstep_cfg2.txt -- the schedule alone ties the old step, with this -1.3 %)
+    auto aside = [] { asm volatile("s_nop 5"); };
+    // Every stream runs four chains abreast (a transcendental's or an asm statement's result costs wait states when the next
+    // instruction reads it: chain by chain the riders came with 93 s_nop per arm)
+    // X: (max3, cvt) x 4, residual x 8, cvt x 4 on the four source pairs 4 (j / 20) ..
+    auto x_op = [&](int j) {
+        const int q = 4 * (j / 20), k = j % 20;
+        const int p = q + (k < 8 ? k / 2 : (k < 16 ? (k - 8) / 2 : k - 16));
+#pragma unroll
+        for (int n = 0; n < NS; ++n) {
+            const float v0 = src.v[n][2 * p], v1 = src.v[n][2 * p + 1];
+            const uint32_t ph = xhi[n][p >> 2][p & 3];
+            if (k < 8 && !(k & 1)) {
+                if (j == 0) asm("v_max3_f32 %0, 0, |%1|, |%2|" : "=v"(mx) : "v"(v0), "v"(v1));      // (no register for the chain's zero)
+                else mx = rng_max(mx, v0, v1);
+                mx = pinned(mx);
+            } else if (k < 8) xhi[n][p >> 2][p & 3] = pinned_u(pk_f16(v0, v1));
+            else if (k < 16 && !(k & 1)) { asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(t0[n][p & 3]) : "v"(ph), "v"(v0)); t0[n][p & 3] = pinned(t0[n][p & 3]); }
+            else if (k < 16) { asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(t1[n][p & 3]) : "v"(ph), "v"(v1)); t1[n][p & 3] = pinned(t1[n][p & 3]); }
+            else xlo[n][p >> 2][p & 3] = pinned_u(pk_f16(t0[n][p & 3], t1[n][p & 3]));
+        }
+    };
+    // S: exp2 x 4, add x 4, rcp x 4 on the hidden registers 4 (j / 12) .., in place
+    auto s_op = [&](float (&h)[NS][16], int j) {
+        const int k = j % 12, r = 4 * (j / 12) + (k & 3);
+#pragma unroll
+        for (int n = 0; n < NS; ++n) {
+            const float v = h[n][r];
+            h[n][r] = pinned(k < 4 ? __builtin_amdgcn_exp2f(v) : (k < 8 ? v + 1.0f : __builtin_amdgcn_rcpf(v)));
+        }
+    };
+    // P: cvt x 4, residual x 8, cvt x 4 on the four activated pairs 4 (j / 16) .. (bounded: not tracked)
+    auto p_op = [&](const float (&h)[NS][16], int j) {
+        const int q = 4 * (j / 16), k = j % 16;
+        const int p = q + (k < 4 ? k : (k < 12 ? (k - 4) / 2 : k - 12));
+#pragma unroll
+        for (int n = 0; n < NS; ++n) {
+            const float v0 = h[n][2 * p], v1 = h[n][2 * p + 1];
+            const uint32_t ph = phi[n][p >> 2][p & 3];
+            if (k < 4) phi[n][p >> 2][p & 3] = pinned_u(pk_f16(v0, v1));
+            else if (k < 12 && !(k & 1)) { asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(t0[n][p & 3]) : "v"(ph), "v"(v0)); t0[n][p & 3] = pinned(t0[n][p & 3]); }
+            else if (k < 12) { asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(t1[n][p & 3]) : "v"(ph), "v"(v1)); t1[n][p & 3] = pinned(t1[n][p & 3]); }
+            else plo[n][p >> 2][p & 3] = pinned_u(pk_f16(t0[n][p & 3], t1[n][p & 3]));
+        }
+    };
+    tile<NS> ls, sh;
+    // E: the log-det adds of log-scale pair p = j / 4, then its exp2 in place
+    auto e_op = [&](int j) {
+        const int p = j / 4, k = j % 4;
+#pragma unroll
+        for (int n = 0; n < NS; ++n) {
+            if (k == 0) sum[n].x = pinned(sum[n].x + ls.v[n][2 * p]);
+            else if (k == 1) sum[n].y = pinned(sum[n].y + ls.v[n][2 * p + 1]);
+            else ls.v[n][2 * p + k - 2] = pinned(__builtin_amdgcn_exp2f(ls.v[n][2 * p + k - 2]));
+        }
+    };
+    // F: the affine map of pair p
+    auto f_op = [&](int p) {
+#pragma unroll
+        for (int n = 0; n < NS; ++n) {
+            const f32x2 xv = {x.v[n][2 * p], x.v[n][2 * p + 1]}, sv = {sh.v[n][2 * p], sh.v[n][2 * p + 1]};
+            const f32x2 ev = {ls.v[n][2 * p], ls.v[n][2 * p + 1]};
+            const f32x2 yv = REV ? pk_mul(pk_sub(xv, sv), ev) : pk_add(pk_mul(xv, ev), sv);
+            x.v[n][2 * p] = yv.x;
+            x.v[n][2 * p + 1] = yv.y;
+        }
+    };
+    tile<NS> c0, c1;
+    float h0[NS][16], h1[NS][16];                  // the hidden tiles as single registers once their GEMM is done: halves die separately
+    ks_frag f, g;
+    ks_ops<0, 5>(x_op);
+    __builtin_amdgcn_sched_barrier(0);
+    c0 = load_cfrag<NS>(w.cb, bias1);
+    f = ks_load(w.wb, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    ks_ops<5, 20>(x_op);
+    __builtin_amdgcn_sched_barrier(0);
+    ks_group<NS>(c0, f, xhi, xlo, 0, [&] { ks_ops<20, 24>(x_op); }, [&] { ks_ops<24, 28>(x_op); },
+                 [&] { c1 = load_cfrag<NS>(w.cb, bias1 + 32); g = ks_load(w.wb, 1024, 0); ks_ops<28, 31>(x_op); });
+    ks_group<NS>(c1, g, xhi, xlo, 0, [&] { ks_ops<31, 34>(x_op); }, [&] { ks_ops<34, 37>(x_op); },
+                 [&] { f = ks_load(w.wb, 0, 1); ks_ops<37, 40>(x_op); rng_note(rg, mx); });
+    ks_group<NS>(c0, f, xhi, xlo, 1, aside, aside, [&] { aside(); g = ks_load(w.wb, 1024, 1); });
+#pragma unroll
+    for (int n = 0; n < NS; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h0[n][r] = c0.v[n][r];
+    ks_group<NS>(c1, g, xhi, xlo, 1, [&] { ks_ops<0, 3>([&](int j) { s_op(h0, j); }); }, [&] { ks_ops<3, 8>([&](int j) { s_op(h0, j); }); },
+                 [&] { f = ks_load(w.wb, a2, 0); ks_ops<8, 11>([&](int j) { s_op(h0, j); }); });
+#pragma unroll
+    for (int n = 0; n < NS; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h1[n][r] = c1.v[n][r];
+    ks_ops<11, 24>([&](int j) { s_op(h0, j); });
+    ks_ops<0, 8>([&](int j) { p_op(h0, j); });
+    __builtin_amdgcn_sched_barrier(0);
+    ls = load_cfrag<NS>(w.cb, b2);                 // (the output biases as late as their first MFMA allows: 32 registers)
+    __builtin_amdgcn_sched_barrier(0);
+    ks_ops<8, 16>([&](int j) { p_op(h0, j); });
+    __builtin_amdgcn_sched_barrier(0);
+    // the output layer: k-tile 0 under the rest of h0's and the first half of h1's activation, k-tile 1 under the second half
+    ks_group<NS>(ls, f, phi, plo, 0, [&] { ks_ops<24, 27>([&](int j) { s_op(h0, j); }); }, [&] { ks_ops<27, 32>([&](int j) { s_op(h0, j); }); },
+                 [&] { sh = load_cfrag<NS>(w.cb, b2 + 32); g = ks_load(w.wb, a2 + 2 * 1024, 0); ks_ops<32, 35>([&](int j) { s_op(h0, j); }); });
+    ks_group<NS>(sh, g, phi, plo, 0, [&] { ks_ops<35, 38>([&](int j) { s_op(h0, j); }); }, [&] { ks_ops<38, 42>([&](int j) { s_op(h0, j); }); },
+                 [&] { f = ks_load(w.wb, a2, 1); ks_ops<42, 46>([&](int j) { s_op(h0, j); }); });
+    ks_ops<46, 48>([&](int j) { s_op(h0, j); });
+    ks_ops<16, 32>([&](int j) { p_op(h0, j); });
+    __builtin_amdgcn_sched_barrier(0);
+    ks_group<NS>(ls, f, phi, plo, 1, [&] { ks_ops<0, 3>([&](int j) { s_op(h1, j); }); }, [&] { ks_ops<3, 8>([&](int j) { s_op(h1, j); }); },
+                 [&] { g = ks_load(w.wb, a2 + 2 * 1024, 1); ks_ops<8, 11>([&](int j) { s_op(h1, j); }); });
+    ks_group<NS>(sh, g, phi, plo, 1, [&] { ks_ops<11, 14>([&](int j) { s_op(h1, j); }); }, [&] { ks_ops<14, 18>([&](int j) { s_op(h1, j); }); },
+                 [&] { f = ks_load(w.wb, a2 + 1024, 0); ks_ops<18, 22>([&](int j) { s_op(h1, j); }); });
+    ks_ops<22, 24>([&](int j) { s_op(h1, j); });
+    ks_ops<0, 16>([&](int j) { p_op(h1, j); });
+    __builtin_amdgcn_sched_barrier(0);
+    ks_group<NS>(ls, f, phi, plo, 0, [&] { ks_ops<24, 27>([&](int j) { s_op(h1, j); }); }, [&] { ks_ops<27, 32>([&](int j) { s_op(h1, j); }); },
+                 [&] { g = ks_load(w.wb, a2 + 3 * 1024, 0); ks_ops<32, 35>([&](int j) { s_op(h1, j); }); });
+    ks_group<NS>(sh, g, phi, plo, 0, [&] { ks_ops<35, 38>([&](int j) { s_op(h1, j); }); }, [&] { ks_ops<38, 42>([&](int j) { s_op(h1, j); }); },
+                 [&] { f = ks_load(w.wb, a2 + 1024, 1); ks_ops<42, 46>([&](int j) { s_op(h1, j); }); });
+    ks_ops<46, 48>([&](int j) { s_op(h1, j); });
+    ks_ops<16, 32>([&](int j) { p_op(h1, j); });
+    __builtin_amdgcn_sched_barrier(0);
+    ks_group<NS>(ls, f, phi, plo, 1, aside, aside, [&] { aside(); g = ks_load(w.wb, a2 + 3 * 1024, 1); });
+    ks_group<NS>(sh, g, phi, plo, 1, [&] { ks_ops<0, 4>(e_op); }, [&] { ks_ops<4, 8>(e_op); }, [&] { ks_ops<8, 12>(e_op); });
+    ks_ops<12, 32>(e_op);
+    ks_ops<0, 8>(f_op);
+#pragma unroll
+    for (int n = 0; n < NS; ++n) ldj[n] += st.ldj_scale * (sum[n].x + sum[n].y);
+}
 #endif
 // Deep conditioners (>= 2 hidden layers, kernel MODE 9): the earlier hidden layers ran as their own steps and left their
 // activations in `hsrc`; this step evaluates the last hidden layer from them, then the output layer and the affine map.
@@ -1553,6 +1739,12 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             if constexpr (MODE == 5 || MODE == 6) {
                 // pure split-coupling programs (host: validate_and_convert): two straight-line arms, state in place
                 if constexpr (TX >= 2) {
+#ifdef SX_F16X3
+                    if constexpr (TX == 2 && HT == 2) {        // one source, one transformed tile, hidden 33..64: the k16-step-grain schedule
+                        if (st.c0 == 0) coupling_affine_ks<NS, 0, 1, MODE == 5>(xs, w, st, ldj, rg);
+                        else coupling_affine_ks<NS, 1, 0, MODE == 5>(xs, w, st, ldj, rg);
+                    } else
+#endif
                     if (st.c0 == 0) coupling_affine<NS, TX, HT, 0, TX / 2, TX / 2, TX / 2, true, MODE == 5>(xs, w, st, ldj, rg);
                     else coupling_affine<NS, TX, HT, TX / 2, TX / 2, 0, TX / 2, true, MODE == 5>(xs, w, st, ldj, rg);
                 }
