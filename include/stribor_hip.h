@@ -770,6 +770,26 @@ size_t sx_cnf_lds_bytes(const sx_cnf_net *net_host, int32_t want_ldj);
 int sx_cnf_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int64_t n_rows,
                 int32_t solver, int32_t n_steps, float t0, float t1, float step_size, int32_t want_ldj, void *stream);
 
+/* ---- the dense CNF under a per-sample adaptive solver (ContinuousTransform with solver='dopri5_per_sample'; cnf.py:127-130, 139-140,
+ * 204-212: where the reference hands atol / rtol / method to an adaptive odeint) ----
+ * The network is an sx_cnf_net within: dim <= 32, 1 + dim + latent_dim <= 128, one or two hidden layers of <= 64 units, the
+ * activations of sx_cnf_flow.  Dormand-Prince 5(4) with FSAL and ONE STEP-SIZE CONTROLLER PER ROW (the specification: DESIGN.md
+ * "CNF"): a row's result does not depend on the rows that share its batch. */
+
+/* Bytes of LDS the launch stages for this network (the forward images and the trace constants); 0 outside the coverage above.
+ * Never launches. */
+size_t sx_cnf_adaptive_lds_bytes(const sx_cnf_net *net_host);
+
+/* x, y: fp32 [n_rows, dim] (may alias); latent: fp32 [n_rows, latent_dim] or NULL; ldj: fp32 [n_rows], the integral of tr df/dx from
+ * t0 to t1 (written iff want_trace, which also makes it part of the error norm; sign as sx_cnf_flow's); stats: int32 [n_rows, 3] =
+ * (accepted steps, rejected steps, status: 0 done, 1 more than max_num_steps attempts, 2 step-size underflow or a non-finite error
+ * ratio).  A row whose status is not 0 ends with y = ldj = NaN.  rtol, atol >= 0; first_step <= 0: chosen per row by Hairer's rule
+ * (one more evaluation); max_num_steps: 1 .. 2^20 attempts per row, after which the row gives up -- the launch always ends.  A row
+ * costs 1 (+ 1 with an automatic first step) + 6 (accepted + rejected) evaluations of the network. */
+int sx_cnf_adaptive_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int32_t *stats,
+                         int64_t n_rows, float t0, float t1, float rtol, float atol, float first_step, int32_t max_num_steps,
+                         int32_t want_trace, void *stream);
+
 /* ---- training the dense CNF: the Hutchinson forward and its discrete adjoint (ContinuousTransform with divergence='approximate' in
  * training mode, cnf.py:76-97) ----
  * The network is an sx_cnf_net -- its `trace` is not read -- within: dim <= SX_CNF_TRAIN_MAX_DIM, 1 + dim + latent_dim <= SX_CNF_TRAIN_MAX_IN,

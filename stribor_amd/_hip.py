@@ -64,6 +64,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow',
            'sx_cnf_exact_attn_lds_bytes', 'sx_cnf_exact_attn_flow',
            'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd',
+           'sx_cnf_adaptive_lds_bytes', 'sx_cnf_adaptive_flow',
            'sx_base_logprob', 'sx_normal_bwd_partial_floats', 'sx_normal_logprob_bwd', 'sx_mvn_lds_bytes', 'sx_mvn_logprob']
 
 # base densities (include/stribor_hip.h: sx_base_logprob / sx_mvn_logprob)
@@ -79,6 +80,9 @@ RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
 CNF_MAX_DIM = 64
 CNF_LDS_BYTES = 160 * 1024
 CNF_SOLVERS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
+# ... under the per-sample adaptive solver (sx_cnf_adaptive_flow)
+CNF_ADAPTIVE_MAX_DIM, CNF_ADAPTIVE_MAX_IN, CNF_ADAPTIVE_MAX_HIDDEN, CNF_ADAPTIVE_MAX_STEPS = 32, 128, 64, 1 << 20
+CNF_ADAPTIVE_DONE, CNF_ADAPTIVE_STEP_CAP, CNF_ADAPTIVE_UNDERFLOW = 0, 1, 2
 # ... training the dense CNF (sx_cnf_train_fwd / sx_cnf_train_bwd)
 CNF_TRAIN_MAX_DIM, CNF_TRAIN_MAX_IN, CNF_TRAIN_MAX_HIDDEN = 32, 64, 32
 # ... over sets (sx_cnf_set_flow)
@@ -312,6 +316,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_lds_bytes.argtypes = [C.POINTER(sx_cnf_net), i32]
     lib.sx_cnf_flow.restype = i32
     lib.sx_cnf_flow.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_cnf_adaptive_lds_bytes.restype = C.c_size_t
+    lib.sx_cnf_adaptive_lds_bytes.argtypes = [C.POINTER(sx_cnf_net)]
+    lib.sx_cnf_adaptive_flow.restype = i32
+    lib.sx_cnf_adaptive_flow.argtypes = [C.POINTER(sx_cnf_net), vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, i32, vp]
     lib.sx_cnf_train_lds_bytes.restype = C.c_size_t
     lib.sx_cnf_train_lds_bytes.argtypes = [C.POINTER(sx_cnf_net), i32]
     lib.sx_cnf_train_partial_floats.restype = i64

@@ -2,8 +2,18 @@
 
 Same constructor, methods and ``state_dict`` keys (``odefunc.diffeq.net.net.0.weight``, ..., ``odefunc._num_evals``).  The solve
 runs on a FIXED grid with ``solver='euler' | 'midpoint' | 'rk4'`` (torchdiffeq 0.2.2's fixed-grid family; ``rk4`` is the 3/8
-rule); the adaptive and Adams solver names are accepted -- they are the reference's defaults and checkpoints must load -- and
-raise ``NotImplementedError`` when evaluated (DESIGN.md "CNF").
+rule), or under ``solver='dopri5_per_sample'`` with error control to ``atol`` / ``rtol``; the reference's adaptive and Adams solver
+names are accepted -- they are its defaults and checkpoints must load -- and raise ``NotImplementedError`` when evaluated (DESIGN.md
+"CNF").
+
+``'dopri5_per_sample'`` is Dormand-Prince 5(4) with ONE STEP-SIZE CONTROLLER PER SAMPLE (a row; under ``set_data`` a set): the error
+norm is taken over the sample's own entries, so its result does not depend on its batch, and the last step lands on T exactly -- two
+deliberate differences from torchdiffeq's ``dopri5``, which is why that name still raises.  In the dense tier's setting without a
+graph, a ``DiffeqMLP`` with dim <= 32, 1 + dim + latent <= 128 and hidden layers of <= 64 units is ONE launch of
+``sx_cnf_adaptive_flow`` (time is the net's first input column, so every row of a tile carries its own time).  Sets, masks, calls
+that want a graph, training mode and the other five tiers' nets all run the same controller as torch ops for now
+(``_solve_composed_adaptive``; with a graph: through the accepted steps, step sizes frozen).  ``last_solver_stats`` holds (accepted,
+rejected, status) per sample.
 
 Without an autograd graph, a ``DiffeqMLP`` with one or two hidden layers is ONE launch of ``sx_cnf_flow``: the state, the stage
 vectors and the log-det accumulator stay in registers for the whole grid, the weights sit in LDS, and the exact divergence comes
@@ -68,7 +78,34 @@ from ..util.divergence import divergence_approx, divergence_exact, divergence_ex
 __all__ = ['ContinuousTransform']
 
 FIXED_SOLVERS = ('euler', 'midpoint', 'rk4')
+ADAPTIVE_SOLVERS = ('dopri5_per_sample',)
 STAGES = {'euler': 1, 'midpoint': 2, 'rk4': 4}
+MAX_NUM_STEPS = 4096          # attempts per sample before an adaptive solve gives up: a safety cap, not a tuned value
+
+
+def _r32(v: float) -> float:
+    """The fp32 rounding of an fp64 value, as a Python float (tensor * float then multiplies by exactly that fp32 number)."""
+    return float(np.float32(v))
+
+
+class DormandPrince(NamedTuple):
+    """The Dormand-Prince 5(4) tableau of 'dopri5_per_sample' (DESIGN.md "CNF") in fp64: a[i] = the weights of k1 .. k_i in the input
+    of stage i + 1 (a[6] = b: FSAL), the nodes c, the solution weights b and the error weights e = b - b*."""
+    a: tuple
+    c: tuple
+    b: tuple
+    e: tuple
+
+
+def _dormand_prince() -> DormandPrince:
+    b = (35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84, 0.0)
+    b_star = (5179 / 57600, 0.0, 7571 / 16695, 393 / 640, -92097 / 339200, 187 / 2100, 1 / 40)
+    a = ((), (1 / 5,), (3 / 40, 9 / 40), (44 / 45, -56 / 15, 32 / 9), (19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729),
+         (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656), b[:6])
+    return DormandPrince(a, (0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0), b, tuple(p - q for p, q in zip(b, b_star)))
+
+
+DOPRI5 = _dormand_prince()
 _DIVERGENCES = ('compute', 'compute_set', 'approximate', 'exact', 'none')
 
 
@@ -278,7 +315,9 @@ class ODEfunc(nn.Module):
     def forward(self, t, states):
         """states = (x, a[, latent][, mask]) -> their time derivatives (zeros for latent and mask)."""
         y = states[0]
-        t = torch.as_tensor(t).reshape(1).to(y)
+        t = torch.as_tensor(t)
+        # (one time for all, or -- an adaptive solve -- one per sample, shaped to broadcast against y[..., :1])
+        t = (t.reshape(1) if t.numel() == 1 else t).to(y)
         latent = mask = None
         if len(states) == 4:
             latent, mask = states[2], states[3]
@@ -354,9 +393,11 @@ class ContinuousTransform(Transform):
 
     solver: 'euler', 'midpoint' or 'rk4' run (fixed grid; ``solver_options={'step_size': h}``, else the single step [0, T]).  The
     reference's default 'dopri5' and the other adaptive / Adams names construct and load but raise ``NotImplementedError`` when
-    evaluated: pass ``solver='rk4', solver_options={'step_size': ...}``.  ``use_adjoint`` is recorded and does not change the
+    evaluated: pass ``solver='rk4', solver_options={'step_size': ...}``, or ``solver='dopri5_per_sample'`` for error control to
+    ``atol`` / ``rtol`` per sample (``solver_options``: ``first_step``, else chosen per sample; ``max_num_steps``, default 4096 attempts
+    per sample, after which the sample returns NaN with status 1 in ``last_solver_stats``).  ``use_adjoint`` is recorded and does not change the
     arithmetic: gradients are those of ``odeint`` through the discretised steps (``odeint_adjoint``'s differ from them by
-    discretisation error only).  ``atol`` / ``rtol`` are recorded; a fixed grid does not use them."""
+    discretisation error only).  ``atol`` / ``rtol`` steer 'dopri5_per_sample'; a fixed grid does not use them."""
 
     def __init__(self, dim: int, net: nn.Module = None, T: float = 1.0, divergence: str = 'approximate', use_adjoint: bool = True,
                  has_latent: bool = False, solver: str = 'dopri5', solver_options: Optional[Dict] = {}, test_solver: str = None,
@@ -375,23 +416,44 @@ class ContinuousTransform(Transform):
         self.rtol = rtol
         self._trace = ProgramCache()
         self._last_path = None             # 'kernel' | 'composed': which path the last call took (tests, tools/bench_cnf.py)
+        self.last_solver_stats = None      # an adaptive solve's int32 [..., 3] per sample: accepted steps, rejected steps, status
 
     # ---- the grid ---------------------------------------------------------------------------------------------------------------
+    def _solver_name(self):
+        return self.solver if self.training else self.test_solver
+
     def _solver(self):
-        name = self.solver if self.training else self.test_solver
+        name = self._solver_name()
         opts = self.solver_options if self.training else self.test_solver_options
+        if name in ADAPTIVE_SOLVERS:
+            self._adaptive_options()
+            return name, None
         if name not in FIXED_SOLVERS:
             raise NotImplementedError(
                 f'stribor_amd: solver {name!r} is not implemented; the implemented solvers are {", ".join(FIXED_SOLVERS)} on a fixed '
-                f"grid -- e.g. solver='rk4', solver_options={{'step_size': 0.05}}")
+                f"grid -- e.g. solver='rk4', solver_options={{'step_size': 0.05}} -- and {', '.join(ADAPTIVE_SOLVERS)} with atol / rtol")
         opts = dict(opts or {})
         step = opts.pop('step_size', None)
         if opts:
             raise NotImplementedError(f'stribor_amd: solver options {sorted(opts)} are not implemented (step_size only)')
         return name, (None if step is None else float(step))
 
+    def _adaptive_options(self):
+        """(first_step | None: automatic, max_num_steps) of an adaptive solve; any other option raises."""
+        opts = dict((self.solver_options if self.training else self.test_solver_options) or {})
+        first, cap = opts.pop('first_step', None), opts.pop('max_num_steps', MAX_NUM_STEPS)
+        if opts:
+            raise NotImplementedError(f'stribor_amd: solver options {sorted(opts)} are not implemented (first_step and max_num_steps only)')
+        if first is not None and not float(first) > 0:
+            raise ValueError(f'first_step must be positive (got {first})')
+        if not 1 <= int(cap) <= _hip.CNF_ADAPTIVE_MAX_STEPS:
+            raise ValueError(f'max_num_steps must be in 1..{_hip.CNF_ADAPTIVE_MAX_STEPS} (got {cap})')
+        return (None if first is None else float(first)), int(cap)
+
     def _grid(self, reverse: bool):
         name, step = self._solver()
+        if name in ADAPTIVE_SOLVERS:
+            raise ValueError(f'stribor_amd: solver {name!r} has no fixed grid')
         t0, t1 = (self.T, 0.0) if reverse else (0.0, self.T)
         return Grid(name, step, fixed_grid(t0, t1, step))
 
@@ -435,6 +497,14 @@ class ContinuousTransform(Transform):
         (DESIGN.md "CNF": dim <= 32, 1 + dim + latent <= 64, hidden layers of <= 32 units)."""
         plan = self._kernel_net(latent_dim, False, device)
         if plan is None or _hip.lib().sx_cnf_train_lds_bytes(plan[0], 1) == 0 or _hip.lib().sx_cnf_train_lds_bytes(plan[0], 0) == 0:
+            return None
+        return plan
+
+    def _adaptive_kernel_net(self, latent_dim: int, want_trace: bool, device):
+        """(sx_cnf_net, keep-alive list) for sx_cnf_adaptive_flow, or None outside its coverage (dim <= 32, 1 + dim + latent <= 128,
+        hidden layers of <= 64 units)."""
+        plan = self._kernel_net(latent_dim, want_trace, device)
+        if plan is None or _hip.lib().sx_cnf_adaptive_lds_bytes(plan[0]) == 0:
             return None
         return plan
 
@@ -669,6 +739,9 @@ class ContinuousTransform(Transform):
 
     def _composed_reference(self, x, latent=None, mask=None, reverse: bool = False):
         """The composition path without a graph (tests and tools/bench_cnf.py compare the kernel with it)."""
+        if self._solver_name() in ADAPTIVE_SOLVERS:
+            with torch.no_grad():
+                return self._solve_composed_adaptive(x.to(torch.float32), latent, mask, reverse, False)[:2]
         name, step, grid = self._grid(reverse)
         with torch.no_grad():
             return self._solve_composed(x.to(torch.float32), latent, mask, name, grid, False)
@@ -696,11 +769,21 @@ class ContinuousTransform(Transform):
 
     def _choose(self, shape, latent_dim: int, masked: bool, graph: bool, want_ldj: bool, device):
         """What runs a call on x of `shape` -> (route, plan, trace).  route: 'train' (the Hutchinson pair, asked first: it also serves
-        calls that want a graph), a tier's entry point (no graph), or 'composed' (plan None; every masked call).  trace: does the kernel
+        calls that want a graph), a tier's entry point (no graph), or 'composed' (plan None; every masked call).  Under an adaptive
+        solver: 'sx_cnf_adaptive_flow' where a fixed one would get 'sx_cnf_flow' and the adaptive planner covers the net, else 'composed'
+        -- sets, masks, calls that want a graph, training mode and the other five tiers' nets are all composed for now.  trace: does the kernel
         accumulate the log-det.  Host code only: `device` may be the CPU."""
         func = self.odefunc
         trace = want_ldj and func.divergence != 'none'
         if masked:
+            return 'composed', None, trace
+        if self._solver_name() in ADAPTIVE_SOLVERS:
+            # the dense tier's setting and no graph, or composed; the kernel integrates the trace whenever there is one (it is part of
+            # the error norm), whether or not the caller takes the log-det
+            if not graph and self._TIERS[0].applies(func, len(shape)):
+                plan = self._adaptive_kernel_net(latent_dim, func.divergence != 'none', device)
+                if plan is not None:
+                    return 'sx_cnf_adaptive_flow', plan, trace
             return 'composed', None, trace
         if func.divergence == 'approximate' and self.training and not func.set_data:
             plan = self._train_kernel_net(latent_dim, device)
@@ -715,6 +798,8 @@ class ContinuousTransform(Transform):
 
     def _solve(self, x, latent, mask, reverse: bool, want_ldj: bool):
         _hip.require_device(x, 'x')
+        if self._solver_name() in ADAPTIVE_SOLVERS:
+            return self._solve_adaptive(x, latent, mask, reverse, want_ldj)
         grid = self._grid(reverse)
         out_dtype = x.dtype
         x = x.to(torch.float32)
@@ -748,6 +833,146 @@ class ContinuousTransform(Transform):
         self._last_path = 'composed' if route == 'composed' else 'kernel'
         self.odefunc._num_evals.fill_((len(grid.points) - 1) * STAGES[grid.name])
         return (y.to(out_dtype) if out_dtype == torch.bfloat16 else y), ldj
+
+    # ---- the per-sample adaptive solver ('dopri5_per_sample', DESIGN.md "CNF") ---------------------------------------------------
+    def _solve_adaptive(self, x, latent, mask, reverse: bool, want_ldj: bool):
+        first_step, max_steps = self._adaptive_options()
+        out_dtype = x.dtype
+        x = x.to(torch.float32)
+        latent_dim = 0 if latent is None else latent.shape[-1]
+        if latent is not None:
+            latent = latent.to(device=x.device, dtype=torch.float32).expand(*x.shape[:-1], latent_dim)
+        graph = graph_wanted(self, x, latent)
+        route, plan, trace = self._choose(x.shape, latent_dim, mask is not None, graph, want_ldj, x.device)
+        if route == 'composed':
+            with torch.set_grad_enabled(graph):
+                y, ldj, stats = self._solve_composed_adaptive(x, latent, mask, reverse, graph)
+        else:
+            x2, lead = flatten_rows(x)
+            lat2 = None if latent is None else flatten_rows(latent)[0]
+            d, keep = plan
+            n = x2.shape[0]
+            want_trace = self.odefunc.divergence != 'none'
+            t0, t1 = (self.T, 0.0) if reverse else (0.0, self.T)
+            with torch.no_grad():
+                y2 = torch.empty_like(x2)
+                l2 = torch.empty(n, dtype=torch.float32, device=x.device) if want_trace else None
+                stats = torch.empty(n, 3, dtype=torch.int32, device=x.device)
+                if n:
+                    _hip.call(route, x2, ctypes.byref(d), x2.data_ptr(), _hip.ptr(lat2), y2.data_ptr(), _hip.ptr(l2), stats.data_ptr(), n,
+                              float(t0), float(t1), float(self.rtol), float(self.atol), float(first_step or 0.0), max_steps, int(want_trace))
+            del keep
+            if not want_ldj:
+                l2 = None
+            elif l2 is None:                                            # (divergence 'none')
+                l2 = torch.zeros(n, dtype=torch.float32, device=x.device)
+            y, ldj, stats = y2.reshape(*lead, self.dim), (None if l2 is None else l2.reshape(*lead, 1)), stats.reshape(*lead, 3)
+        self._last_path = 'composed' if route == 'composed' else 'kernel'
+        self.last_solver_stats = stats
+        # evaluations of the slowest sample, left on the device: reading it (_num_evals) synchronises, the solve does not
+        with torch.no_grad():
+            steps = stats[..., :2].sum(-1).max() if stats.numel() else torch.zeros((), dtype=torch.int32, device=x.device)
+            self.odefunc._num_evals.copy_(steps * 6 + (1 if first_step is not None else 2))
+        return (y.to(out_dtype) if out_dtype == torch.bfloat16 else y), ldj
+
+    def _solve_composed_adaptive(self, x, latent, mask, reverse: bool, keep_graph: bool):
+        """The controller of sx_cnf_adaptive_flow as vectorised torch ops over the module, one step size per sample, on any leading
+        shape, mask and net whose time argument may be a tensor (every DiffeqConcat) -> (y, log-det [..., 1], stats [samples, 3]).  A
+        sample is a row, or under `set_data` a set.  Accepting is a `torch.where`; with `keep_graph` the step sizes and the accept
+        decisions are constants and the graph runs through the accepted arithmetic (discretise-then-optimise with frozen steps)."""
+        func = self.odefunc
+        if func.divergence == 'exact':
+            raise NotImplementedError("stribor_amd: the exact-trace nets take one time for the whole batch; 'dopri5_per_sample' needs one per sample")
+        func.before_odeint()
+        first_step, max_steps = self._adaptive_options()
+        rtol, atol = float(self.rtol), float(self.atol)
+        t0, t1 = (self.T, 0.0) if reverse else (0.0, self.T)
+        sgn = -1.0 if t1 < t0 else 1.0
+        T = float(abs(np.float32(t1) - np.float32(t0)))
+        nsd = 2 if self.set_data and x.dim() >= 2 else 1                 # trailing axes of one sample
+        lead = x.shape[:-nsd]
+        want = func.divergence != 'none'
+        tail = (() if latent is None else (latent,)) + (() if mask is None else (mask,))
+        col = lambda v: v.reshape(*lead, *([1] * nsd))                  # a per-sample scalar against x ...
+        row = lambda v: v.reshape(*lead, *([1] * (nsd - 1)))            # ... and against the trace integral a [..., (N)]
+        rms = lambda v: v.reshape(*lead, -1).pow(2).mean(-1).sqrt()
+        norm = lambda vx, va: torch.maximum(rms(vx), rms(va)) if want else rms(vx)
+        tab = DOPRI5
+        A = [[_r32(v) for v in r] for r in tab.a]
+        C, E = [_r32(v) for v in tab.c], [_r32(v) for v in tab.e]
+
+        def f(s, xs):                                                    # sgn f and sgn tr df/dx at t0 + sgn s
+            out = func(col(s) * sgn + t0, (xs, torch.zeros_like(xs)) + tail)
+            return out[0] * sgn, -out[1].sum(-1) * sgn
+
+        def weighted(w, ks):                                            # sum_j w_j k_j, left to right, zero weights left out
+            acc = None
+            for wj, kj in zip(w, ks):
+                if wj != 0.0:
+                    acc = kj * wj if acc is None else acc + kj * wj
+            return acc
+
+        zeros = lambda dtype: torch.zeros(lead, dtype=dtype, device=x.device)
+        y, a, s = x, torch.zeros(x.shape[:-1], dtype=torch.float32, device=x.device), zeros(torch.float32)
+        k1, q1 = f(s, y)
+        with torch.no_grad():
+            if first_step is not None:
+                dt = torch.full(lead, first_step, dtype=torch.float32, device=x.device)
+            else:
+                scale = atol + rtol * y.abs()
+                d0, d1 = rms(y / scale), norm(k1 / scale, q1 / atol)
+                h0 = torch.where((d0 < 1e-5) | (d1 < 1e-5), torch.full_like(d0, 1e-6), 0.01 * d0 / d1)
+                kp, qp = f(h0, y + col(h0) * k1)
+                d2 = norm((kp - k1) / scale, (qp - q1) / atol) / h0
+                dm = torch.where((d1 > d2) | (d1 != d1), d1, d2)
+                h1 = torch.where((d1 <= 1e-15) & (d2 <= 1e-15), torch.clamp(1e-3 * h0, min=1e-6), (0.01 / dm).pow(0.2))
+                dt = torch.where((100.0 * h0 < h1) | (h0 != h0), 100.0 * h0, h1)
+            done = zeros(torch.bool) | (not T > 0.0)
+        n_att, n_acc, n_rej, status = (zeros(torch.int32) for _ in range(4))
+        while True:
+            with torch.no_grad():
+                rem = T - s
+                last = dt >= rem
+                h = torch.where(last, rem, dt)
+                cap = ~done & (n_att >= max_steps)
+                status, done = torch.where(cap, 1, status), done | cap
+                under = ~done & (s + h == s)
+                status, done = torch.where(under, 2, status), done | under
+                if bool(done.all()):
+                    break
+                act = ~done
+                h = torch.where(act, h, torch.zeros_like(h))
+                n_att = n_att + act
+                hx, ha = col(h), row(h)
+            K, Q = [k1], [q1]
+            for st in range(1, 7):
+                xs = y + hx * weighted(A[st], K)
+                k, q = f(s + C[st] * h, xs)
+                K.append(k)
+                Q.append(q)
+            a1 = a + ha * weighted(A[6], Q)                      # (xs is the step: a7 = b)
+            with torch.no_grad():
+                err_x, err_a = hx * weighted(E, K), ha * weighted(E, Q)
+                tol_x = atol + rtol * torch.maximum(y.abs(), xs.abs())
+                tol_a = atol + rtol * torch.maximum(a.abs(), a1.abs())
+                ratio = norm(err_x / tol_x, err_a / tol_a)
+                finite = torch.isfinite(ratio)
+                accept = act & finite & (ratio <= 1.0)
+                floor = torch.where(ratio < 1.0, 1.0, 0.2).to(ratio)
+                factor = torch.where(ratio == 0.0, torch.full_like(ratio, 10.0), torch.clamp(torch.maximum(0.9 * ratio.pow(-0.2), floor), max=10.0))
+                s = torch.where(accept, torch.where(last, torch.full_like(s, T), s + h), s)
+                n_acc, n_rej = n_acc + accept, n_rej + (act & ~accept)
+                bad = act & ~finite
+                status, done = torch.where(bad, 2, status), done | bad | (accept & last)
+                dt = torch.where(act, h * factor, dt)
+            y, a = torch.where(col(accept), xs, y), torch.where(row(accept), a1, a)
+            k1, q1 = torch.where(col(accept), K[6], k1), torch.where(row(accept), Q[6], q1)
+            if not keep_graph:
+                y, a, k1, q1 = y.detach(), a.detach(), k1.detach(), q1.detach()
+        failed = status != 0
+        nan = torch.full((), float('nan'), dtype=torch.float32, device=x.device)
+        y, a = torch.where(col(failed), nan, y), torch.where(row(failed), nan, a)
+        return y, a.unsqueeze(-1), torch.stack([n_acc, n_rej, status], -1).to(torch.int32)
 
     # ---- reference method set ---------------------------------------------------------------------------------------------------
     def forward_and_log_det_jacobian(self, x, latent=None, mask=None, *, reverse=False, **kwargs):

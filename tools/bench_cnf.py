@@ -46,7 +46,13 @@ and dim 32 / [64, 64] train on the composition path and are timed on it alone), 
 composition path on the same build and rows (forced by hiding the kernel plan), and the checkpoint bytes n_steps x rows x dim x 4.
 --train-only prints these lines alone.
 
-    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only] [--exact-attention-only] [--train-only] [--train-rows 16384]
+The adaptive lines: solver='dopri5_per_sample' at the default tolerances (atol 1e-5, rtol 1e-3, automatic first step) on
+sx_cnf_adaptive_flow at dim 2 / [64] and dim 32 / [64, 64] (the widest two-layer net that kernel covers), --rows rows, the log_prob
+direction: call time (device events around whole calls), the composed adaptive path on the same build timed at --fallback-rows rows and
+scaled, the mean and the largest number of attempts per row (last_solver_stats), and sx_cnf_flow's rk4 x --steps on the same net and
+rows for scale.  --adaptive-only prints these lines alone.
+
+    python tools/bench_cnf.py [--rows 262144] [--steps 16] [--json out.json] [--attention-only] [--exact-attention-only] [--train-only] [--train-rows 16384] [--adaptive-only]
 """
 import argparse
 import json
@@ -210,11 +216,12 @@ def main():
     ap.add_argument('--attention-only', action='store_true', help='print the attention line alone')
     ap.add_argument('--exact-attention-only', action='store_true', help='print the exact-trace attention line alone')
     ap.add_argument('--train-only', action='store_true', help='print the training lines alone')
+    ap.add_argument('--adaptive-only', action='store_true', help="print the 'dopri5_per_sample' lines alone")
     ap.add_argument('--train-rows', type=int, default=1 << 14, help='rows of the training lines (the composition path finishes in seconds)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_cnf needs a GPU'
     results = {}
-    only = a.attention_only or a.exact_attention_only or a.train_only
+    only = a.attention_only or a.exact_attention_only or a.train_only or a.adaptive_only
     ok = True
     if not only:
         earlier_lines(a, results)
@@ -224,6 +231,8 @@ def main():
         ok = exact_attention_line(a, results)
     if a.train_only or not only:
         training_lines(a, results)
+    if a.adaptive_only or not only:
+        adaptive_lines(a, results)
     results['config'] = {'rows': a.rows, 'steps': a.steps, 'solver': 'rk4', 'fallback_rows': a.fallback_rows, 'sets': a.sets,
                          'set_fallback_sets': a.set_fallback_sets, 'train_rows': a.train_rows,
                          'build_id': st._hip.build_id()}
@@ -232,6 +241,37 @@ def main():
             json.dump(results, fh, indent=1)
     if not ok:
         sys.exit('bench_cnf: the exact-attention line misses one of its two conditions (within_bound, kernel_faster_at_small)')
+
+
+def adaptive_lines(a, results):
+    for dim, hidden in ((2, [64]), (32, [64, 64])):
+        torch.manual_seed(0)
+        net = st.net.DiffeqMLP(dim + 1, hidden, dim)
+        f = st.ContinuousTransform(dim, net=net, divergence='compute', solver='dopri5_per_sample').eval().to('cuda')
+        fixed = st.ContinuousTransform(dim, net=net, divergence='compute', solver='rk4', solver_options={'step_size': 1.0 / a.steps}).eval().to('cuda')
+        y = torch.randn(a.rows, dim, device='cuda')
+        ys = y[:a.fallback_rows]
+        with torch.no_grad():
+            ms = timed(lambda: f.inverse_and_log_det_jacobian(y), a.reps)
+            assert f._last_path == 'kernel'
+            stats = f.last_solver_stats
+            attempts = stats[:, :2].sum(-1).float()
+            failed = int((stats[:, 2] != 0).sum().item())
+            num_evals = f._num_evals()                 # (read now: the composed reference below resets the counter)
+            ms_rk4 = timed(lambda: fixed.inverse_and_log_det_jacobian(y), a.reps)
+            assert fixed._last_path == 'kernel'
+            fb = timed(lambda: f._composed_reference(ys, reverse=True), 1, warm=1) * (a.rows / ys.shape[0])
+            xk, lk = f.inverse_and_log_det_jacobian(ys)
+            xc, lc = f._composed_reference(ys, reverse=True)
+        r = results[f'adaptive_dim{dim}_h{"x".join(map(str, hidden))}'] = {
+            'solve_ldj_ms': ms, 'composed_ms_scaled': fb, 'composed_over_kernel': fb / ms, 'rows_per_s': a.rows / ms * 1e3,
+            'attempts_mean': attempts.mean().item(), 'attempts_max': int(attempts.max().item()), 'rejected': int(stats[:, 1].sum().item()),
+            'failed_rows': failed, 'num_evals': num_evals, 'rk4_ms': ms_rk4, 'rk4_steps': a.steps, 'atol': f.atol, 'rtol': f.rtol,
+            'max_abs_x': (xk - xc).abs().max().item(), 'max_abs_ldj': (lk - lc).abs().max().item()}
+        print(f'adaptive dim {dim} {hidden} N={a.rows} dopri5_per_sample atol {f.atol:g} rtol {f.rtol:g}: solve + log-det {ms:.2f} ms per call '
+              f'({r["rows_per_s"]:.3g} rows/s), attempts per row mean {r["attempts_mean"]:.2f} max {r["attempts_max"]} ({r["rejected"]} rejected, '
+              f'{failed} failed rows); composed adaptive path {fb:.0f} ms (timed at {ys.shape[0]} rows, scaled) = {r["composed_over_kernel"]:.0f} x; '
+              f'sx_cnf_flow rk4 x {a.steps} on the same net {ms_rk4:.2f} ms; kernel vs composed max abs x {r["max_abs_x"]:.2e} ldj {r["max_abs_ldj"]:.2e}')
 
 
 def earlier_lines(a, results):
