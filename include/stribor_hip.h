@@ -301,6 +301,29 @@ int sx_pointwise(const void *x, void *y, float *ldj, float *ldiag, int64_t n_row
 int sx_pointwise_bwd(const float *x, const float *gy, const float *gldj, const float *gldiag, float *gx, int64_t n_rows, int32_t dim,
                      int32_t kind, float param, void *stream);
 
+/* Time-dependent element-wise flows (stribor/flows/activations.py:125-196), one time t[n] per row; arguments as sx_pointwise plus t:
+ *   SX_PWT_TANH_FLOW / _INV   ContinuousTanh, y = asinh(exp(+-tau) sinh x) with tau = t, or log1p(t) when param != 0 (log_time); stated in
+ *                             the log domain (finite wherever the result is).  ldiag / ldj: the kind's own log-derivative log dy/dx, which
+ *                             for _INV is what Transform.inverse_and_log_det_jacobian returns (flow.py:42-47).
+ *   SX_PWT_MIX_TANH / _SIGMOID / _RELU   ContinuousActivation, y = x (1 - w) + act(x) w with w = tanh(param t), param = the temperature;
+ *                             no log-derivative (the reference raises NotImplementedError): ldj and ldiag must be NULL. */
+#define SX_PWT_TANH_FLOW 1
+#define SX_PWT_TANH_FLOW_INV 2
+#define SX_PWT_MIX_TANH 3
+#define SX_PWT_MIX_SIGMOID 4
+#define SX_PWT_MIX_RELU 5
+int sx_pointwise_time(const void *x, const float *t, void *y, float *ldj, float *ldiag, int64_t n_rows, int32_t dim, int32_t dtype,
+                      int32_t kind, float param, int32_t ldj_accumulate, void *stream);
+
+/* Backward of sx_pointwise_time (training): x, gy, gx [n_rows, dim] fp32 (gy nullable), gldj [n_rows] / gldiag [n_rows, dim] nullable
+ * (tanh-flow kinds only).  gt (nullable, [n_rows]): dL/dt[n], a row sum.  gparam (nullable, mix kinds, [1]): dL/d(temperature), a sum
+ * over every element: one fp64 partial per wave in a fixed order into `partial` (SX_PWT_PARTIALS doubles, 8-byte aligned), then one
+ * ordered reduce -- no atomics, so two calls on the same inputs return the same bits. */
+#define SX_PWT_PARTIALS 8192
+int sx_pointwise_time_bwd(const float *x, const float *t, const float *gy, const float *gldj, const float *gldiag, float *gx,
+                          float *gt, float *gparam, double *partial, int64_t n_rows, int32_t dim, int32_t kind, float param,
+                          void *stream);
+
 /* out[0] = max(out[0], max |a[0..na)|, max |b[0..nb)|) (b nullable; fp32; `out` holds a non-negative value, e.g. 0, on entry): the
  * magnitude of a backward pass's incoming adjoints (dL/dy [n_rows, dim] and dL/dlog-det [n_rows]), from which sx_rqs_slab_bwd
  * derives its power-of-two normalisation; one launch over every element. */
@@ -482,6 +505,11 @@ int sx_pack_linear_batch(const sx_pack_job *jobs, int32_t n_jobs, int32_t max_fl
                                         /* (in spline programs SX_STEP_RQS_HIDDEN with pad_ == 1 is the LAST hidden layer, fed by these) */
 #define SX_STEP_COUPLING_AFFINE_DEEP 15 /* the coupling's last hidden layer (from the kept hidden state), output layer and affine
                                            map: blob = pack_linear(W_L, h_tiles x h_tiles) ++ pack_linear(W_out, 2*tt x h_tiles) */
+#define SX_STEP_POINTWISE_TIME      25  /* time-dependent point-wise flow on the data tiles (ContinuousTanh / ContinuousActivation, activations.py:125-196)
+                                         * inside a program of SX_STEP_COUPLING_TIME steps: act = SX_PWT_* kind (the direction is the kind),
+                                         * ldj_const = param (log_time flag / temperature), pad_ = which time the step reads (0 row_t, 1 side),
+                                         * blob = live-slot mask [tiles][2][16] as SX_STEP_POINTWISE.  Values only: nothing goes to the
+                                         * log-det accumulator (the mix kinds have none), so such a program is run without ldj_out. */
 
 #define SX_MAX_STEPS 128
 

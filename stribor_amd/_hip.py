@@ -44,6 +44,11 @@ STEP_COUPLING_AFFINE_HC = 21
 STEP_WIDE_HIDDEN = 22
 STEP_WIDE_AFFINE_TILE = 23
 STEP_MLP_INPUT = 24
+STEP_POINTWISE_TIME = 25
+
+# time-dependent point-wise flows (include/stribor_hip.h: sx_pointwise_time)
+PWT_TANH_FLOW, PWT_TANH_FLOW_INV, PWT_MIX_TANH, PWT_MIX_SIGMOID, PWT_MIX_RELU = range(1, 6)
+PWT_PARTIALS = 8192
 
 WGRAD_ROW_MAJOR, WGRAD_ROW_GROUPS, WGRAD_ROW_GROUPS_F16X3 = 0, 1, 3
 
@@ -54,6 +59,7 @@ ACT_CODES = {'Identity': 0, 'Tanh': 1, 'ReLU': 2, 'Sigmoid': 3, 'ELU': 4, 'Softp
 # every symbol include/stribor_hip.h declares (tests check that the library exports all of them)
 EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id', 'sx_absmax2', 'sx_permute', 'sx_affine_coupling', 'sx_rqs_coupling',
            'sx_cubic_coupling', 'sx_pointwise', 'sx_rqs_inverse_bwd', 'sx_rqs_forward_bwd', 'sx_affine_coupling_bwd', 'sx_time_affine_coupling', 'sx_cubic_inverse_bwd', 'sx_cubic_forward_bwd', 'sx_pointwise_bwd',
+           'sx_pointwise_time', 'sx_pointwise_time_bwd',
            'sx_unit_normal_logprob', 'sx_sum_f64', 'sx_packed_linear_floats', 'sx_pack_linear', 'sx_pack_linear_bound', 'sx_pack_linear_batch', 'sx_flow_run', 'sx_flow_run2', 'sx_flow_run3', 'sx_flow_redo_words',
            'sx_flow_launch_info', 'sx_wgrad', 'sx_wgrad_layer', 'sx_colsum', 'sx_tri_inverse_f64',
            'sx_wgrad_scratch_floats', 'sx_wgrad_layer_scratch_floats', 'sx_flow_bwd_max_steps', 'sx_flow_bwd_partials',
@@ -246,6 +252,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cubic_forward_bwd.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, f32, f32, i64, i32, f32, vp]
     lib.sx_pointwise_bwd.restype = i32
     lib.sx_pointwise_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, f32, vp]
+    lib.sx_pointwise_time.restype = i32
+    lib.sx_pointwise_time.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, i32, vp]
+    lib.sx_pointwise_time_bwd.restype = i32
+    lib.sx_pointwise_time_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, vp]
     lib.sx_pointwise.restype = i32
     lib.sx_pointwise.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, f32, i32, vp]
     lib.sx_absmax2.restype = i32

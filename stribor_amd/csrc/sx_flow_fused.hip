@@ -24,7 +24,7 @@ static int validate_and_convert(const sx_program *p, dprog *d, int *buf_floats, 
     int mx = 256;
     bool lin = false, rqs = false, aff = false, bwd = false, deep = false, cub = false, quadr = false;
     int n_bwd128 = 0;
-    bool pw = false, timed = false, wide_rq = false, hc = false;
+    bool pw = false, timed = false, wide_rq = false, hc = false, timed_pw = false;
     int n_hc8 = 0;
     *mlp_mode = 0;
     for (int i = 0; i < p->n_steps; ++i) {
@@ -160,6 +160,10 @@ static int validate_and_convert(const sx_program *p, dprog *d, int *buf_floats, 
             case SX_STEP_POINTWISE:
                 SX_REQUIRE(s.act >= SX_PW_SIGMOID && s.act <= SX_PW_LEAKY_RELU_INV, "sx_flow_run: step %d: point-wise kind %d (1..6)", i, s.act);
                 need = 32 * p->tiles + 1; pw = true; break;
+            case SX_STEP_POINTWISE_TIME:
+                SX_REQUIRE(s.act >= SX_PWT_TANH_FLOW && s.act <= SX_PWT_MIX_RELU, "sx_flow_run: step %d: time point-wise kind %d (1..5)", i, s.act);
+                SX_REQUIRE(s.pad_ == 0 || s.pad_ == 1, "sx_flow_run: step %d: time slot %d (0 row_t, 1 side)", i, s.pad_);
+                need = 32 * p->tiles; timed_pw = true; break;
             case SX_STEP_RQS_HIDDEN: {
                 const int T = p->tiles;
                 const bool low = T >= 2 && s.c0 == 0 && s.ct == T / 2;
@@ -215,6 +219,10 @@ static int validate_and_convert(const sx_program *p, dprog *d, int *buf_floats, 
     if (bwd) *mlp_mode = 4;
     SX_REQUIRE(!(timed && (rqs || lin || aff || bwd || deep || pw || *mlp_mode == 1)), "sx_flow_run: time couplings form programs of their own");
     if (timed) *mlp_mode = 15;
+    // MODE 21: time couplings and time-dependent point-wise flows (NeuralFlow), or the latter alone
+    SX_REQUIRE(!(timed_pw && (rqs || lin || aff || bwd || deep || pw || hc || *mlp_mode == 1 || p->tiles > 4)),
+               "sx_flow_run: time-dependent point-wise steps share a program with time couplings only (up to four tiles)");
+    if (timed_pw) *mlp_mode = 21;
     SX_REQUIRE(p->tiles != 8 || (p->x_tiles == 4 && bwd && n_bwd128 == p->n_steps) || (p->x_tiles == 8 && hc && n_hc8 == p->n_steps),
                "sx_flow_run: 8 state tiles carry backward steps (kinds 16 - 18; 4 data + 4 adjoint tiles) or the couplings of kinds 22 / 23 and element-wise affines (8 data tiles) only");
     SX_REQUIRE(!(deep && (lin || bwd || *mlp_mode == 1)), "sx_flow_run: deep-conditioner steps only mix with couplings");
@@ -315,6 +323,12 @@ extern "C" int sx_flow_run3(const sx_program *prog_host, const float *blobs, con
     if ((mlp_out != nullptr || side != nullptr) && (mlp_mode == 3 || mlp_mode == 12)) mlp_mode = mlp_mode == 3 ? 18 : 19;
     SX_REQUIRE(mlp_out == nullptr || mlp_mode == 1 || mlp_mode == 18 || mlp_mode == 19,
                "sx_flow_run: mlp_out is the output of MLP programs and the tanh-h side output of pure spline programs with one hidden layer (kernel mode %d has neither)", mlp_mode);
+    SX_REQUIRE(mlp_mode != 21 || (ldj_out == nullptr && logp_out == nullptr && sum_out == nullptr),
+               "sx_flow_run: programs with time-dependent point-wise steps return values only");
+    if (mlp_mode == 21)
+        for (int i = 0; i < prog_host->n_steps; ++i)
+            if (prog_host->steps[i].kind == SX_STEP_POINTWISE_TIME)
+                SX_REQUIRE(prog_host->steps[i].pad_ ? side != nullptr : row_t != nullptr, "sx_flow_run: step %d reads a time vector that was not given", i);
     SX_REQUIRE(x != nullptr && n_rows >= 0, "sx_flow_run: bad x / n_rows");
     SX_REQUIRE(blobs != nullptr || prog_host->n_steps == 0, "sx_flow_run: null blobs");
     SX_REQUIRE(dtype == SX_F32 || dtype == SX_BF16, "sx_flow_run: bad dtype");
@@ -382,8 +396,12 @@ extern "C" int sx_flow_run3(const sx_program *prog_host, const float *blobs, con
         bool found = false;
 #define SX_GOF(TT, HH, F) (prec == SX_GEMM_F16X3 ? sx_flow_launch_f16x3_t##TT##h##HH##_f##F(a) : sx_flow_launch_f32x_t##TT##h##HH##_f##F(a))
 #define SX_GO(TT, HH) if (!found && T == TT && H == HH) { found = true; rc2 = fam == 0 ? SX_GOF(TT, HH, 0) : fam == 1 ? SX_GOF(TT, HH, 1) : SX_GOF(TT, HH, 2); }
+        // (family 3, MODE 21: up to four tiles -- validate_and_convert has refused the rest)
+#define SX_GO3(TT, HH) if (!found && fam == 3 && T == TT && H == HH) { found = true; rc2 = SX_GOF(TT, HH, 3); }
+        SX_GO3(1, 1); SX_GO3(1, 2); SX_GO3(1, 4); SX_GO3(2, 1); SX_GO3(2, 2); SX_GO3(2, 4); SX_GO3(4, 1); SX_GO3(4, 2); SX_GO3(4, 4);
         SX_GO(1, 1); SX_GO(1, 2); SX_GO(1, 4); SX_GO(2, 1); SX_GO(2, 2); SX_GO(2, 4); SX_GO(4, 1); SX_GO(4, 2); SX_GO(4, 4);
         SX_GO(8, 1); SX_GO(8, 2); SX_GO(8, 4);
+#undef SX_GO3
 #undef SX_GO
 #undef SX_GOF
         if (!found) { sx_set_error("sx_flow_run: unsupported tile configuration"); return SX_E_UNSUPPORTED; }

@@ -1,5 +1,5 @@
 // One (tiles, hidden-tiles) instantiation of the fused flow kernel in one GEMM arithmetic and one kernel-MODE FAMILY; compiled once
-// per pair, precision and family (-DSX_TX=.. -DSX_HT=.. [-DSX_F16X3] -DSX_FAMILY=0|1|2: sx_flow_types.h) so the seventy-two objects
+// per pair, precision and family (-DSX_TX=.. -DSX_HT=.. [-DSX_F16X3] -DSX_FAMILY=0|1|2|3: sx_flow_types.h) so the ninety objects
 // build in parallel and an edit of the spline (or backward) header rebuilds that family's objects only.  Without -DSX_FAMILY
 // (tools/rescheck.sh, -DSX_ONLY_MODE studies) the object holds every MODE and keeps the family-less name.
 #ifdef SX_FAMILY

@@ -31,6 +31,7 @@
 #include "sx_flow_types.h"
 #include "sx_cubic_core.h"
 #include "sx_pointwise_core.h"
+#include "sx_pointwise_time_core.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1329,6 +1330,42 @@ __device__ __forceinline__ void pointwise_step(tile<NS> (&xs)[TX], const wptr w,
     }
 }
 
+// Time-dependent point-wise flows inside a program of time couplings (ContinuousTanh / ContinuousActivation, activations.py:125-196;
+// kernel MODE 21): the arithmetic of the stand-alone kernel (sx_pointwise_time_core.h) on the data tiles; tv = the row's time.  blob =
+// live-slot mask as pointwise_tiles.  Values only (NeuralFlow returns no log-det).
+template <int NS, int TX, int KIND>
+__device__ __forceinline__ void pointwise_time_tiles(tile<NS> (&xs)[TX], const wptr w, const dstep &st, int x_tiles, const float (&tv)[NS]) {
+    float rp[NS];
+#pragma unroll
+    for (int n = 0; n < NS; ++n) rp[n] = pwt_row(KIND, st.ldj_const, tv[n]);
+#pragma unroll
+    for (int t = 0; t < TX; ++t) {
+        if (t < x_tiles) {
+            const f32x16 live = load_cfrag1(w.cb, t * 32);
+#pragma unroll
+            for (int n = 0; n < NS; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float xv = xs[t].v[n][r];
+                    float out;
+                    if constexpr (KIND == SX_PWT_TANH_FLOW || KIND == SX_PWT_TANH_FLOW_INV) out = pwt_tanh_flow(rp[n], xv).y;
+                    else out = pwt_mix(KIND, rp[n], xv);
+                    xs[t].v[n][r] = live[r] != 0.f ? out : xv;
+                }
+        }
+    }
+}
+template <int NS, int TX>
+__device__ __forceinline__ void pointwise_time_step(tile<NS> (&xs)[TX], const wptr w, const dstep &st, int x_tiles, const float (&tv)[NS]) {
+    switch (st.act) {
+        case SX_PWT_TANH_FLOW: pointwise_time_tiles<NS, TX, SX_PWT_TANH_FLOW>(xs, w, st, x_tiles, tv); break;
+        case SX_PWT_TANH_FLOW_INV: pointwise_time_tiles<NS, TX, SX_PWT_TANH_FLOW_INV>(xs, w, st, x_tiles, tv); break;
+        case SX_PWT_MIX_TANH: pointwise_time_tiles<NS, TX, SX_PWT_MIX_TANH>(xs, w, st, x_tiles, tv); break;
+        case SX_PWT_MIX_SIGMOID: pointwise_time_tiles<NS, TX, SX_PWT_MIX_SIGMOID>(xs, w, st, x_tiles, tv); break;
+        default: pointwise_time_tiles<NS, TX, SX_PWT_MIX_RELU>(xs, w, st, x_tiles, tv); break;
+    }
+}
+
 #include "sx_flow_spline.h"      // spline-coupling phases (rqs_* / cub_*)
 #include "sx_flow_bwd.h"         // training backward steps
 
@@ -1610,7 +1647,7 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                     for (int r = 0; r < 16; ++r) {
                         const int c = 32 * (t - x_tiles) + sx_kmap(r, h);
                         float v = (k.latent != nullptr && c < prog.latent_dim) ? k.latent[lrow[n] * prog.latent_dim + c] : 0.f;
-                        if constexpr (MODE == 15) {      // the two slots behind the latent columns: t and t0 (coupling.py:155-156)
+                        if constexpr (MODE == 15 || MODE == 21) {      // the two slots behind the latent columns: t and t0 (coupling.py:155-156)
                             if (c == prog.latent_dim && k.row_t != nullptr) v = k.row_t[lrow[n]];
                             if (c == prog.latent_dim + 1 && k.side != nullptr) v = k.side[lrow[n]];
                         }
@@ -1780,6 +1817,25 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                     else if constexpr (TX >= 2) {
                         if (st.tt == TX / 2) coupling_time_dispatch<NS, TX, HT, TX / 2>(xs, w, st, ldj, rg, tv);
                         else if constexpr (TX >= 4) { if (st.tt == TX / 4) coupling_time_dispatch<NS, TX, HT, TX / 4>(xs, w, st, ldj, rg, tv); }
+                    }
+                }
+            } else if constexpr (MODE == 21) {
+                // MODE 15's programs with time-dependent point-wise flows between the couplings (NeuralFlow over ContinuousAffineCoupling,
+                // ContinuousTanh and ContinuousActivation layers): an instance of its own, MODE 15 carries none of this
+                if constexpr (TX <= 4) {
+                    float tv[NS];
+                    if (st.kind == SX_STEP_COUPLING_TIME) {
+#pragma unroll
+                        for (int n = 0; n < NS; ++n) tv[n] = ((st.mask >> 8) & 1u) ? k.side[lrow[n]] : k.row_t[lrow[n]];
+                        if (st.tt == TX) coupling_time_dispatch<NS, TX, HT, TX>(xs, w, st, ldj, rg, tv);
+                        else if constexpr (TX >= 2) {
+                            if (st.tt == TX / 2) coupling_time_dispatch<NS, TX, HT, TX / 2>(xs, w, st, ldj, rg, tv);
+                            else if constexpr (TX >= 4) { if (st.tt == TX / 4) coupling_time_dispatch<NS, TX, HT, TX / 4>(xs, w, st, ldj, rg, tv); }
+                        }
+                    } else if (st.kind == SX_STEP_POINTWISE_TIME) {
+#pragma unroll
+                        for (int n = 0; n < NS; ++n) tv[n] = (st.mask & 1u) ? k.side[lrow[n]] : k.row_t[lrow[n]];
+                        pointwise_time_step<NS, TX>(xs, w, st, x_tiles, tv);
                     }
                 }
             } else if constexpr (MODE == 4 && TX == 8) {
@@ -2234,6 +2290,8 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
                     break;
                 default: break;
             }
+            if constexpr (MODE == 21) { if (st.kind == SX_STEP_COUPLING_TIME) ldj_c += st_cur_const; }          // (SX_STEP_POINTWISE_TIME keeps its parameter there)
+            else
             if (st.kind != SX_STEP_ROW_SCALE_EXP && st.kind != SX_STEP_POINTWISE) ldj_c += st_cur_const;      // (those two keep a parameter there)
             if constexpr (DMA_LATE) {
                 // (buffer cur ^ 1 has been free since this step's barrier; the pieces land while the younger half finishes the step)
@@ -2488,6 +2546,7 @@ static int sx_flow_launch_impl(const sx_flow_args &a) {
     else if (a.mlp_mode == 16) SX_FM(16);
     else if (a.mlp_mode == 17) SX_FM(17);
     else if (a.mlp_mode == 20) { if constexpr (TX >= 2) SX_FM(20); }
+    else if (a.mlp_mode == SX_MODE_TIME_POINTWISE) SX_FM(SX_MODE_TIME_POINTWISE);
     else if (a.mlp_mode == 7) { if constexpr (TX >= 2) SX_FM(7); }
     else if (a.mlp_mode == 8) { if constexpr (TX >= 2) SX_FM(8); }
     else if (a.mlp_mode == 11) {

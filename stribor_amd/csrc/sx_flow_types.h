@@ -52,7 +52,7 @@ struct sx_flow_args {
 // waves per SIMD of the 128-column linear / split-coupling kernels (MODE 7 / 8 on four tiles): one workgroup of 4 x this per CU
 #define SX_M7_WAVES 2
 #define SX_WAVES_FOR(TX, MODE) SX_WAVES_FOR_(TX, SX_MODE_BASE(MODE))
-#define SX_WAVES_FOR_(TX, MODE) ((MODE) == 11 || (MODE) == 14 ? 1 : (MODE) == 20 ? ((TX) >= 4 ? 1 : 2) : ((MODE) == 15 || (MODE) == 16 || (MODE) == 17) ? ((TX) >= 4 ? 1 : 2) : ((MODE) == 10 || (MODE) == 12 || (MODE) == 13) ? ((TX) >= 4 ? 1 : SX_RQS_WAVES) : (MODE) == 9 ? ((TX) >= 4 ? 1 : 2) : (MODE) >= 7 ? ((TX) >= 4 ? SX_M7_WAVES : 2) : (MODE) >= 5 ? ((TX) >= 4 ? 2 : 4) : ((TX) >= 4 ? 1 : ((MODE) == 3 ? SX_RQS_WAVES : ((MODE) == 0 ? 3 : 2))))
+#define SX_WAVES_FOR_(TX, MODE) ((MODE) == 11 || (MODE) == 14 ? 1 : (MODE) == 20 ? ((TX) >= 4 ? 1 : 2) : ((MODE) == 15 || (MODE) == 16 || (MODE) == 17 || (MODE) == 21) ? ((TX) >= 4 ? 1 : 2) : ((MODE) == 10 || (MODE) == 12 || (MODE) == 13) ? ((TX) >= 4 ? 1 : SX_RQS_WAVES) : (MODE) == 9 ? ((TX) >= 4 ? 1 : 2) : (MODE) >= 7 ? ((TX) >= 4 ? SX_M7_WAVES : 2) : (MODE) >= 5 ? ((TX) >= 4 ? 2 : 4) : ((TX) >= 4 ? 1 : ((MODE) == 3 ? SX_RQS_WAVES : ((MODE) == 0 ? 3 : 2))))
 
 // waves per workgroup: the pure split-coupling kernels (MODE 5 / 6) run 8-wave workgroups -- D <= 64 (128 VGPRs): two
 // per CU = 4 waves per SIMD sharing two weight rings; D = 128 (216 VGPRs): one per CU = 2 waves per SIMD on one ring
@@ -65,12 +65,17 @@ struct sx_flow_args {
 //   0  affine / dense / MLP / time-conditioned inference programs (MODE 0, 1, 2, 5 .. 9, 15, 20)
 //   1  spline, cubic-spline and mixed programs (MODE 3, 10, 12, 13, 14, 16 .. 19): the only objects that instantiate sx_flow_spline.h
 //   2  training backward programs (MODE 4, 11): the only objects that instantiate sx_flow_bwd.h
-#define SX_MODE_FAMILY(MODE) ((MODE) == 4 || (MODE) == 11 ? 2 : ((MODE) == 3 || (MODE) == 10 || (MODE) == 12 || (MODE) == 13 || (MODE) == 14 || ((MODE) >= 16 && (MODE) <= 19)) ? 1 : 0)
+//   3  time-conditioned programs that hold SX_STEP_POINTWISE_TIME steps (MODE 21 = MODE 15 + that step; up to four tiles): objects of
+//      their own, so that MODE 15's code object is what it was
+#define SX_MODE_TIME_POINTWISE 21
+#define SX_MODE_FAMILY(MODE) ((MODE) == 21 ? 3 : (MODE) == 4 || (MODE) == 11 ? 2 : ((MODE) == 3 || (MODE) == 10 || (MODE) == 12 || (MODE) == 13 || (MODE) == 14 || ((MODE) >= 16 && (MODE) <= 19)) ? 1 : 0)
 #define SX_DECL_FLOW_F(T, H, F) int sx_flow_launch_f16x3_t##T##h##H##_f##F(const sx_flow_args &a); int sx_flow_launch_f32x_t##T##h##H##_f##F(const sx_flow_args &a);
 #define SX_DECL_FLOW(T, H) SX_DECL_FLOW_F(T, H, 0) SX_DECL_FLOW_F(T, H, 1) SX_DECL_FLOW_F(T, H, 2)
 SX_DECL_FLOW(1, 1) SX_DECL_FLOW(1, 2) SX_DECL_FLOW(1, 4)
 SX_DECL_FLOW(2, 1) SX_DECL_FLOW(2, 2) SX_DECL_FLOW(2, 4)
 SX_DECL_FLOW(4, 1) SX_DECL_FLOW(4, 2) SX_DECL_FLOW(4, 4)
 SX_DECL_FLOW(8, 1) SX_DECL_FLOW(8, 2) SX_DECL_FLOW(8, 4)      // 4 data + 4 adjoint tiles: backward programs of 128-column flows (MODE 4); 8 data tiles: MODE 20
+SX_DECL_FLOW_F(1, 1, 3) SX_DECL_FLOW_F(1, 2, 3) SX_DECL_FLOW_F(1, 4, 3) SX_DECL_FLOW_F(2, 1, 3) SX_DECL_FLOW_F(2, 2, 3) SX_DECL_FLOW_F(2, 4, 3)
+SX_DECL_FLOW_F(4, 1, 3) SX_DECL_FLOW_F(4, 2, 3) SX_DECL_FLOW_F(4, 4, 3)
 #undef SX_DECL_FLOW
 #undef SX_DECL_FLOW_F

@@ -593,6 +593,15 @@ class NormalizingFlow(Transform):
               for f in self.transforms]
         return all(ok)         # (a flow of nothing but Permute / Flip still carries dL/dx: index_select ops + the base density)
 
+    @staticmethod
+    def _time_by_rows(t, lead, device):
+        """The call's `t` as the flattened state's layers see it: a tensor [..., k] broadcast over the leading shape -> [N, k] (k = 1:
+        one time per row; k = dim: per feature), differentiable in t; numbers and 0-dim tensors as they are."""
+        if not torch.is_tensor(t) or t.dim() == 0:
+            return t
+        t = t.to(device)
+        return t.expand(*lead, t.shape[-1]).reshape(-1, t.shape[-1])
+
     def _layerwise_autograd(self, x, latent=None, reverse: bool = True, t=None):
         """The flow layer by layer WITH an autograd graph: each layer's transform (and its backward) is a HIP kernel behind
         an autograd op, conditioners and column shuffles are torch ops on the device.  fp32 state.
@@ -638,6 +647,10 @@ class NormalizingFlow(Transform):
                 total = ldj if total is None else total + ldj
                 continue
             step = f._autograd_inverse if reverse else f._autograd_forward
+            if getattr(f, '_autograd_takes_time', False):                     # time-dependent layers (ContinuousTanh): t by rows
+                cur, ldj = step(cur, lat2, t=self._time_by_rows(t, lead, cur.device))
+                total = ldj if total is None else total + ldj
+                continue
             cur, ldj = step(cur, lat2, dense[id(f)]) if id(f) in dense else step(cur, lat2)
             total = ldj if total is None else total + ldj
         if total is None:
@@ -947,17 +960,21 @@ class NeuralFlow(nn.Module):
 
     def _fused(self, dim: int, latent_dim: int, with_t0: bool, device):
         """The whole flow -- the inverse pass at t0 (when given) and the forward pass at t -- as ONE program of
-        SX_STEP_COUPLING_TIME steps, or None when a transform is not a fusable ContinuousAffineCoupling."""
+        SX_STEP_COUPLING_TIME and SX_STEP_POINTWISE_TIME steps, or None when a transform is neither a fusable
+        ContinuousAffineCoupling, a ContinuousTanh nor a kernel-covered ContinuousActivation (which has no inverse pass)."""
         from .flows.coupling import ContinuousAffineCoupling
+        from .flows.time_pointwise import ContinuousActivation, ContinuousTanh
         cache = self.__dict__.setdefault('_programs', ProgramCache())
         key = (dim, latent_dim, bool(with_t0), str(device))
 
         def build():
             fs = list(self.transforms)
-            if not fs or not all(isinstance(f, ContinuousAffineCoupling) and f._fusable() for f in fs):
+            if not fs or not all((isinstance(f, ContinuousAffineCoupling) and f._fusable()) or
+                                 isinstance(f, (ContinuousTanh, ContinuousActivation)) for f in fs):
                 return None
             try:
-                b = ProgramBuilder(dim, latent_dim, max(f.latent_net.hidden_width for f in fs), time_slots=2 if with_t0 else 1)
+                widths = [f.latent_net.hidden_width for f in fs if isinstance(f, ContinuousAffineCoupling)]
+                b = ProgramBuilder(dim, latent_dim, max(widths, default=32), time_slots=2 if with_t0 else 1)
                 if with_t0:
                     for f in reversed(fs):                                  # flow.py:178-180: x = f.inverse(x, t=t0)
                         if not f._plan_time(b, True, 0.0, 1):
@@ -968,7 +985,9 @@ class NeuralFlow(nn.Module):
                 return b.build(device)
             except NotImplementedError:
                 return None
-        return cache.get(key, build, fingerprint=tuple(map(id, self.transforms)))
+        # (a ContinuousActivation's temperature is baked into its step: an optimizer step or load_state_dict re-plans)
+        guards = [g for f in self.transforms if isinstance(f, Transform) for g in f._plan_guards()]
+        return cache.get(key, build, guards=guards, fingerprint=tuple(map(id, self.transforms)))
 
     def forward(self, x, t, t0=None, **kwargs):
         latent = kwargs.get('latent')
@@ -977,7 +996,10 @@ class NeuralFlow(nn.Module):
             x2, lead = flatten_rows(x)
             n, d = x2.shape
             lat2 = None if latent is None else latent.reshape(n, -1).to(torch.float32).contiguous()
-            prog = self._fused(d, 0 if lat2 is None else lat2.shape[1], t0 is not None, x.device)
+            from .flows.time_pointwise import row_times
+            # one time per row (n values, or anything that broadcasts to x.shape[:-1] + (1,)); a per-feature t goes layer by layer
+            per_row = all(v is None or v.numel() == n or row_times(v, x) is not None for v in (t, t0))
+            prog = self._fused(d, 0 if lat2 is None else lat2.shape[1], t0 is not None, x.device) if per_row else None
             if prog is not None:
                 def rows(v):
                     v = v.to(device=x.device, dtype=torch.float32)

@@ -1,17 +1,18 @@
 """Parameter-free element-wise flows (reference: stribor/flows/sigmoid.py:9-56, flows/activations.py:11-101,
-flows/cumsum.py:40-92, flows/identity.py:6-25): ``Sigmoid``, ``Logit``, ``ELU``, ``LeakyReLU``, ``Cumsum``, ``Diff``,
-``Identity``.  Same constructors and method sets; every call is one ``sx_pointwise`` launch (values, per-element
+flows/cumsum.py:40-142, flows/identity.py:6-25): ``Sigmoid``, ``Logit``, ``ELU``, ``LeakyReLU``, ``Cumsum``, ``Diff``,
+``CumsumColumn``, ``DiffColumn``, ``Identity``.  Same constructors and method sets; every call is one ``sx_pointwise`` launch (values, per-element
 log-derivative and its row sum in the same pass).  They do not join fused programs: a flow that contains one runs
 layer by layer.
 """
 import math
+import warnings
 
 import torch
 
 from .. import _hip
-from ..flow import ElementwiseTransform, flatten_rows, graph_rows, graph_wanted
+from ..flow import ElementwiseTransform, Transform, flatten_rows, graph_rows, graph_wanted
 
-__all__ = ['Sigmoid', 'Logit', 'ELU', 'LeakyReLU', 'Cumsum', 'Diff', 'Identity']
+__all__ = ['Sigmoid', 'Logit', 'ELU', 'LeakyReLU', 'Cumsum', 'Diff', 'CumsumColumn', 'DiffColumn', 'Identity']
 
 PW_SIGMOID, PW_LOGIT, PW_ELU, PW_ELU_INV, PW_LEAKY, PW_LEAKY_INV, PW_CUMSUM, PW_DIFF = range(1, 9)
 
@@ -197,6 +198,46 @@ class Cumsum(_Pointwise):
 
 class Diff(Cumsum):
     """cumsum.py:76-85."""
+    _fwd, _inv = PW_DIFF, PW_CUMSUM
+
+
+class CumsumColumn(Transform):
+    """cumsum.py:94-132: cumulative sum along ONE column of (..., M, N) matrices, i.e. over the M entries x[..., :, column].  The column is
+    gathered into contiguous rows, summed by the PW_CUMSUM launch and written into a clone of x; log-determinant 0."""
+    _fwd, _inv = PW_CUMSUM, PW_DIFF
+
+    def __init__(self, column: int):
+        super().__init__()
+        warnings.warn('The Jacobian related function are not tested.', RuntimeWarning)       # cumsum.py:111
+        self.column = column
+
+    def _scan(self, x, kind):
+        _hip.require_device(x, 'x')
+        col = x[..., self.column]                                                    # (..., M)
+        if graph_wanted(None, x):
+            c2, _, lead = graph_rows(col)
+            out = PointwiseOp.apply(c2, kind, 0.0)[0].reshape(*lead, c2.shape[1])
+        else:
+            out = run_pointwise(col, kind)[0]
+        y = x.clone()
+        y[..., self.column] = out.to(y.dtype)
+        return y
+
+    def forward(self, x, **kwargs):
+        return self._scan(x, self._fwd)
+
+    def inverse(self, y, **kwargs):
+        return self._scan(y, self._inv)
+
+    def log_det_jacobian(self, x, y=None, **kwargs):
+        return torch.zeros_like(x[..., :1])
+
+    def log_diag_jacobian(self, x, y=None, **kwargs):
+        return torch.zeros_like(x)
+
+
+class DiffColumn(CumsumColumn):
+    """cumsum.py:134-142: the inverse of CumsumColumn."""
     _fwd, _inv = PW_DIFF, PW_CUMSUM
 
 

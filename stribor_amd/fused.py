@@ -1136,6 +1136,21 @@ class ProgramBuilder:
         self.jobs.append(_ScalarsJob(vals, off))
         self._step(_hip.STEP_POINTWISE, off, n, tt=T, act=int(kind), ldj_scale=float(ldj_coeff), ldj_const=float(param))
 
+    def add_pointwise_time(self, kind: int, param: float, time_sel: int) -> None:
+        """One time-dependent point-wise flow on the data columns (activations.py:125-196) as an SX_STEP_POINTWISE_TIME step: `kind` = the
+        sx_pointwise_time kind for the direction taken, `param` its parameter (log_time flag / temperature), `time_sel` which of the
+        program's times the step reads (0: t, 1: t0).  Values only: the step adds nothing to the log-det accumulator."""
+        self._narrow_only('time-dependent point-wise flows')
+        self._freeze_input()
+        T = self.tiles
+        off, n = self._alloc(32 * T)
+        vals = np.zeros(32 * T, dtype=np.float64)
+        for i, c in self._register_order():
+            if c >= 0:
+                vals[i] = 1.0
+        self.jobs.append(_ScalarsJob(vals, off))
+        self._step(_hip.STEP_POINTWISE_TIME, off, n, tt=T, act=int(kind), ldj_const=float(param), pad_=int(time_sel))
+
     def add_linear(self, sources, fn, ldj_fn=None) -> None:
         """y = W . x + b on the data columns (W, b = fn(device), torch Linear layout [out, in]): one LINEAR_TILE step
         for the whole layer; ldj_fn(device) -> its log-det term (0-dim tensor, signed and scaled) or None for 0."""
@@ -1258,8 +1273,9 @@ class ProgramBuilder:
                                len({s['act'] & 1 for s in self.steps if s['kind'] == _hip.STEP_RQS_PHASE}) > 1)
         if mixed and any(s['kind'] == _hip.STEP_RQS_PHASE and s['tt'] > 16 for s in self.steps):
             raise NotImplementedError('spline couplings of 17..32 bins fuse in programs of rational-quadratic couplings only')
-        if _hip.STEP_COUPLING_TIME in kinds and len(kinds) > 1:
-            raise NotImplementedError('time-conditioned couplings form fused programs of their own')
+        timed = kinds & {_hip.STEP_COUPLING_TIME, _hip.STEP_POINTWISE_TIME}
+        if timed and kinds - timed:
+            raise NotImplementedError('time-conditioned couplings and time-dependent point-wise flows form fused programs of their own')
         if pointwise and (dense or (deep and not mixed) or kinds & {_hip.STEP_MLP_HIDDEN, _hip.STEP_MLP_HIDDEN2, _hip.STEP_MLP_OUT_TILE}):
             raise NotImplementedError('point-wise steps share fused programs with couplings and element-wise affines only')
         if deep and kinds & {_hip.STEP_LINEAR_TILE, _hip.STEP_ROW_SCALE_EXP, _hip.STEP_MLP_HIDDEN, _hip.STEP_MLP_HIDDEN2,

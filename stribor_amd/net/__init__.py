@@ -1,4 +1,5 @@
 from .mlp import MLP
+from .resnet import ResNet, ResNetBlock
 from .time_net import TimeFourier, TimeFourierBounded, TimeIdentity, TimeLinear, TimeLog, TimeTanh
 from .attention import Attention, InducedSelfAttention, SelfAttention, attention, self_attention_closed_form
 from .equivariant import EquivariantLayer, EquivariantNet
