@@ -760,6 +760,30 @@ typedef struct {
 } sx_sn_job;
 int sx_spectral_sigma(const sx_sn_job *job_host, int32_t n_calls, float *sigma, void *stream);
 
+/* Backward of sx_resnet_flow, for training (csrc/sx_resnet_bwd.hip).  With h_0 = x, a_l = (W_l h_{l-1}) / sigma_l + b_l,
+ * h_l = phi_l(a_l), g = h_L, r = s * g, and J_r^T the transpose product of r's Jacobian at x:
+ *   inverse == 0: gout = gin + J_r(x)^T gin (x: the forward's input); parameter cotangents at c = gin
+ *   inverse != 0: w = gin; `iterations` times w = gin - J_r(x)^T w (x: the fixed point the inverse returned); gout = w;
+ *                 parameter cotangents at c = -w (the implicit-function gradient of the fixed-point inverse)
+ * dW[l] = sum_rows e_l h_{l-1}^T is the gradient with respect to the EFFECTIVE weight W_l / sigma_l (the caller carries it
+ * to weight_orig), db[l] = sum_rows e_l, gs = c * g as rows (the cotangent of s).  A NULL dW[l] / db[l] / gs is not computed;
+ * with all of them NULL the call is a pure vector-Jacobian product and `partial` is not touched.
+ * Coverage: dim and every width <= SX_RESNET_BWD_MAX_WIDTH, up to three hidden layers, forward + transposed images + scratch
+ * within SX_RESNET_LDS_BYTES (sx_resnet_bwd_lds_bytes returns 0 outside it).  x, s_rows (NULL: s = 1), gin, gout, gs: fp32
+ * [n_rows, dim]; sigma: ONE row [n_wrapped]; partial: sx_resnet_bwd_partial_floats(net, n_rows) floats of scratch (needs no
+ * initialisation).  Two launches (the kernel and the ordered sum of its per-wave partials), one when no dW / db is wanted;
+ * no atomics: the same inputs give the same bits. */
+#define SX_RESNET_BWD_MAX_WIDTH 64
+typedef struct {
+    float *dW[SX_RESNET_MAX_LAYERS];   /* [out_dim, in_dim] of layer l, or NULL */
+    float *db[SX_RESNET_MAX_LAYERS];   /* [out_dim] of layer l, or NULL         */
+} sx_resnet_grads;
+size_t sx_resnet_bwd_lds_bytes(const sx_resnet_net *net_host);
+size_t sx_resnet_bwd_partial_floats(const sx_resnet_net *net_host, int64_t n_rows);
+int sx_resnet_flow_bwd(const sx_resnet_net *net_host, const float *x, const float *s_rows, const float *sigma, const float *gin,
+                       float *gout, float *gs, float *partial, const sx_resnet_grads *grads, int64_t n_rows, int32_t iterations,
+                       int32_t inverse, void *stream);
+
 /* ---- continuous normalizing flow on a fixed grid (ContinuousTransform, stribor/flows/cnf.py:13-262; net/diffeq.py:51-75) ----
  * The ODE function is DiffeqMLP: an MLP over the columns [t, x (dim), latent (latent_dim)] with one or two hidden layers and no
  * final activation.  One launch integrates x from t0 to t1 and, on request, the exact divergence along the path. */

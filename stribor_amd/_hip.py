@@ -65,7 +65,8 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_wgrad_scratch_floats', 'sx_wgrad_layer_scratch_floats', 'sx_flow_bwd_max_steps', 'sx_flow_bwd_partials',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
-           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
+           'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_resnet_bwd_lds_bytes', 'sx_resnet_bwd_partial_floats',
+           'sx_resnet_flow_bwd', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
            'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
            'sx_cnf_exact_set_lds_bytes', 'sx_cnf_exact_set_flow', 'sx_cnf_attn_lds_bytes', 'sx_cnf_attn_flow',
            'sx_cnf_exact_attn_lds_bytes', 'sx_cnf_exact_attn_flow',
@@ -81,6 +82,7 @@ MVN_MAX_DIM = 128
 RESNET_MAX_LAYERS = 4
 RESNET_LDS_BYTES = 160 * 1024
 RESNET_TIME_NONE, RESNET_TIME_ROWS = -1, 5
+RESNET_BWD_MAX_WIDTH = 64        # ... their backward (sx_resnet_flow_bwd)
 
 # continuous normalizing flow on a fixed grid (include/stribor_hip.h: sx_cnf_flow)
 CNF_MAX_DIM = 64
@@ -136,6 +138,10 @@ class sx_resnet_layer(C.Structure):
 class sx_resnet_net(C.Structure):
     _fields_ = [('layer', sx_resnet_layer * 4), ('n_layers', C.c_int32), ('dim', C.c_int32), ('act', C.c_int32),
                 ('final_act', C.c_int32), ('n_wrapped', C.c_int32), ('pad_', C.c_int32)]
+
+
+class sx_resnet_grads(C.Structure):
+    _fields_ = [('dW', C.c_void_p * 4), ('db', C.c_void_p * 4)]
 
 
 class sx_cnf_layer(C.Structure):
@@ -318,6 +324,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_resnet_flow.argtypes = [C.POINTER(sx_resnet_net), vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sx_spectral_sigma.restype = i32
     lib.sx_spectral_sigma.argtypes = [C.POINTER(sx_sn_job), i32, vp, vp]
+    lib.sx_resnet_bwd_lds_bytes.restype = C.c_size_t
+    lib.sx_resnet_bwd_lds_bytes.argtypes = [C.POINTER(sx_resnet_net)]
+    lib.sx_resnet_bwd_partial_floats.restype = C.c_size_t
+    lib.sx_resnet_bwd_partial_floats.argtypes = [C.POINTER(sx_resnet_net), i64]
+    lib.sx_resnet_flow_bwd.restype = i32
+    lib.sx_resnet_flow_bwd.argtypes = [C.POINTER(sx_resnet_net), vp, vp, vp, vp, vp, vp, vp, C.POINTER(sx_resnet_grads), i64, i32, i32, vp]
     lib.sx_attention_fwd.restype = i32
     lib.sx_attention_fwd.argtypes = [C.POINTER(sx_attention_args), vp, vp, vp]
     lib.sx_attention_bwd.restype = i32
