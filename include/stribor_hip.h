@@ -1132,6 +1132,58 @@ int sx_attention_fwd(const sx_attention_args *args_host, float *out, float *lse,
 int sx_attention_bwd(const sx_attention_args *args_host, const float *y, const float *dy, const float *lse, float *dq, float *dk,
                      float *dv, float *delta, void *stream);
 
+/* ---- Deep Sets conditioner (net.EquivariantNet, stribor/net/equivariant.py:6-93; csrc/sx_equivariant.hip) ----------------------
+ * Rows are set elements, the set_size = N elements of a set contiguous; n_rows = (number of sets) * N.  With h_0 = x and
+ * S = sum_j h_{l-1,j} over EVERY element of the set, equivariant layer l is
+ *   mask == NULL:  z_i = (A h_{l-1,i} + a) + (B S + b) / N
+ *   mask:          z_i = (A h_{l-1,i} + a) m_i + ((B S + b) m_i) / c,   m_i = mask[i * mask_rs], c = sum_j m_j (a true division:
+ *                  a set with c == 0 is NaN in every element, and in that set only)
+ * h_l = act(z_l) below the last layer, y = final_act(z_L).  Every pointer of the descriptor is a parameter of the module itself;
+ * nothing is derived by the caller.  Exact fp32 (v_mfma_f32_32x32x2_f32); a set's result does not depend on the other sets. */
+#define SX_EQUIVARIANT_MAX_SIZE   128
+#define SX_EQUIVARIANT_MAX_IN     64
+#define SX_EQUIVARIANT_MAX_HIDDEN 64
+#define SX_EQUIVARIANT_MAX_OUT    128
+/* ... of the backward */
+#define SX_EQUIVARIANT_BWD_MAX_IN     32
+#define SX_EQUIVARIANT_BWD_MAX_HIDDEN 64
+#define SX_EQUIVARIANT_BWD_MAX_OUT    64
+typedef struct {
+    const float *A[3];      /* l1.weight of layer l, [out_dim[l], in] row-major (in = in_dim, then out_dim[l - 1])              */
+    const float *a[3];      /* l1.bias, [out_dim[l]]                                                                          */
+    const float *B[3];      /* l2.weight, the shape of A                                                                      */
+    const float *b[3];      /* l2.bias                                                                                        */
+    int32_t n_layers;       /* equivariant layers: 2 (one hidden layer) or 3 (two)                                            */
+    int32_t in_dim;         /* 1..SX_EQUIVARIANT_MAX_IN                                                                       */
+    int32_t act;            /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU, between the layers                                        */
+    int32_t final_act;      /* the same codes, after the last layer                                                           */
+    int32_t set_size;       /* 1..SX_EQUIVARIANT_MAX_SIZE                                                                     */
+    int32_t out_dim[3];     /* hidden widths 1..SX_EQUIVARIANT_MAX_HIDDEN, then the output 1..SX_EQUIVARIANT_MAX_OUT          */
+} sx_equivariant_net;
+typedef struct {
+    float *dA[3], *da[3], *dB[3], *db[3];      /* the shapes of A, a, B, b; NULL: not wanted                                  */
+} sx_equivariant_grads;
+
+/* Bytes of LDS a launch stages for this network (backward != 0: of sx_equivariant_bwd): the vectors, the set-sum scratch, the
+ * backward's contraction slots and as many of the weight images as fit SX_CNF_LDS_BYTES (the others are read from the parameters in
+ * global memory); 0 for a network outside the coverage (the backward's: SX_EQUIVARIANT_BWD_MAX_*).  Reads the integer fields only. */
+size_t sx_equivariant_lds_bytes(const sx_equivariant_net *net_host, int32_t backward);
+
+/* y [n_rows, out_dim] contiguous = net(x, mask).  x: row r at x + r * x_rs (unit column stride); mask: NULL, or one value per row
+ * at mask + r * mask_rs (mask[..., 0] of a (..., N, k) tensor is read in place with mask_rs = k).  n_rows must be a multiple of
+ * set_size.  One launch; the hidden activations never reach global memory. */
+int sx_equivariant_fwd(const sx_equivariant_net *net_host, const float *x, int64_t x_rs, const float *mask, int64_t mask_rs, float *y,
+                       int64_t n_rows, void *stream);
+
+/* The backward of the call above at gy = dloss/dy [n_rows, out_dim] contiguous: dx [n_rows, in_dim] contiguous (NULL: not wanted)
+ * and the parameter gradients of `grads` (NULL, or NULL entries: not wanted).  The mask gets no gradient.  h_l is recomputed from x.
+ * partial: sx_equivariant_bwd_partial_floats(net, n_rows) floats of scratch when a parameter gradient is wanted (needs no
+ * initialisation).  Two launches (the kernel and the ordered sum of its per-wave partials), one when only dx is wanted; no atomics:
+ * the same inputs give the same bits. */
+size_t sx_equivariant_bwd_partial_floats(const sx_equivariant_net *net_host, int64_t n_rows);
+int sx_equivariant_bwd(const sx_equivariant_net *net_host, const float *x, int64_t x_rs, const float *mask, int64_t mask_rs,
+                       const float *gy, float *dx, float *partial, const sx_equivariant_grads *grads, int64_t n_rows, void *stream);
+
 /* LDS bytes and grid the launcher will use for a program (introspection for tests/bench). */
 int sx_flow_launch_info(const sx_program *prog_host, int64_t n_rows, int32_t *grid, int32_t *block,
                         int32_t *lds_bytes);

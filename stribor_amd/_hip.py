@@ -72,6 +72,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_cnf_exact_attn_lds_bytes', 'sx_cnf_exact_attn_flow',
            'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd',
            'sx_cnf_adaptive_lds_bytes', 'sx_cnf_adaptive_flow',
+           'sx_equivariant_lds_bytes', 'sx_equivariant_bwd_partial_floats', 'sx_equivariant_fwd', 'sx_equivariant_bwd',
            'sx_base_logprob', 'sx_normal_bwd_partial_floats', 'sx_normal_logprob_bwd', 'sx_mvn_lds_bytes', 'sx_mvn_logprob']
 
 # base densities (include/stribor_hip.h: sx_base_logprob / sx_mvn_logprob)
@@ -100,6 +101,10 @@ CNF_ATTN_MAX_DIM, CNF_ATTN_MAX_IN, CNF_ATTN_MAX_HIDDEN, CNF_ATTN_MAX_EMBED, CNF_
 
 # multi-head attention core (include/stribor_hip.h: sx_attention_fwd / sx_attention_bwd)
 ATTENTION_MAX_HEAD_DIM = 128
+
+# Deep Sets conditioner (include/stribor_hip.h: sx_equivariant_fwd / sx_equivariant_bwd)
+EQUIVARIANT_MAX_SIZE, EQUIVARIANT_MAX_IN, EQUIVARIANT_MAX_HIDDEN, EQUIVARIANT_MAX_OUT = 128, 64, 64, 128
+EQUIVARIANT_BWD_MAX_IN, EQUIVARIANT_BWD_MAX_HIDDEN, EQUIVARIANT_BWD_MAX_OUT = 32, 64, 64
 
 
 class HipLibraryMissing(RuntimeError):
@@ -192,6 +197,15 @@ class sx_attention_args(C.Structure):
                 ('k_bs', C.c_int64), ('k_rs', C.c_int64), ('v_bs', C.c_int64), ('v_rs', C.c_int64), ('mask', C.c_void_p),
                 ('mask_bs', C.c_int64), ('R', C.c_int64), ('Nq', C.c_int32), ('Nk', C.c_int32), ('E', C.c_int32),
                 ('n_heads', C.c_int32), ('mask_diagonal', C.c_int32), ('out_mask', C.c_int32)]
+
+
+class sx_equivariant_net(C.Structure):
+    _fields_ = [('A', C.c_void_p * 3), ('a', C.c_void_p * 3), ('B', C.c_void_p * 3), ('b', C.c_void_p * 3), ('n_layers', C.c_int32),
+                ('in_dim', C.c_int32), ('act', C.c_int32), ('final_act', C.c_int32), ('set_size', C.c_int32), ('out_dim', C.c_int32 * 3)]
+
+
+class sx_equivariant_grads(C.Structure):
+    _fields_ = [('dA', C.c_void_p * 3), ('da', C.c_void_p * 3), ('dB', C.c_void_p * 3), ('db', C.c_void_p * 3)]
 
 
 class sx_sn_layer(C.Structure):
@@ -371,6 +385,14 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_cnf_attn_lds_bytes.argtypes = [C.POINTER(sx_cnf_attn_net)]
     lib.sx_cnf_attn_flow.restype = i32
     lib.sx_cnf_attn_flow.argtypes = [C.POINTER(sx_cnf_attn_net), vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32, vp]
+    lib.sx_equivariant_lds_bytes.restype = C.c_size_t
+    lib.sx_equivariant_lds_bytes.argtypes = [C.POINTER(sx_equivariant_net), i32]
+    lib.sx_equivariant_bwd_partial_floats.restype = C.c_size_t
+    lib.sx_equivariant_bwd_partial_floats.argtypes = [C.POINTER(sx_equivariant_net), i64]
+    lib.sx_equivariant_fwd.restype = i32
+    lib.sx_equivariant_fwd.argtypes = [C.POINTER(sx_equivariant_net), vp, i64, vp, i64, vp, i64, vp]
+    lib.sx_equivariant_bwd.restype = i32
+    lib.sx_equivariant_bwd.argtypes = [C.POINTER(sx_equivariant_net), vp, i64, vp, i64, vp, vp, vp, C.POINTER(sx_equivariant_grads), i64, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

@@ -44,6 +44,9 @@ class DiffeqConcat(DiffeqNet):
         if isinstance(self.net, SelfAttention) and type(self.net).forward is SelfAttention.forward and torch.is_grad_enabled():
             # the same for the attention: its HIP core and batch_linear are differentiable once
             return self.net.forward_twice_differentiable(inp, **kwargs)
+        if isinstance(self.net, EquivariantNet) and type(self.net).forward is EquivariantNet.forward:
+            # the same for the Deep Sets net, in every grad mode: the reference's op sequence, never the once-differentiable kernel
+            return self.net.forward_twice_differentiable(inp, **kwargs)
         return self.net(inp, **kwargs)
 
 
