@@ -1374,6 +1374,43 @@ __device__ __forceinline__ void st_elem(void *p, int64_t off, float v, int bf16)
     else reinterpret_cast<float *>(p)[off] = v;
 }
 
+// The x tiles of one sample slot, all pieces issued back to back (flow_fused_kernel's one-flight path); p = the row's first element.
+// A bf16 piece stays raw (two dwords, registers of its own) until x_flight_widen; fp32 pieces land in the state registers.
+template <int TX>
+__device__ __forceinline__ void x_flight_issue(u32x2 (&raw)[TX][4], const uint16_t *p, int h) {
+    // (plain loads: the eight pieces of a lane share one 128-B line; the streaming policy re-fetched it between them)
+#pragma unroll
+    for (int t = 0; t < TX; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) raw[t][q] = *reinterpret_cast<const u32x2 *>(p + 32 * t + 8 * q + 4 * h);
+}
+template <int TX, int NS>
+__device__ __forceinline__ void x_flight_widen(tile<NS> (&xs)[TX], int n, const u32x2 (&raw)[TX][4]) {
+#pragma unroll
+    for (int t = 0; t < TX; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t a = raw[t][q].x, b = raw[t][q].y;
+            xs[t].v[n][4 * q + 0] = __uint_as_float(a << 16); xs[t].v[n][4 * q + 1] = __uint_as_float(a & 0xffff0000u);
+            xs[t].v[n][4 * q + 2] = __uint_as_float(b << 16); xs[t].v[n][4 * q + 3] = __uint_as_float(b & 0xffff0000u);
+        }
+}
+template <int TX, int MODE, int NS>
+__device__ __forceinline__ void x_flight_issue(tile<NS> (&xs)[TX], int n, const float *p, int h) {
+    // spline programs re-read 3.2 MB of blobs from L2 per chunk: x is kept out of their way by the streaming policy
+    constexpr bool NT_X = MODE == 3 || MODE == 10 || MODE == 12 || MODE == 13 || MODE == 18 || MODE == 19;
+#pragma unroll
+    for (int t = 0; t < TX; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            f32x4 v;
+            if constexpr (NT_X) v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p + 32 * t + 8 * q + 4 * h));
+            else v = *reinterpret_cast<const f32x4 *>(p + 32 * t + 8 * q + 4 * h);
+            xs[t].v[n][4 * q + 0] = v.x; xs[t].v[n][4 * q + 1] = v.y;
+            xs[t].v[n][4 * q + 2] = v.z; xs[t].v[n][4 * q + 3] = v.w;
+        }
+}
+
 // A step descriptor out of the kernarg segment, as DWORDS: the eight byte-sized fields of dstep otherwise come through vector
 // byte loads (no scalar sub-dword load on gfx9) -- and a vector load's s_waitcnt vmcnt(0) right behind the next step's
 // LDS-DMA issue waits for that DMA and for every store still in flight (vector-memory operations retire in order).
@@ -1500,6 +1537,17 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
     lds_u32 *slot = (lds_u32 *)(smem + (resident ? buf_floats + WB * 4096 : 2 * buf_floats));      // ds_write_b32 / ds_read_b32, ordered by the barrier
     [[maybe_unused]] bool have_pf = false;
     [[maybe_unused]] float gg_next = 0.f;                     // MODE 11: dL/dlog_prob of the prefetched chunk's row
+    // whole x tiles in identity column order and no other state tile: the chunk's rows are loaded in one flight (x_flight_issue);
+    // ragged widths, gathered columns, latent tiles and the backward kernels' adjoint tiles and fragment paths keep the loads below
+    const bool x_flight = MODE != 4 && MODE != 11 && prog.identity_cols && x_tiles == TX && dim == 32 * TX;
+    // MODE 5 / 6 on bf16 rows: the NEXT chunk's rows and ticket are requested behind this chunk's last step, in front of its stores,
+    // row reduction and LDS sum (below).  The raw pieces are defined there on every path and read only at the top of the next chunk:
+    // never live across the step loop, where these kernels have no register to spare (LDS_SUM).  (fp32 rows keep the flight at the
+    // top: their 32 raw registers, held across the epilogue as four-register tuples, made <1,2,2,5> spill seven VGPRs to scratch.)
+    constexpr bool X_AHEAD = MODE == 5 || MODE == 6;
+    [[maybe_unused]] u32x2 xpre[NS][TX][4];
+    [[maybe_unused]] uint32_t ticket_pre = 0;
+    [[maybe_unused]] bool have_xpre = false;
     int iter = 0;
     for (int64_t chunk = blockIdx.x; chunk < n_chunks; ++iter) {
         // lane-derived indices are re-derived per chunk from the thread id (opaque to the optimizer) instead of
@@ -1584,6 +1632,34 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             }
             have_pf = false;
         }
+        // the ticket is requested behind the x loads and, like them, first waited for at step 0's vmcnt(0)
+        // (built with the atomic optimizer off: its readfirstlane epilogue would wait right here)
+        uint32_t ticket = 0;
+        const auto take_ticket = [&]() { if (dyn && threadIdx.x == 0) ticket = atomicAdd(k.work, 1u); };
+        if (x_flight) {
+            // ONE FLIGHT: every piece of the chunk's rows goes out back to back -- no branch and no wait between them -- and is first
+            // waited for behind the ticket request (bf16 pieces are widened there): one memory round trip per chunk where a load and
+            // its conversion under `c + 3 < dim` made one per piece (eight dependent ones on the headline).  The row address is
+            // formed once, for the storage type in use.  Bounds: lrow[] is clamped to [0, n_rows) and dim == 32 * TX, so the pieces
+            // are exactly the bytes of one row of x -- the very bytes the loop below reads.
+            if (X_AHEAD && have_xpre) {
+                // (requested a chunk ago, and long since landed: the previous chunk's closing wait covers them)
+#pragma unroll
+                for (int n = 0; n < NS; ++n) x_flight_widen<TX>(xs, n, xpre[n]);
+                ticket = ticket_pre;
+            } else if (bf16) {
+                u32x2 raw[NS][TX][4];
+#pragma unroll
+                for (int n = 0; n < NS; ++n) x_flight_issue<TX>(raw[n], reinterpret_cast<const uint16_t *>(k.x) + lrow[n] * dim, h);
+                take_ticket();
+#pragma unroll
+                for (int n = 0; n < NS; ++n) x_flight_widen<TX>(xs, n, raw[n]);
+            } else {
+#pragma unroll
+                for (int n = 0; n < NS; ++n) x_flight_issue<TX, MODE>(xs, n, reinterpret_cast<const float *>(k.x) + lrow[n] * dim, h);
+                take_ticket();
+            }
+        } else {
         if (!from_frag)
 #pragma unroll
         for (int n = 0; n < NS; ++n) {
@@ -1657,10 +1733,8 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             }
         }
 
-        // the ticket is requested behind the x loads and, like them, first waited for at step 0's vmcnt(0)
-        // (built with the atomic optimizer off: its readfirstlane epilogue would wait right here)
-        uint32_t ticket = 0;
-        if (dyn && threadIdx.x == 0) ticket = atomicAdd(k.work, 1u);
+        take_ticket();
+        }
         float ldj[NS];
 #pragma unroll
         for (int n = 0; n < NS; ++n) ldj[n] = 0.f;
@@ -2338,6 +2412,33 @@ __global__ __launch_bounds__(64 * SX_BLOCK_WAVES(TX, MODE), SX_WAVES_FOR(TX, MOD
             if (rg.bad && k.redo != nullptr) redo_push<NS>(k.redo, rg, lane, (uint32_t)chunk * (uint32_t)(WB * NS) + (uint32_t)(wave * NS));
         }
 #endif
+        if constexpr (X_AHEAD) {
+            // the next chunk's rows, raw, and the ticket that goes with it: their round trip passes under this chunk's stores, row
+            // reduction and sum instead of in front of the next chunk's first barrier, where all waves of the workgroup stood in it
+            // together.  They stand BEHIND the range check above: in front of it the compiler parked the state tiles in other
+            // registers behind an s_waitcnt vmcnt(0) of its own, i.e. waited for these loads right where they were issued.  (The
+            // redo pass takes its rows from its list at the top.)  Bounds: next_chunk < n_chunks, so the chunk has a row; every
+            // lane's row is clamped to [0, n_rows) as lrow[] is, and dim == 32 * TX: the pieces are the bytes of that row of x.
+            have_xpre = x_flight && bf16 && !redo_pass && next_chunk < n_chunks;
+#pragma unroll
+            for (int n = 0; n < NS; ++n)
+#pragma unroll
+                for (int t = 0; t < TX; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)      // (defined on every path, by no instruction)
+                        asm volatile("" : "=v"(xpre[n][t][q].x), "=v"(xpre[n][t][q].y));
+            ticket_pre = 0;
+            if (have_xpre) {
+                uint32_t tid_ = threadIdx.x;
+                asm volatile("" : "+v"(tid_));
+#pragma unroll
+                for (int n = 0; n < NS; ++n) {
+                    const int64_t r = next_chunk * ROWS_PER_BLOCK + (tid_ >> 6) * (32 * NS) + n * 32 + (tid_ & 31);
+                    x_flight_issue<TX>(xpre[n], reinterpret_cast<const uint16_t *>(k.x) + (r < n_rows ? r : n_rows - 1) * dim, (tid_ >> 5) & 1);
+                }
+                if (dyn && threadIdx.x == 0) ticket_pre = atomicAdd(k.work, 1u);
+            }
+        }
         if constexpr (MODE == 11) {
             if (k.frag_out != nullptr && chunk * WB + wave < ((n_rows + 31) >> 5)) {
                 f32x4 *fo = reinterpret_cast<f32x4 *>(k.frag_out) + (chunk * WB + wave) * (TX * 4 * 64) + lane;
