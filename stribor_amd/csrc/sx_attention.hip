@@ -4,9 +4,9 @@
 // sx_attention_fwd -- one workgroup = W waves (W = 1..4) = 32 W queries of one (batch row r, head); each wave owns 32 queries and
 // walks the key / value tiles of 32 keys with an online (running max, running sum) softmax:
 //   * swapped Q K^T: S^T = K Q^T on v_mfma_f32_32x32x2_f32 (A = the K tile from LDS, B = the wave's queries, held in registers for
-//     the whole walk), so a lane owns ONE query (lane & 31) and 16 of the tile's 32 keys (at_kmap(r, lane >> 5)) -- the row max
+//     the whole walk), so a lane owns ONE query (lane & 31) and 16 of the tile's 32 keys (sx_kmap(r, lane >> 5)) -- the row max
 //     and row sum are 15 in-lane ops + one swap with lane ^ 32, no serial-lane softmax;
-//   * the probability tile P^T is, register for register, the B operand of O^T += V^T P^T (k-step r <-> key at_kmap(r, h)),
+//   * the probability tile P^T is, register for register, the B operand of O^T += V^T P^T (k-step r <-> key sx_kmap(r, h)),
 //     so P never leaves registers either; O^T accumulates in up to four 32 x 32 tiles (dh <= 128);
 //   * the contraction over d splits the head into two halves of HALF features, one per lane half (k-step s of lane half h <->
 //     feature h HALF + s); HALF = 4, 8, 16, 32 or 64 is a template parameter (dh <= 2 HALF, zero-padded), so every LDS address
@@ -28,8 +28,6 @@
 #define SX_ATT_MAX_WAVES 4
 
 namespace {
-
-__host__ __device__ inline int at_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 extern __shared__ __attribute__((aligned(16))) float at_smem[];
 
@@ -81,7 +79,7 @@ __device__ __forceinline__ f32x16 at_dot_tile(const float *tile, int WS, const f
     return acc;
 }
 
-// acc[t] += tile^T x for the d tiles t: A lane (c, h) of k-step r = tile[at_kmap(r, h)][32 t + c], B = x[r]
+// acc[t] += tile^T x for the d tiles t: A lane (c, h) of k-step r = tile[sx_kmap(r, h)][32 t + c], B = x[r]
 template <int DT>
 __device__ __forceinline__ void at_acc_tiles(f32x16 (&acc)[DT], const float *tile, int WS, const f32x16 &x, int c, int h, int dh) {
 #pragma unroll
@@ -89,11 +87,11 @@ __device__ __forceinline__ void at_acc_tiles(f32x16 (&acc)[DT], const float *til
         if (32 * t >= dh) break;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[at_kmap(r, h) * WS + 32 * t + c], x[r], acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[sx_kmap(r, h) * WS + 32 * t + c], x[r], acc[t], 0, 0, 0);
     }
 }
 
-// out[row][head dh + d] = acc[t][r] * f for d = 32 t + at_kmap(r, h) < dh (the lane's column is `row`)
+// out[row][head dh + d] = acc[t][r] * f for d = 32 t + sx_kmap(r, h) < dh (the lane's column is `row`)
 template <int DT>
 __device__ __forceinline__ void at_store_tiles(float *out, int64_t row, int E, int head, int dh, const f32x16 (&acc)[DT], int h,
                                                float f) {
@@ -102,7 +100,7 @@ __device__ __forceinline__ void at_store_tiles(float *out, int64_t row, int E, i
     for (int t = 0; t < DT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int d = 32 * t + at_kmap(r, h);
+            const int d = 32 * t + sx_kmap(r, h);
             if (d < dh) o[d] = acc[t][r] * f;
         }
 }
@@ -159,12 +157,12 @@ __global__ __launch_bounds__(SX_ATT_MAX_WAVES * 64) void attention_q_kernel(cons
             if (threadIdx.x < 32) kb[threadIdx.x] = at_key_live(p, r, k0 + (int)threadIdx.x) ? 0.f : -INFINITY;
             __syncthreads();
             if (!wave_live) continue;
-            f32x16 s = at_dot_tile<HALF>(Ks, WS, qb, c, h);      // S^T[key at_kmap(j, h)][query c]
+            f32x16 s = at_dot_tile<HALF>(Ks, WS, qb, c, h);      // S^T[key sx_kmap(j, h)][query c]
             if constexpr (!BWD) {
                 float tmax = -INFINITY;
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    const int key = at_kmap(j, h);
+                    const int key = sx_kmap(j, h);
                     float v = s[j] * a.scale + kb[key];
                     if (p.mask_diagonal && k0 + key == qi) v = -INFINITY;
                     s[j] = v;
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(SX_ATT_MAX_WAVES * 64) void attention_q_kernel(cons
                 const f32x16 dp = at_dot_tile<HALF>(Vs, WS, gb, c, h);   // dP^T[key][query]
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    const int key = at_kmap(j, h);
+                    const int key = sx_kmap(j, h);
                     float pv = __expf(s[j] * a.scale + kb[key] - lse_q);
                     if (p.mask_diagonal && k0 + key == qi) pv = 0.f;
                     s[j] = pv * (dp[j] - dlt);
@@ -207,7 +205,7 @@ __global__ __launch_bounds__(SX_ATT_MAX_WAVES * 64) void attention_q_kernel(cons
             for (int t = 0; t < DT; ++t)
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    const int d = 32 * t + at_kmap(j, h);
+                    const int d = 32 * t + sx_kmap(j, h);
                     if (d < dh) o[d] = (acc[t][j] * inv) * mo;
                 }
             if (h == 0) a.lse[(r * H + head) * p.Nq + qi] = l > 0.f ? m + __logf(l) : INFINITY;
@@ -255,10 +253,10 @@ __global__ __launch_bounds__(SX_ATT_MAX_WAVES * 64) void attention_kv_kernel(con
             }
             __syncthreads();
             if (!wave_live) continue;
-            f32x16 s = at_dot_tile<HALF>(Qs, WS, kr, c, h);          // S[query at_kmap(j, h)][key c]
+            f32x16 s = at_dot_tile<HALF>(Qs, WS, kr, c, h);          // S[query sx_kmap(j, h)][key c]
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                const int qr = at_kmap(j, h);
+                const int qr = sx_kmap(j, h);
                 float pv = __expf(s[j] * a.scale + kbias - ls[qr]);
                 if (p.mask_diagonal && q0 + qr == kj) pv = 0.f;
                 s[j] = pv;
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(SX_ATT_MAX_WAVES * 64) void attention_kv_kernel(con
             at_acc_tiles<DT>(gv, Gs, WS, s, c, h, dh);                   // dV^T += dy_att^T P
             const f32x16 dp = at_dot_tile<HALF>(Gs, WS, vr, c, h);   // dP[query][key]
 #pragma unroll
-            for (int j = 0; j < 16; ++j) s[j] = s[j] * (dp[j] - ds[at_kmap(j, h)]);
+            for (int j = 0; j < 16; ++j) s[j] = s[j] * (dp[j] - ds[sx_kmap(j, h)]);
             at_acc_tiles<DT>(gk, Qs, WS, s, c, h, dh);                   // dK^T += Q^T dS
         }
         if (!klive) continue;

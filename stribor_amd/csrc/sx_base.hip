@@ -176,7 +176,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void mvn_kernel(mvn_args a) {
         while (mvn_tri(m + 1, 0) <= tile) ++m;
         const int c = tile - mvn_tri(m, 0);
         const int g = rem >> 8, ln = (rem >> 2) & 63, j = rem & 3;
-        const int row = 32 * m + (ln & 31), col = 32 * c + cnf_kmap(4 * g + j, ln >> 5);
+        const int row = 32 * m + (ln & 31), col = 32 * c + sx_kmap(4 * g + j, ln >> 5);
         cnf_smem[e] = (row < D && col < D && col <= row) ? a.linv[(int64_t)row * D + col] : 0.f;
     }
     float *locs = cnf_smem + mvn_tri(T, 0) * 1024;

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
         for (int c = 0; c < DT; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + cnf_kmap(r, h);
+                const int f = 32 * c + sx_kmap(r, h);
                 y.v[c][r] = (live && f < D) ? a.x[row * D + f] : 0.f;
             }
         // the latent share of the first layer: W1[:, 1 + D ..] . latent_row, once per row
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
                 f32x16 lb;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * c + cnf_kmap(r, h);
+                    const int f = 32 * c + sx_kmap(r, h);
                     lb[r] = (live && f < L) ? a.latent[row * L + f] : 0.f;
                 }
 #pragma unroll
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
                     const int wr = 32 * m + (lane & 31);
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const int f = 32 * c + cnf_kmap(q, h);
+                        const int f = 32 * c + sx_kmap(q, h);
                         const float av = (wr < H1 && f < L) ? W1[(int64_t)wr * in_dim + 1 + D + f] : 0.f;
                         lat.v[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, lb[q], lat.v[m], 0, 0, 0);
                     }
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_flow_kernel(const cn_args 
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * c + cnf_kmap(r, h);
+                    const int f = 32 * c + sx_kmap(r, h);
                     if (f < D) a.y[row * D + f] = y.v[c][r];
                 }
             if (want && h == 0) a.ldj[row] = l;

@@ -128,7 +128,7 @@ __device__ __forceinline__ float ca_rms(const cnf_tile<DT> &num, const cnf_tile<
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float q = num.v[c][r] / den.v[c][r];
-            s = s + ((32 * c + cnf_kmap(r, h) < D) ? q * q : 0.f);
+            s = s + ((32 * c + sx_kmap(r, h) < D) ? q * q : 0.f);
         }
     s = s + __shfl_xor(s, 32, 64);
     return sqrtf(s / (float)D);

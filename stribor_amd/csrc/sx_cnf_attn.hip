@@ -141,7 +141,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                 f32x16 qm;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = cnf_kmap(r, h);
+                    const int f = sx_kmap(r, h);
                     qm[r] = (f >= lo && f < hi) ? z[0][r] : 0.f;
                 }
                 float m = -INFINITY, l = 0.f;
@@ -151,7 +151,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                     float tmax = -INFINITY;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        s[r] = ca_valid(p, 32 * kt + cnf_kmap(r, h), md) ? s[r] * scale : -INFINITY;
+                        s[r] = ca_valid(p, 32 * kt + sx_kmap(r, h), md) ? s[r] * scale : -INFINITY;
                         tmax = fmaxf(tmax, s[r]);
                     }
                     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -173,7 +173,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                     f32x16 s = ca_scores(qm, xk + (32 * kt + (lane & 31)) * CA_LD + 4 * h, lo, hi);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int js = 32 * kt + cnf_kmap(r, h);
+                        const int js = 32 * kt + sx_kmap(r, h);
                         s[r] = ca_valid(p, js, md) ? expf(s[r] * scale - mu) * inv : 0.f;
                         own += js == p.rho ? s[r] : 0.f;
                     }
@@ -233,7 +233,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                 float dot = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = cnf_kmap(r, h);
+                    const int f = sx_kmap(r, h);
                     const bool in = f >= lo && f < hi;
                     dot += in ? z[0][r] * zd[1][r] : 0.f;
                     s += in ? cnf_vec(pr, 0, r) * (self * zd[2][r]) : 0.f;
@@ -250,7 +250,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                 f32x16 qm, qdm;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = cnf_kmap(r, h);
+                    const int f = sx_kmap(r, h);
                     const bool in = f >= lo && f < hi;
                     qm[r] = in ? z[0][r] : 0.f;
                     qdm[r] = in ? zd[0][r] : 0.f;
@@ -263,7 +263,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                     f32x16 w = ca_scores(qdm, kb, lo, hi);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int js = 32 * kt + cnf_kmap(r, h);
+                        const int js = 32 * kt + sx_kmap(r, h);
                         const float pj = expf(sc[r] * scale - mu) * inv;
                         const float sd = w[r] * scale + (js == p.rho ? own_h : 0.f);
                         w[r] = ca_valid(p, js, md) ? pj * sd : 0.f;
@@ -274,7 +274,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const ca_pos &p, const
                 c = c + __shfl_xor(c, 32, 64);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = cnf_kmap(r, h);
+                    const int f = sx_kmap(r, h);
                     s += (f >= lo && f < hi) ? cnf_vec(pr, 0, r) * (u[r] - c * o[r]) : 0.f;
                 }
             }
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_attn_flow_kernel(const ca_
         cnf_tile<1> y;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = cnf_kmap(r, h);
+            const int f = sx_kmap(r, h);
             y.v[0][r] = !live ? 0.f : f < D ? a.x[row * D + f] : f < D + L ? a.latent[row * L + (f - D)] : 0.f;
         }
         float l = 0.f;
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_attn_flow_kernel(const ca_
             const float nan = __builtin_nanf("");
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = cnf_kmap(r, h);
+                const int f = sx_kmap(r, h);
                 if (f < D) a.y[row * D + f] = poison ? nan : y.v[0][r];
             }
             if (want && h == 0) a.ldj[row] = poison ? nan : l;

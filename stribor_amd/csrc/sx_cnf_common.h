@@ -1,12 +1,14 @@
 // What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip, sx_cnf_attn.hip) and the training
 // kernels of the dense CNF (sx_cnf_train.hip) have in common:
 //   * the layout: a workgroup of 4 waves, one wave = 32 rows on the MFMA column (lane & 31), features on the C rows, a 32-feature tile
-//     of a row = one f32x16 C fragment = the B operand of the next GEMM; feature kmap(r, h) sits in register r of lane half h;
+//     of a row = one f32x16 C fragment = the B operand of the next GEMM; feature sx_kmap(r, h) (sx_common.h) sits in register r of
+//     lane half h;
 //   * the seven activations whose derivative is a function of the activation's OUTPUT;
 //   * LDS images in A-fragment order, their staging, and the exact-fp32 product against them (v_mfma_f32_32x32x2_f32);
 //   * the fixed grid and the euler / midpoint / rk4 (3/8 rule) tableau.  The files that include this header are compiled with
 //     -ffp-contract=off: the tableau's parenthesisation is the reference solver's sequence of roundings;
-//   * the launcher and the per-call argument checks.
+//   * the per-call argument checks, and cnf_launch: sx_common.h's sx_launch_capped at this family's workgroup size and LDS limit.
+// The weight-gradient contraction of the training kernels is not here: sx_train_contract.h.
 // sx_cnf.hip and sx_cnf_train.hip take it through sx_cnf_dense.h, which adds what the two dense files share with each other alone;
 // they use all of it but cnf_act_all (sx_cnf_dense.h's sweep keeps the widest dense kernel free of spills) and cnf_latent_packed.
 // sx_cnf_exact.hip and sx_cnf_exact_set.hip take it through sx_cnf_exact_common.h, which does the same for the two exact-trace files.
@@ -19,8 +21,6 @@
 #define SX_CNF_ROWS (SX_CNF_WAVES * 32)          /* row slots of a workgroup */
 
 namespace {
-
-__host__ __device__ inline int cnf_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // tiles of 32 that hold n features (the exact-trace and set kernels cap their widths at 64 in their validators: 1 or 2 there); tiles that hold the d_h slots of every dimension, two slots (the two lane halves) per tile
 __host__ __device__ constexpr int cnf_tiles(int n) { return n <= 32 ? 1 : n <= 64 ? 2 : 4; }
@@ -94,7 +94,7 @@ __device__ __forceinline__ void cnf_stage(const float *__restrict__ W, int out_d
         const int tile = e >> 10, rem = e & 1023;
         const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
         const int m = tile / KT, c = tile - m * KT;
-        const int row = 32 * m + (lane & 31), col = 32 * c + cnf_kmap(4 * g + j, lane >> 5);
+        const int row = 32 * m + (lane & 31), col = 32 * c + sx_kmap(4 * g + j, lane >> 5);
         cnf_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * ld + col0 + col] : 0.f;
     }
 }
@@ -277,29 +277,10 @@ inline int cnf_check_call(const char *fn, int solver, int64_t n_rows, int set_si
     return SX_OK;
 }
 
-// KERN with `lds` bytes of dynamic LDS on min(want, CUs x resident blocks per CU) workgroups.  The dynamic LDS limit is raised once per
-// device and kernel (raised_on belongs to this instantiation, i.e. to KERN).  `fn`: the entry point's name, for the messages.
+// sx_common.h's launcher at this family's workgroup size and LDS limit.  `fn`: the entry point's name, for the messages.
 template <auto KERN, class A>
-int cnf_launch(const char *fn, const A &a, size_t lds, int64_t want, void *stream) {
-    static bool raised_on[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!raised_on[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, SX_CNF_LDS_BYTES);
-        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        raised_on[dev & 63] = true;
-    }
-    int cus = 0, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)KERN, SX_CNF_THREADS, lds);
-    if (cus < 1) cus = 1;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const int grid = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(KERN, dim3(grid), dim3(SX_CNF_THREADS), lds, sx_stream(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { sx_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return (int)e; }
-    return SX_OK;
+int cnf_launch(const char *fn, const A &a, size_t lds, int64_t want, void *stream, int *grid_out = nullptr) {
+    return sx_launch_capped<KERN>(fn, a, SX_CNF_THREADS, lds, SX_CNF_LDS_BYTES, want, stream, grid_out);
 }
 
 }  // namespace

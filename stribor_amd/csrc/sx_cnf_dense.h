@@ -86,7 +86,7 @@ __device__ __forceinline__ void cnf_dense_load(cnf_tile<DT> &v, const float *p, 
     for (int c = 0; c < DT; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = 32 * c + cnf_kmap(r, h);
+            const int f = 32 * c + sx_kmap(r, h);
             v.v[c][r] = (live && f < D) ? p[row * D + f] : 0.f;
         }
 }
@@ -98,7 +98,7 @@ __device__ __forceinline__ void cnf_dense_store(float *p, const cnf_tile<DT> &v,
     for (int c = 0; c < DT; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = 32 * c + cnf_kmap(r, h);
+            const int f = 32 * c + sx_kmap(r, h);
             if (f < D) p[row * D + f] = v.v[c][r];
         }
 }
@@ -119,7 +119,7 @@ __device__ __forceinline__ void cnf_dense_latent(const cnf_dense_args &a, cnf_ti
             f32x16 lb;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + cnf_kmap(r, h);
+                const int f = 32 * c + sx_kmap(r, h);
                 if (staged != nullptr) {
                     const float t = staged[(lane & 31) * L + (f < L ? f : 0)];
                     lb[r] = (live && f < L) ? t : 0.f;
@@ -132,7 +132,7 @@ __device__ __forceinline__ void cnf_dense_latent(const cnf_dense_args &a, cnf_ti
                 const int wr = 32 * m + (lane & 31);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const int f = 32 * c + cnf_kmap(q, h);
+                    const int f = 32 * c + sx_kmap(q, h);
                     const float av = (wr < H1 && f < L) ? W1[(int64_t)wr * in_dim + 1 + D + f] : 0.f;
                     lat.v[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, lb[q], lat.v[m], 0, 0, 0);
                 }

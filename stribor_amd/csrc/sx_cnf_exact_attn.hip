@@ -194,7 +194,7 @@ __device__ __forceinline__ void xa_eval(const xa_args &a, const xa_plan &p, cons
                     f32x16 qm;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int f = cnf_kmap(r, h);
+                        const int f = sx_kmap(r, h);
                         qm[r] = (f >= lo && f < hi) ? qv[r] : 0.f;
                     }
                     float m = -INFINITY, l = 0.f;
@@ -204,7 +204,7 @@ __device__ __forceinline__ void xa_eval(const xa_args &a, const xa_plan &p, cons
                         float tmax = -INFINITY;
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            s[r] = ca_valid(pos, 32 * kt + cnf_kmap(r, h), true) ? s[r] * scale : -INFINITY;
+                            s[r] = ca_valid(pos, 32 * kt + sx_kmap(r, h), true) ? s[r] * scale : -INFINITY;
                             tmax = fmaxf(tmax, s[r]);
                         }
                         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -223,7 +223,7 @@ __device__ __forceinline__ void xa_eval(const xa_args &a, const xa_plan &p, cons
                         f32x16 s = ca_scores(qm, xk + (32 * kt + (lane & 31)) * CA_LD + 4 * h - o0, lo, hi);
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
-                            s[r] = ca_valid(pos, 32 * kt + cnf_kmap(r, h), true) ? expf(s[r] * scale - mu) * inv : 0.f;
+                            s[r] = ca_valid(pos, 32 * kt + sx_kmap(r, h), true) ? expf(s[r] * scale - mu) * inv : 0.f;
                         ca_pv(o, s, xv + (32 * kt + 4 * h) * CA_LD + (lane & 31), e_in);
                     }
                 }

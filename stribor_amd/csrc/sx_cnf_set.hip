@@ -261,7 +261,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_a
         cnf_tile<1> y;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = cnf_kmap(r, h);
+            const int f = sx_kmap(r, h);
             y.v[0][r] = (live && f < D) ? a.x[row * D + f] : 0.f;
         }
         // the latent share of the first layer: A1[:, latent] . latent_row + G1[:, latent] . (the set's latent sum), once per pass
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_a
             float unused;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + cnf_kmap(r, h);
+                const int f = 32 * c + sx_kmap(r, h);
                 lb.v[0][r] = (live && f < L) ? a.latent[row * L + f] : 0.f;
             }
             cs_setsum<1, LD>(a, p, lb, ml, 0.f, unused, lane);
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_a
                 const int wr = 32 * m + (lane & 31);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const int f = 32 * c + cnf_kmap(q, h);
+                    const int f = 32 * c + sx_kmap(q, h);
                     const bool in = wr < H1 && f < L;
                     const float av = in ? net.A[0][(int64_t)wr * in_dim + 1 + D + f] : 0.f;
                     const float gv = in ? net.G[0][(int64_t)wr * in_dim + 1 + D + f] : 0.f;
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_a
         if (live) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = cnf_kmap(r, h);
+                const int f = sx_kmap(r, h);
                 if (f < D) a.y[row * D + f] = y.v[0][r];
             }
             if (want && h == 0) a.ldj[row] = l;

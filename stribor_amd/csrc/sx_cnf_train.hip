@@ -22,18 +22,22 @@
 //
 // Everything the solve has in common with sx_cnf_flow -- the staging of the forward images, the row load / store, the latent GEMM,
 // the hidden layers, the output layer, the network validator and the plan of the forward images -- is sx_cnf_dense.h's, used here
-// with one state tile and one hidden tile; this file's own are the estimate, the adjoint sweep and the partial sums.
+// with one state tile and one hidden tile.  The contraction slots (tc_put / tc_outer / tc_rowsum), the transposed stager and the
+// layout of an accumulator tile (tc_tile_off) are sx_train_contract.h's, shared with sx_resnet_bwd.hip and sx_equivariant.hip.  Every
+// row sum here is followed by a tc_put to the OTHER slot and then tc_outer's opening fence, so tc_rowsum's missing closing fence is
+// not needed (the header's fence rule).  This file's own are the estimate, the adjoint sweep and the fp32 sum of the partials, whose
+// dW_1 is assembled from three places and does not fit the shared table.
 //
 // Coverage: dim <= 32, 1 + dim + latent_dim <= 64, one or two hidden layers of <= 32 units (one tile: the adjoint sweep of a
 // two-tile hidden layer does not build without scratch, so every hidden quantity below is ONE tile), the seven activations of
 // sx_cnf_flow.
 #include "sx_cnf_dense.h"
+#include "sx_train_contract.h"
 
 #define SX_CNF_TRAIN_MAX_BLOCKS 512      /* partial slots = 4 waves x min(row blocks, this) */
 #if SX_CNF_TRAIN_MAX_HIDDEN != 32 || SX_CNF_TRAIN_MAX_DIM != 32 || SX_CNF_TRAIN_MAX_IN != 64
 #error "the kernels below are built for one hidden tile, one state tile and two latent tiles"
 #endif
-#define CT_SLOT 1056                     /* one transposed tile: 32 features x (32 rows + 1) */
 
 namespace {
 
@@ -109,24 +113,15 @@ __device__ __forceinline__ void ct_d2act_tile(const f32x16 &a, const f32x16 &d, 
     }
 }
 
-// image of W^T, one tile: float g*256 + lane*4 + j holds W[kmap(4g + j, lane >> 5)][col0 + (lane & 31)]
-__device__ __forceinline__ void ct_stage_t(const float *__restrict__ W, int out_dim, int in_dim, int ld, int col0, int base) {
-    for (int e = threadIdx.x; e < 1024; e += SX_CNF_THREADS) {
-        const int g = e >> 8, lane = (e >> 2) & 63, j = e & 3;
-        const int row = lane & 31, col = cnf_kmap(4 * g + j, lane >> 5);
-        cnf_smem[base + e] = (row < in_dim && col < out_dim) ? W[(int64_t)col * ld + col0 + row] : 0.f;
-    }
-}
-
 template <int NH>
 __device__ __forceinline__ void ct_stage_all(const ct_args &a, bool backward) {
     const sx_cnf_net &net = a.net;
     const int D = net.dim, in_dim = 1 + D + net.latent_dim, H1 = net.layer[0].out_dim, Hl = net.layer[NH - 1].out_dim;
     cnf_dense_stage<1, 1, NH>(a);
-    ct_stage_t(net.layer[NH].W, D, Hl, Hl, 0, a.base_t[NH]);
+    tc_stage_t(cnf_smem + a.base_t[NH], net.layer[NH].W, D, Hl, Hl, 0, 1, 1, SX_CNF_THREADS);
     if (backward) {
-        ct_stage_t(net.layer[0].W, H1, D, in_dim, 1, a.base_t[0]);
-        if (NH == 2) ct_stage_t(net.layer[1].W, Hl, H1, H1, 0, a.base_t[1]);
+        tc_stage_t(cnf_smem + a.base_t[0], net.layer[0].W, H1, D, in_dim, 1, 1, 1, SX_CNF_THREADS);
+        if (NH == 2) tc_stage_t(cnf_smem + a.base_t[1], net.layer[1].W, Hl, H1, H1, 0, 1, 1, SX_CNF_THREADS);
     }
 }
 
@@ -145,7 +140,7 @@ __device__ __forceinline__ float ct_estimate(const ct_args &a, const ct_tile &h1
         ct_dact_tile(h1.v[0], w.v[0], act);
 #pragma unroll
         for (int r = 0; r < 16; ++r) w.v[0][r] = w.v[0][r] * u1.v[0][r];
-        asm volatile("" ::: "memory");
+        SX_NO_HOIST();
         cnf_gemm<1, 1>(w, rr, cnf_smem + a.base_w[1] + lane * 4);
         f32x16 d2;
         ct_dact_tile(h2.v[0], d2, act);
@@ -158,7 +153,7 @@ __device__ __forceinline__ float ct_estimate(const ct_args &a, const ct_tile &h1
 // the per-row constants of a solve: u1 = W1x e, v = W_last^T e
 template <int NH>
 __device__ __forceinline__ void ct_row_constants(const ct_args &a, const ct_tile &e, ct_tile &u1, ct_tile &v, int lane) {
-    asm volatile("" ::: "memory");
+    SX_NO_HOIST();
     cnf_gemm<1, 1>(e, u1, cnf_smem + a.base_w[0] + lane * 4);
     cnf_gemm<1, 1>(e, v, cnf_smem + a.base_t[NH] + lane * 4);
 }
@@ -204,32 +199,6 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_
 }
 
 // ---- the backward ---------------------------------------------------------------------------------------------------------------
-// a tile into a scratch slot, feature-major: slot[feature * 33 + row]
-__device__ __forceinline__ void ct_put(float *slot, const f32x16 &x, int lane) {
-    const int h = lane >> 5, n = lane & 31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) slot[cnf_kmap(r, h) * 33 + n] = x[r];
-}
-
-// acc[X feature kmap(r, h)][Y feature lane & 31] += sum over the 32 rows of X Y^T, X in slot sa, Y in slot sb
-__device__ __forceinline__ void ct_outer(f32x16 &acc, const float *sa, const float *sb, int lane) {
-    const int o = (lane & 31) * 33 + (lane >> 5);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sa[o + 2 * kk], sb[o + 2 * kk], acc, 0, 0, 0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
-// feature lane & 31 of the tile in `slot` summed over rows 16 h .. 16 h + 15 (the two halves meet in the reduction)
-__device__ __forceinline__ float ct_rowsum(const float *slot, int lane) {
-    const float *p = slot + (lane & 31) * 33 + 16 * (lane >> 5);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += p[i];
-    return s;
-}
-
 // The backward moves rows between global memory and its tiles through the wave's LDS: a coalesced copy of the group's contiguous
 // block (rows row0 .. row0 + n_live - 1 of a row-major [n, ld] array, ld <= 62: at most 2 slots), then one LDS address per lane --
 // no per-element 64-bit addresses and no lane-dependent branches, which this kernel has no registers for.
@@ -266,7 +235,7 @@ __device__ __forceinline__ void ct_give(float *slot, const f32x16 &v, int ld, in
     const int h = lane >> 5, n = lane & 31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int f = c0 + cnf_kmap(r, h);
+        const int f = c0 + sx_kmap(r, h);
         slot[f < ld ? n * ld + f : spare + n] = v[r];
     }
 }
@@ -286,8 +255,8 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
     const int LT = (L + 31) >> 5;
     const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
     // the wave's scratch: two transposition slots, the stage inputs z_1 .. z_3 (also the staging area of the latent rows), e, gx
-    float *sA = cnf_smem + a.base_scr + wave * a.scr_stride, *sB = sA + CT_SLOT, *zb = sB + CT_SLOT, *sE = zb + 3 * 1024, *sY = sE + 1024;
-    float *sL = sY + CT_SLOT + lane;          // sum a1b of the group's rows (read by the latent columns only), [register][lane]
+    float *sA = cnf_smem + a.base_scr + wave * a.scr_stride, *sB = sA + SX_TC_SLOT, *zb = sB + SX_TC_SLOT, *sE = zb + 3 * 1024, *sY = sE + 1024;
+    float *sL = sY + SX_TC_SLOT + lane;          // sum a1b of the group's rows (read by the latent columns only), [register][lane]
     float *sP = zb + 2 * 1024 + lane, *sQ = zb + 1024 + lane;          // the tableau's two carried tiles, in the z slots their stages have left
     float *part = a.partial + ((int64_t)blockIdx.x * SX_CNF_WAVES + wave) * a.part_floats;
     const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
@@ -373,18 +342,18 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                 // ---- one evaluation's adjoint at (t, z) -------------------------------------------------------------------------
                 ct_tile h1, h2, a1;
                 cnf_dense_hidden<1, 1, NH, true>(a, z, t, lat, h1, h2, lane);
-                asm volatile("" ::: "memory");
+                SX_NO_HOIST();
                 if constexpr (NH == 1) {
                     ct_tile hb1, u1, v;
                     cnf_gemm<1, 1>(kb, hb1, cnf_smem + a.base_t[1] + lane * 4);
                     // dW2 += kb h1^T + e (qb d1 u1)^T, db2 += kb
-                    ct_put(sA, kb.v[0], lane);
-                    gbl += ct_rowsum(sA, lane);
-                    ct_put(sB, h1.v[0], lane);
-                    ct_outer(gWl, sA, sB, lane);
+                    tc_put(sA, kb.v[0], lane);
+                    gbl += tc_rowsum(sA, lane);
+                    tc_put(sB, h1.v[0], lane);
+                    tc_outer(gWl, sA, sB, lane);
                     ct_take(e.v[0], sE, D, 0, live, lane);
                     ct_row_constants<NH>(a, e, u1, v, lane);
-                    ct_put(sA, e.v[0], lane);
+                    tc_put(sA, e.v[0], lane);
                     f32x16 pv, d1, s1;
                     ct_dact_tile(h1.v[0], d1, act);
                     ct_d2act_tile(h1.v[0], d1, s1, act);
@@ -394,12 +363,12 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                         a1.v[0][r] = hb1.v[0][r] * d1[r] + ((qb * s1[r]) * u1.v[0][r]) * v.v[0][r];
                         u1.v[0][r] = (qb * d1[r]) * v.v[0][r];          // (the adjoint of u1)
                     }
-                    ct_put(sB, pv, lane);
-                    ct_outer(gWl, sA, sB, lane);
+                    tc_put(sB, pv, lane);
+                    tc_outer(gWl, sA, sB, lane);
                     // the u1 adjoint's share of dW1x: (qb d1 v) e^T
-                    ct_put(sB, e.v[0], lane);
-                    ct_put(sA, u1.v[0], lane);
-                    ct_outer(gW1, sA, sB, lane);
+                    tc_put(sB, e.v[0], lane);
+                    tc_put(sA, u1.v[0], lane);
+                    tc_outer(gW1, sA, sB, lane);
                 } else {
                     ct_tile w, rr, hb2, a2, rb, wb, hb1, u1, v;
                     ct_take(e.v[0], sE, D, 0, live, lane);
@@ -410,11 +379,11 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                     cnf_gemm<1, 1>(w, rr, cnf_smem + a.base_w[1] + lane * 4);
                     cnf_gemm<1, 1>(kb, hb2, cnf_smem + a.base_t[2] + lane * 4);
                     // dW3 += kb h2^T + e (qb d2 r)^T, db3 += kb
-                    ct_put(sA, kb.v[0], lane);
-                    gbl += ct_rowsum(sA, lane);
-                    ct_put(sB, h2.v[0], lane);
-                    ct_outer(gWl, sA, sB, lane);
-                    ct_put(sA, e.v[0], lane);
+                    tc_put(sA, kb.v[0], lane);
+                    gbl += tc_rowsum(sA, lane);
+                    tc_put(sB, h2.v[0], lane);
+                    tc_outer(gWl, sA, sB, lane);
+                    tc_put(sA, e.v[0], lane);
                     f32x16 pv, d2, s2;
                     ct_dact_tile(h2.v[0], d2, act);
                     ct_d2act_tile(h2.v[0], d2, s2, act);
@@ -424,18 +393,18 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                         rb.v[0][r] = (qb * v.v[0][r]) * d2[r];
                         a2.v[0][r] = hb2.v[0][r] * d2[r] + ((qb * s2[r]) * v.v[0][r]) * rr.v[0][r];
                     }
-                    ct_put(sB, pv, lane);
-                    ct_outer(gWl, sA, sB, lane);
-                    asm volatile("" ::: "memory");
+                    tc_put(sB, pv, lane);
+                    tc_outer(gWl, sA, sB, lane);
+                    SX_NO_HOIST();
                     // dW2 += a2b h1^T + rb w^T, db2 += a2b
-                    ct_put(sA, a2.v[0], lane);
-                    gb2 += ct_rowsum(sA, lane);
-                    ct_put(sB, h1.v[0], lane);
-                    ct_outer(gW2, sA, sB, lane);
-                    ct_put(sA, rb.v[0], lane);
-                    ct_put(sB, w.v[0], lane);
-                    ct_outer(gW2, sA, sB, lane);
-                    asm volatile("" ::: "memory");
+                    tc_put(sA, a2.v[0], lane);
+                    gb2 += tc_rowsum(sA, lane);
+                    tc_put(sB, h1.v[0], lane);
+                    tc_outer(gW2, sA, sB, lane);
+                    tc_put(sA, rb.v[0], lane);
+                    tc_put(sB, w.v[0], lane);
+                    tc_outer(gW2, sA, sB, lane);
+                    SX_NO_HOIST();
                     cnf_gemm<1, 1>(rb, wb, cnf_smem + a.base_t[1] + lane * 4);
                     cnf_gemm<1, 1>(a2, hb1, cnf_smem + a.base_t[1] + lane * 4);
                     f32x16 d1, s1;
@@ -448,20 +417,20 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                     }
                     // the u1 adjoint's share of dW1x: (wb d1) e^T
                     ct_take(e.v[0], sE, D, 0, live, lane);
-                    ct_put(sB, e.v[0], lane);
-                    ct_put(sA, wb.v[0], lane);
-                    ct_outer(gW1, sA, sB, lane);
+                    tc_put(sB, e.v[0], lane);
+                    tc_put(sA, wb.v[0], lane);
+                    tc_outer(gW1, sA, sB, lane);
                 }
                 // dW1x += a1b z^T, db1 += a1b, the time column += t a1b, and sum a1b for the latent columns
-                ct_put(sB, z.v[0], lane);
-                ct_put(sA, a1.v[0], lane);
-                const float s = ct_rowsum(sA, lane);
+                tc_put(sB, z.v[0], lane);
+                tc_put(sA, a1.v[0], lane);
+                const float s = tc_rowsum(sA, lane);
                 gb1 += s;
                 gtc += t * s;
-                ct_outer(gW1, sA, sB, lane);
+                tc_outer(gW1, sA, sB, lane);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sL[r * 64] += a1.v[0][r];
-                asm volatile("" ::: "memory");
+                SX_NO_HOIST();
                 cnf_gemm<1, 1>(a1, zbar, cnf_smem + a.base_t[0] + lane * 4);
 
                 if (SOLVER == SX_CNF_EULER || st == 0) {
@@ -499,7 +468,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
                     const int lc = 32 * c + (lane & 31);
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const int j = cnf_kmap(q, h);
+                        const int j = sx_kmap(q, h);
                         const float t = W1[(int64_t)(j < H1 ? j : 0) * in_dim + 1 + D + (lc < L ? lc : 0)];
                         const float av = (lc < L && j < H1) ? t : 0.f;
                         g = __builtin_amdgcn_mfma_f32_32x32x2f32(av, A1[q], g, 0, 0, 0);
@@ -513,12 +482,12 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_bwd_kernel(const ct_
             for (int c = 0; c < LT; ++c) {
                 f32x16 lt, acc;
                 ct_take(lt, zb, L, 32 * c, live, lane);
-                ct_put(sB, lt, lane);
+                tc_put(sB, lt, lane);
                 float *p = part + a.off_lat + c * 1024 + lane;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = p[r * 64];
-                ct_put(sA, A1, lane);
-                ct_outer(acc, sA, sB, lane);
+                tc_put(sA, A1, lane);
+                tc_outer(acc, sA, sB, lane);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) p[r * 64] = acc[r];
             }
@@ -551,9 +520,6 @@ struct ct_reduce_args {
     int off_w2, off_wl, off_lat, off_vec;
 };
 
-// float offset of element [X feature fx][Y feature fy] inside an accumulator tile as the backward wrote it
-__device__ __forceinline__ int ct_tile_off(int fx, int fy) { return ((fx & 3) + 4 * (fx >> 3)) * 64 + fy + 32 * ((fx >> 2) & 1); }
-
 __global__ void cnf_train_reduce_kernel(const ct_reduce_args a) {
     const int in_dim = 1 + a.D + a.L, Hl = a.NH == 1 ? a.H1 : a.H2;
     const int n0 = a.H1 * in_dim, n1 = a.H1, n2 = a.NH == 2 ? a.H2 * a.H1 : 0, n3 = a.NH == 2 ? a.H2 : 0, n4 = a.D * Hl, n5 = a.D;
@@ -564,18 +530,18 @@ __global__ void cnf_train_reduce_kernel(const ct_reduce_args a) {
         const int j = i / in_dim, c = i - j * in_dim;
         dst = a.dW[0];
         if (c == 0) { off = a.off_vec + 64 + j; pair = 1; }
-        else if (c <= a.D) off = ct_tile_off(j, c - 1);
-        else off = a.off_lat + ((c - 1 - a.D) >> 5) * 1024 + ct_tile_off(j, (c - 1 - a.D) & 31);
+        else if (c <= a.D) off = tc_tile_off(j, c - 1);
+        else off = a.off_lat + ((c - 1 - a.D) >> 5) * 1024 + tc_tile_off(j, (c - 1 - a.D) & 31);
     } else if ((i -= n0) < n1) {
         dst = a.db[0]; off = a.off_vec + i; pair = 1;
     } else if ((i -= n1) < n2) {
         const int k = i / a.H1, j = i - k * a.H1;
-        dst = a.dW[1]; off = a.off_w2 + ct_tile_off(k, j);
+        dst = a.dW[1]; off = a.off_w2 + tc_tile_off(k, j);
     } else if ((i -= n2) < n3) {
         dst = a.db[1]; off = a.off_vec + 128 + i; pair = 1;
     } else if ((i -= n3) < n4) {
         const int d = i / Hl, j = i - d * Hl;
-        dst = a.dW[a.NH]; off = a.off_wl + ct_tile_off(d, j);
+        dst = a.dW[a.NH]; off = a.off_wl + tc_tile_off(d, j);
     } else if ((i -= n4) < n5) {
         dst = a.db[a.NH]; off = a.off_vec + 192 + i; pair = 1;
     } else return;
@@ -599,7 +565,7 @@ size_t ct_plan(const sx_cnf_net &net, bool backward, ct_args &a) {
     if (backward) {
         a.base_t[0] = (int)off; off += 1024;
         if (NH == 2) { a.base_t[1] = (int)off; off += 1024; }
-        a.base_scr = (int)off; a.scr_stride = 3 * CT_SLOT + 5 * 1024;
+        a.base_scr = (int)off; a.scr_stride = 3 * SX_TC_SLOT + 5 * 1024;
         off += (size_t)SX_CNF_WAVES * a.scr_stride;
     }
     a.off_w2 = 1024;

@@ -32,6 +32,39 @@ void sx_set_error(const char *fmt, ...);
     } while (0)
 
 static inline hipStream_t sx_stream(void *s) { return (hipStream_t)s; }
+static inline bool sx_aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+
+// The 32x32 C fragment of the MFMAs (v_mfma_f32_32x32x2_f32 and its kin): register r of lane half h holds feature sx_kmap(r, h)
+// of row lane & 31.  THE definition for every kernel that keeps rows on the MFMA column.
+__host__ __device__ static inline int sx_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// KERN(a) with `lds` bytes of dynamic LDS on min(want, CUs x resident workgroups per CU) workgroups of `threads` threads; the grid
+// goes to *grid_out when given.  The dynamic LDS limit is raised to lds_limit once per device and kernel (raised_on belongs to this
+// instantiation, i.e. to KERN).  `fn`: the entry point's name, for the messages.
+template <auto KERN, class A>
+static int sx_launch_capped(const char *fn, const A &a, int threads, size_t lds, int lds_limit, int64_t want, void *stream,
+                            int *grid_out = nullptr) {
+    static bool raised_on[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!raised_on[dev & 63]) {
+        hipError_t e = hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+        raised_on[dev & 63] = true;
+    }
+    int cus = 0, per_cu = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)KERN, threads, lds);
+    if (cus < 1) cus = 1;
+    if (per_cu < 1) per_cu = 1;
+    const int64_t cap = (int64_t)cus * per_cu;
+    const int grid = (int)(want < cap ? want : cap);
+    if (grid_out != nullptr) *grid_out = grid;
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), lds, sx_stream(stream), a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { sx_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return (int)e; }
+    return SX_OK;
+}
 
 // ---- bf16 <-> f32 (storage only; all arithmetic is fp32) --------------------------------------
 __device__ __forceinline__ float bf16_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }

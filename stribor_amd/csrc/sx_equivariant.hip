@@ -25,16 +25,16 @@
 //     dB_l = sum_sets r_l S_{l-1}^T,  db_l = sum_sets r_l,   dh_{l-1,i} = A_l^T (m_i e_l,i) + B_l^T r_l,   e_{l-1} = act'(h_{l-1}) dh_{l-1}
 // One launch recomputes h_l from x (the forward saves nothing), walks the layers down with transpose products from transposed
 // images staged once per workgroup, exchanges r_l through the same scratch, and contracts dA, da, dB, db over its rows with the
-// same MFMA (sx_resnet_bwd.hip's scheme: both operands turn through two per-wave LDS slots, feature-major; dB's row operand is r on
-// the FIRST row of each set and zero elsewhere).  A wave owns one partial and accumulates into it in place: the first pass writes,
-// later passes add, so nothing needs a zero-fill and no two waves touch the same word.  equivariant_reduce_kernel then sums the
-// partials in slot order: no atomics, and two calls on the same inputs give the same bits.
+// same MFMA (sx_train_contract.h, shared with sx_cnf_train.hip and sx_resnet_bwd.hip: both operands turn through two per-wave LDS
+// slots, feature-major; dB's row operand is r on the FIRST row of each set and zero elsewhere).  A wave owns one partial and
+// accumulates into it in place: the first pass writes, later passes add, so nothing needs a zero-fill and no two waves touch the
+// same word.  tc_reduce_kernel then sums the partials in slot order: no atomics, and two calls on the same inputs give the same bits.
+// From sx_train_contract.h: the slots, tc_put / tc_add_tile / tc_add_rowsum, the transposed stager and the ordered sum; this file's
+// own: eq_contract's loop nest over operands held in registers.  Both launches are cnf_launch.
 #include "sx_cnf_common.h"
+#include "sx_train_contract.h"
 
 #define SX_EQ_BWD_MAX_BLOCKS 512         /* partial slots = 4 waves x min(passes, this) */
-#define EQ_SLOT 1056                     /* one transposed tile: 32 features x (32 rows + 1) */
-// (keeps the loop-invariant LDS weight loads beside their MFMAs: without it the compiler holds whole matrices in registers)
-#define EQ_NO_HOIST() asm volatile("" ::: "memory")
 // the backward's instantiations (input tiles, hidden tiles, output tiles, layers): every shape within SX_EQUIVARIANT_BWD_MAX_* whose
 // forward and transposed images all fit SX_CNF_LDS_BYTES beside the scratch and the slots (eq_bwd_resident)
 #define EQ_BWD_CASES EQ_CASE(1, 1, 1, 2) EQ_CASE(1, 1, 2, 2) EQ_CASE(1, 2, 1, 2) EQ_CASE(1, 1, 1, 3) EQ_CASE(1, 1, 2, 3)
@@ -139,27 +139,6 @@ __device__ __forceinline__ void eq_mma_t(f32x16 &acc, const cnf_tile<KT> &e, int
     cnf_mma<KT>(acc, e, cnf_smem + base + m * KT * 1024 + lane * 4);
 }
 
-// An address that is the same in every pass would be computed once, outside the pass loop, and kept: two registers per word.  One
-// that passes through here is rebuilt where it is used.
-template <class T>
-__device__ __forceinline__ T *eq_here(T *p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
-// image of W^T: MT x KT tiles (MT: the layer's INPUT tiles, KT: its output tiles); tile (m, c), float g*256 + lane*4 + j holds
-// W[32c + kmap(4g + j, lane >> 5)][32m + (lane & 31)]
-__device__ __forceinline__ void eq_stage_t(const float *__restrict__ W, int out_dim, int in_dim, int MT, int KT, int base) {
-    const int n_w = MT * KT * 1024;
-    for (int e = threadIdx.x; e < n_w; e += SX_CNF_THREADS) {
-        const int tile = e >> 10, rem = e & 1023;
-        const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
-        const int m = tile / KT, c = tile - m * KT;
-        const int col = 32 * m + (lane & 31), row = 32 * c + cnf_kmap(4 * g + j, lane >> 5);
-        cnf_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * in_dim + col] : 0.f;
-    }
-}
-
 // tiles of layer l: KT inputs, MT outputs (NL layers; KT0 / HT / OT: input, hidden and output tiles of the net)
 __host__ __device__ inline int eq_kt(int l, int KT0, int HT) { return l == 0 ? KT0 : HT; }
 __host__ __device__ inline int eq_mt(int l, int NL, int HT, int OT) { return l == NL - 1 ? OT : HT; }
@@ -173,8 +152,8 @@ __device__ __forceinline__ void eq_stage(const eq_args &a, int KT0, int HT, int 
         cnf_stage_vec(net.a[l], out, 1, MT * 32, a.base_va[l]);
         cnf_stage_vec(net.b[l], out, 1, MT * 32, a.base_vb[l]);
         if (backward) {
-            if (a.base_at[l] >= 0) eq_stage_t(net.A[l], out, in, KT, MT, a.base_at[l]);
-            if (a.base_bt[l] >= 0) eq_stage_t(net.B[l], out, in, KT, MT, a.base_bt[l]);
+            if (a.base_at[l] >= 0) tc_stage_t(cnf_smem + a.base_at[l], net.A[l], out, in, in, 0, KT, MT, SX_CNF_THREADS);
+            if (a.base_bt[l] >= 0) tc_stage_t(cnf_smem + a.base_bt[l], net.B[l], out, in, in, 0, KT, MT, SX_CNF_THREADS);
         }
     }
 }
@@ -183,7 +162,7 @@ __device__ __forceinline__ void eq_stage(const eq_args &a, int KT0, int HT, int 
 template <int KT, bool G>
 __device__ __forceinline__ void eq_z(const eq_args &a, int l, int m, const cnf_tile<KT> &hin, const cnf_tile<KT> &S, const eq_row &p, f32x16 &z,
                                      int lane) {
-    EQ_NO_HOIST();
+    SX_NO_HOIST();
     const int h = lane >> 5, in = eq_in_dim(a.net, l), out = a.net.out_dim[l];
     f32x16 u = {}, v = {};
     eq_mma<KT, G>(u, hin, a.base_a[l], m, a.net.A[l], out, in, lane);
@@ -221,7 +200,7 @@ __device__ __forceinline__ void eq_begin(const eq_args &a, int64_t pass, eq_row 
     for (int c = 0; c < KT0; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = 32 * c + cnf_kmap(r, h);
+            const int f = 32 * c + sx_kmap(r, h);
             x.v[c][r] = (p.live && f < D) ? xr[f] : 0.f;
         }
     p.mi = (a.mask != nullptr && p.live) ? a.mask[p.row * a.mask_rs] : 1.f;
@@ -262,7 +241,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_fwd_kernel(const e
             if (p.live) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * m + cnf_kmap(r, h);
+                    const int f = 32 * m + sx_kmap(r, h);
                     if (f < out_dim) yr[f] = cnf_act(z[r], fact);
                 }
             }
@@ -271,33 +250,6 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_fwd_kernel(const e
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------
-// a tile into a contraction slot, feature-major: slot[feature * 33 + row]
-__device__ __forceinline__ void eq_put(float *slot, const f32x16 &x, int lane) {
-    const int h = lane >> 5, n = lane & 31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) slot[cnf_kmap(r, h) * 33 + n] = x[r];
-}
-
-// acc[X feature kmap(r, h)][Y feature lane & 31] += sum over the wave's 32 rows of X Y^T, X in slot sa, Y in slot sb
-__device__ __forceinline__ void eq_outer(f32x16 &acc, const float *sa, const float *sb, int lane) {
-    const int o = (lane & 31) * 33 + (lane >> 5);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sa[o + 2 * kk], sb[o + 2 * kk], acc, 0, 0, 0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
-// feature lane & 31 of the tile in `slot` summed over rows 16 h .. 16 h + 15 (the two halves meet in the reduction)
-__device__ __forceinline__ float eq_rowsum(const float *slot, int lane) {
-    const float *p = slot + (lane & 31) * 33 + 16 * (lane >> 5);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += p[i];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    return s;
-}
-
 // W += X Y^T and v += sum X over the wave's 32 rows, into the wave's partial (pw: MT x KT tiles, pv: MT x 64 floats)
 template <int MT, int KT>
 __device__ __forceinline__ void eq_contract(const cnf_tile<MT> &X, const cnf_tile<KT> &Y, float *pw, float *pv, bool want_w, bool want_v, bool first,
@@ -305,32 +257,22 @@ __device__ __forceinline__ void eq_contract(const cnf_tile<MT> &X, const cnf_til
     if (want_w) {
 #pragma unroll
         for (int c = 0; c < KT; ++c) {
-            EQ_NO_HOIST();
-            eq_put(sB, Y.v[c], lane);
+            SX_NO_HOIST();
+            tc_put(sB, Y.v[c], lane);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                EQ_NO_HOIST();
-                eq_put(sA, X.v[m], lane);
-                float *dst = eq_here(pw + (m * KT + c) * 1024 + lane);
-                f32x16 acc = {};
-                if (!first) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = dst[r * 64];
-                }
-                eq_outer(acc, sA, sB, lane);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
+                SX_NO_HOIST();
+                tc_put(sA, X.v[m], lane);
+                tc_add_tile(pw + (m * KT + c) * 1024 + lane, sA, sB, first, lane);
             }
         }
     }
     if (want_v) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            EQ_NO_HOIST();
-            eq_put(sA, X.v[m], lane);
-            const float sum = eq_rowsum(sA, lane);
-            float *dst = eq_here(pv + m * 64 + lane);
-            *dst = first ? sum : *dst + sum;
+            SX_NO_HOIST();
+            tc_put(sA, X.v[m], lane);
+            tc_add_rowsum(pv + m * 64 + lane, sA, first, lane);
         }
     }
 }
@@ -368,7 +310,7 @@ __device__ __forceinline__ void eq_bwd_layer(const eq_args &a, int l, const eq_r
     if (want_dh) {
 #pragma unroll
         for (int m = 0; m < KT; ++m) {
-            EQ_NO_HOIST();
+            SX_NO_HOIST();
             f32x16 acc = {};
             eq_mma_t<MT>(acc, e, a.base_at[l], m, lane);
             eq_mma_t<MT>(acc, r, a.base_bt[l], m, lane);
@@ -392,7 +334,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
     eq_stage(a, KT0, HT, OT, true);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-    float *sA = cnf_smem + a.base_scr + wave * 2 * EQ_SLOT, *sB = sA + EQ_SLOT;
+    float *sA = cnf_smem + a.base_scr + wave * 2 * SX_TC_SLOT, *sB = sA + SX_TC_SLOT;
     float *part = a.partial + ((int64_t)blockIdx.x * SX_CNF_WAVES + wave) * a.part_floats;
     const int rows_per_pass = cnf_rows_per_pass(a.net.set_size);
     const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
@@ -416,14 +358,14 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
         eq_setsum<HT, LD>(a, p, hl, Sl, 0.f, unused, lane);
         // ---- e_L = final_act'(y) gy (zero on padding rows and padded features)
         cnf_tile<OT> e;
-        const float *gr = eq_here(a.gy + p.row * out_dim);
+        const float *gr = tc_here(a.gy + p.row * out_dim);
 #pragma unroll
         for (int m = 0; m < OT; ++m) {
             f32x16 z;
             eq_z<HT, false>(a, NL - 1, m, hl, Sl, p, z, lane);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * m + cnf_kmap(r, h);
+                const int f = 32 * m + sx_kmap(r, h);
                 e.v[m][r] = (p.live && f < out_dim) ? cnf_dact(cnf_act(z[r], fact), fact) * gr[f] : 0.f;
             }
         }
@@ -441,12 +383,12 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
         if (a.want_b[0]) eq_setsum<KT0, LD>(a, p, x, S0, 0.f, unused, lane);
         eq_bwd_layer<KT0, HT, LD>(a, 0, p, dh, x, S0, dx, a.dx != nullptr, part, first, sA, sB, lane);
         if (a.dx != nullptr && p.live) {
-            float *dr = eq_here(a.dx + p.row * D);
+            float *dr = tc_here(a.dx + p.row * D);
 #pragma unroll
             for (int m = 0; m < KT0; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * m + cnf_kmap(r, h);
+                    const int f = 32 * m + sx_kmap(r, h);
                     if (f < D) dr[f] = dx.v[m][r];
                 }
         }
@@ -454,41 +396,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
     }
 }
 
-// ---- the partial sum: one thread per gradient element, the slots in order -------------------------------------------------------
-struct eq_reduce_args {
-    const float *partial;
-    float *dst[12];                    // per layer: dA, da, dB, db
-    int rows[12], cols[12], kt[12], off[12];       // cols == 0: a vector of `rows` entries
-    int n_slots, part_floats;
-};
-
-// float offset of element [X feature fx][Y feature fy] (both < 32) inside an accumulator tile as eq_contract wrote it
-__device__ __forceinline__ int eq_tile_off(int fx, int fy) { return ((fx & 3) + 4 * (fx >> 3)) * 64 + fy + 32 * ((fx >> 2) & 1); }
-
-__global__ void equivariant_reduce_kernel(const eq_reduce_args a) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int k = 0; k < 12; ++k) {
-        const int n = a.cols[k] ? a.rows[k] * a.cols[k] : a.rows[k];
-        if (i >= n) { i -= n; continue; }
-        if (a.dst[k] == nullptr) return;
-        int off;
-        if (a.cols[k]) {
-            const int fx = i / a.cols[k], fy = i - fx * a.cols[k];
-            off = a.off[k] + ((fx >> 5) * a.kt[k] + (fy >> 5)) * 1024 + eq_tile_off(fx & 31, fy & 31);
-        } else {
-            off = a.off[k] + (i >> 5) * 64 + (i & 31);
-        }
-        double s = 0.0;                 // up to 2048 slots in a row: the sum is carried in fp64 and rounded once
-        const float *p = a.partial + off;
-        for (int q = 0; q < a.n_slots; ++q, p += a.part_floats) s += a.cols[k] ? (double)p[0] : (double)p[0] + (double)p[32];
-        a.dst[k][i] = (float)s;
-        return;
-    }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-inline bool eq_aligned(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-
 // the shape of the network alone (no pointer is read)
 int eq_check_shape(const char *fn, const sx_equivariant_net *net_host, bool backward) {
     SX_REQUIRE(net_host != nullptr, "%s: null network", fn);
@@ -534,7 +442,7 @@ size_t eq_plan(const sx_equivariant_net &net, bool backward, eq_args &a) {
     if (backward && OT > XT) XT = OT;
     a.base_x = (int)off; off += (size_t)SX_CNF_ROWS * (32 * XT + 4);
     a.base_scr = (int)off;
-    if (backward) off += (size_t)SX_CNF_WAVES * 2 * EQ_SLOT;
+    if (backward) off += (size_t)SX_CNF_WAVES * 2 * SX_TC_SLOT;
     for (int l = 0; l < 3; ++l) a.base_a[l] = a.base_b[l] = a.base_at[l] = a.base_bt[l] = -1;
     for (int l = 0; l < NL; ++l) {
         const size_t img = (size_t)eq_mt(l, NL, HT, OT) * eq_kt(l, KT0, HT) * 1024;
@@ -566,40 +474,15 @@ int64_t eq_bwd_blocks(int64_t n_rows, int set_size) {
 int eq_check_call(const char *fn, const sx_equivariant_net &net, const float *x, int64_t x_rs, const float *mask, int64_t mask_rs, int64_t n_rows) {
     for (int l = 0; l < net.n_layers; ++l) {
         SX_REQUIRE(net.A[l] != nullptr && net.a[l] != nullptr && net.B[l] != nullptr && net.b[l] != nullptr, "%s: layer %d lacks a weight or a bias", fn, l);
-        SX_REQUIRE(eq_aligned(net.A[l]) && eq_aligned(net.a[l]) && eq_aligned(net.B[l]) && eq_aligned(net.b[l]),
+        SX_REQUIRE(sx_aligned4(net.A[l]) && sx_aligned4(net.a[l]) && sx_aligned4(net.B[l]) && sx_aligned4(net.b[l]),
                    "%s: layer %d has a pointer that is not 4-byte aligned", fn, l);
     }
     SX_REQUIRE(n_rows >= 0, "%s: negative n_rows", fn);
     SX_REQUIRE(n_rows % net.set_size == 0, "%s: n_rows (%lld) is not a multiple of set_size (%d)", fn, (long long)n_rows, net.set_size);
-    SX_REQUIRE(x != nullptr && eq_aligned(x), "%s: x is null or not 4-byte aligned", fn);
+    SX_REQUIRE(x != nullptr && sx_aligned4(x), "%s: x is null or not 4-byte aligned", fn);
     SX_REQUIRE(x_rs >= net.in_dim, "%s: the row stride of x (%lld) is below in_dim (%d)", fn, (long long)x_rs, net.in_dim);
-    SX_REQUIRE(mask == nullptr || (eq_aligned(mask) && mask_rs >= 1), "%s: the mask is not 4-byte aligned, or its row stride (%lld) is below 1", fn,
+    SX_REQUIRE(mask == nullptr || (sx_aligned4(mask) && mask_rs >= 1), "%s: the mask is not 4-byte aligned, or its row stride (%lld) is below 1", fn,
                (long long)mask_rs);
-    return SX_OK;
-}
-
-// the backward launcher: cnf_launch, handing the grid back (the reduce needs the number of partials written)
-template <auto KERN>
-int eq_launch_bwd(const eq_args &a, size_t lds, int64_t want, int *grid_out, void *stream) {
-    static bool raised_on[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!raised_on[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, SX_CNF_LDS_BYTES);
-        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        raised_on[dev & 63] = true;
-    }
-    int cus = 0, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)KERN, SX_CNF_THREADS, lds);
-    if (cus < 1) cus = 1;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const int grid = (int)(want < cap ? want : cap);
-    *grid_out = grid;
-    hipLaunchKernelGGL(KERN, dim3(grid), dim3(SX_CNF_THREADS), lds, sx_stream(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { sx_set_error("sx_equivariant_bwd: launch failed: %s", hipGetErrorString(e)); return (int)e; }
     return SX_OK;
 }
 
@@ -628,7 +511,7 @@ extern "C" int sx_equivariant_fwd(const sx_equivariant_net *net_host, const floa
     const sx_equivariant_net &net = *net_host;
     const int rc_call = eq_check_call(fn, net, x, x_rs, mask, mask_rs, n_rows);
     if (rc_call != SX_OK) return rc_call;
-    SX_REQUIRE(y != nullptr && eq_aligned(y), "%s: y is null or not 4-byte aligned", fn);
+    SX_REQUIRE(y != nullptr && sx_aligned4(y), "%s: y is null or not 4-byte aligned", fn);
     eq_args a{};
     a.net = net;
     const size_t lds = eq_plan(net, false, a) * 4;
@@ -655,8 +538,8 @@ extern "C" int sx_equivariant_bwd(const sx_equivariant_net *net_host, const floa
     const sx_equivariant_net &net = *net_host;
     const int rc_call = eq_check_call(fn, net, x, x_rs, mask, mask_rs, n_rows);
     if (rc_call != SX_OK) return rc_call;
-    SX_REQUIRE(gy != nullptr && eq_aligned(gy), "%s: gy is null or not 4-byte aligned", fn);
-    SX_REQUIRE(eq_aligned(dx) && eq_aligned(partial), "%s: dx or the partial buffer is not 4-byte aligned", fn);
+    SX_REQUIRE(gy != nullptr && sx_aligned4(gy), "%s: gy is null or not 4-byte aligned", fn);
+    SX_REQUIRE(sx_aligned4(dx) && sx_aligned4(partial), "%s: dx or the partial buffer is not 4-byte aligned", fn);
     eq_args a{};
     a.net = net;
     const size_t lds = eq_plan(net, true, a) * 4;
@@ -665,23 +548,21 @@ extern "C" int sx_equivariant_bwd(const sx_equivariant_net *net_host, const floa
     int KT0, HT, OT;
     eq_tiles(net, KT0, HT, OT);
     const int NL = net.n_layers;
-    eq_reduce_args r{};
+    tc_reduce_args<12> r{};              // per layer: dA, da, dB, db
     bool any = false;
     int total = 0;
     for (int l = 0; l < NL; ++l) {
         float *g[4] = {nullptr, nullptr, nullptr, nullptr};
         if (grads != nullptr) { g[0] = grads->dA[l]; g[1] = grads->da[l]; g[2] = grads->dB[l]; g[3] = grads->db[l]; }
+        const int off[4] = {a.off_a[l], a.off_va[l], a.off_b[l], a.off_vb[l]};
         for (int k = 0; k < 4; ++k) {
-            SX_REQUIRE(eq_aligned(g[k]), "%s: a gradient of layer %d is not 4-byte aligned", fn, l);
+            SX_REQUIRE(sx_aligned4(g[k]), "%s: a gradient of layer %d is not 4-byte aligned", fn, l);
             any = any || g[k] != nullptr;
-            r.dst[4 * l + k] = g[k];
-            r.rows[4 * l + k] = net.out_dim[l];
-            r.cols[4 * l + k] = (k & 1) ? 0 : (l == 0 ? net.in_dim : net.out_dim[l - 1]);
-            r.kt[4 * l + k] = eq_kt(l, KT0, HT);
-            total += r.rows[4 * l + k] * ((k & 1) ? 1 : r.cols[4 * l + k]);
+            const int cols = (k & 1) ? 0 : (l == 0 ? net.in_dim : net.out_dim[l - 1]);
+            r.e[4 * l + k] = {g[k], net.out_dim[l], cols, eq_kt(l, KT0, HT), off[k]};
+            total += net.out_dim[l] * ((k & 1) ? 1 : cols);
         }
         a.want_a[l] = g[0] != nullptr; a.want_va[l] = g[1] != nullptr; a.want_b[l] = g[2] != nullptr; a.want_vb[l] = g[3] != nullptr;
-        r.off[4 * l] = a.off_a[l]; r.off[4 * l + 1] = a.off_va[l]; r.off[4 * l + 2] = a.off_b[l]; r.off[4 * l + 3] = a.off_vb[l];
     }
     SX_REQUIRE(any || dx != nullptr, "%s: nothing to compute (no dx and no parameter gradient)", fn);
     SX_REQUIRE(!any || n_rows == 0 || partial != nullptr, "%s: the partial buffer is missing (sx_equivariant_bwd_partial_floats)", fn);
@@ -690,7 +571,7 @@ extern "C" int sx_equivariant_bwd(const sx_equivariant_net *net_host, const floa
         a.x = x; a.x_rs = x_rs; a.mask = mask; a.mask_rs = mask_rs; a.gy = gy; a.dx = dx; a.partial = partial; a.n_rows = n_rows;
         const int64_t want = eq_bwd_blocks(n_rows, net.set_size);
         int rc_k = SX_E_UNSUPPORTED;
-#define EQ_CASE(K_, H_, O_, N_) if (KT0 == K_ && HT == H_ && OT == O_ && NL == N_) rc_k = eq_launch_bwd<equivariant_bwd_kernel<K_, H_, O_, N_>>(a, lds, want, &grid, stream);
+#define EQ_CASE(K_, H_, O_, N_) if (KT0 == K_ && HT == H_ && OT == O_ && NL == N_) rc_k = cnf_launch<equivariant_bwd_kernel<K_, H_, O_, N_>>(fn, a, lds, want, stream, &grid);
         EQ_BWD_CASES
 #undef EQ_CASE
         if (rc_k == SX_E_UNSUPPORTED) sx_set_error("%s: no kernel for %d / %d / %d tiles, %d layers", fn, KT0, HT, OT, NL);
@@ -699,8 +580,5 @@ extern "C" int sx_equivariant_bwd(const sx_equivariant_net *net_host, const floa
     if (!any) return SX_OK;
     // every wave of every workgroup launched wrote its slot on its first pass (no rows: no slots, the gradients are zero)
     r.partial = partial; r.part_floats = a.part_floats; r.n_slots = grid * SX_CNF_WAVES;
-    hipLaunchKernelGGL(equivariant_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, sx_stream(stream), r);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { sx_set_error("%s: reduce launch failed: %s", fn, hipGetErrorString(err)); return (int)err; }
-    return SX_OK;
+    return tc_reduce(fn, r, total, stream);
 }

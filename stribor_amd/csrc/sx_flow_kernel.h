@@ -46,8 +46,6 @@
 #endif
 namespace SX_PREC_NS {
 
-__host__ __device__ static inline int sx_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 extern __shared__ __attribute__((aligned(16))) float smem[];
 
 typedef __attribute__((address_space(3))) void lds_void;

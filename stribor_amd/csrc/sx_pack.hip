@@ -8,8 +8,6 @@
 // weight column kmap(s,h).  That permutation is baked in here, once per parameter update.
 #include "sx_common.h"
 
-__host__ __device__ static inline int sx_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 // the library's default GEMM arithmetic (both are built in; sx_pack_linear / sx_flow_run take `precision`)
 extern "C" int sx_fragment_mode(void) { return SX_GEMM_F16X3; }
 

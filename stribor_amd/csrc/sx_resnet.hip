@@ -89,7 +89,7 @@ __global__ __launch_bounds__(SX_RESNET_THREADS) void resnet_flow_kernel(const rn
         for (int c = 0; c < DT; ++c) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = 32 * c + rn_kmap(r, h);
+                const int f = 32 * c + sx_kmap(r, h);
                 const bool ok = live && f < D;
                 y.v[c][r] = ok ? a.in[row * D + f] : 0.f;
                 s.v[c][r] = !ok ? 0.f : a.time_kind == SX_RESNET_TIME_NONE ? 1.f : rn_time(a, row, f, tv);
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(SX_RESNET_THREADS) void resnet_flow_kernel(const rn
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int f = 32 * c + rn_kmap(r, h);
+                    const int f = 32 * c + sx_kmap(r, h);
                     if (f < D) a.out[row * D + f] = x.v[c][r];
                 }
         }
@@ -180,31 +180,6 @@ __global__ __launch_bounds__(SX_RESNET_THREADS) void spectral_sigma_kernel(const
 }
 
 inline int rn_tiles(int n) { return n <= 32 ? 1 : n <= 64 ? 2 : 4; }
-
-template <int DT, int HT>
-int rn_launch(const rn_args &a, size_t lds, void *stream) {
-    auto kern = resnet_flow_kernel<DT, HT>;
-    static bool raised_on[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!raised_on[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SX_RESNET_LDS_BYTES);
-        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        raised_on[dev & 63] = true;
-    }
-    int cus = 0, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, SX_RESNET_THREADS, lds);
-    if (cus < 1) cus = 1;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t n_groups = (a.n_rows + 31) / 32;
-    const int64_t want = (n_groups + SX_RESNET_WAVES - 1) / SX_RESNET_WAVES;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const int grid = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SX_RESNET_THREADS), lds, sx_stream(stream), a);
-    SX_LAUNCH_CHECK();
-    return SX_OK;
-}
 
 }  // namespace
 
@@ -272,7 +247,8 @@ extern "C" int sx_resnet_flow(const sx_resnet_net *net_host, const float *in, fl
     a.in = in; a.out = out; a.n_rows = n_rows; a.t = t; a.s_rows = s_rows; a.time_a = time_a; a.time_b = time_b;
     a.sigma = sigma; a.time_kind = time_kind; a.time_hidden = time_hidden; a.sigma_rows = sigma_rows;
     a.iterations = iterations; a.inverse = inverse ? 1 : 0; a.lds_floats = off;
-#define RN_CASE(D_, H_) if (DT == D_ && HT == H_) return rn_launch<D_, H_>(a, lds, stream);
+    const int64_t want = ((n_rows + 31) / 32 + SX_RESNET_WAVES - 1) / SX_RESNET_WAVES;
+#define RN_CASE(D_, H_) if (DT == D_ && HT == H_) return sx_launch_capped<resnet_flow_kernel<D_, H_>>("sx_resnet_flow", a, SX_RESNET_THREADS, lds, SX_RESNET_LDS_BYTES, want, stream);
     RN_CASE(1, 1) RN_CASE(1, 2) RN_CASE(1, 4) RN_CASE(2, 1) RN_CASE(2, 2) RN_CASE(2, 4) RN_CASE(4, 1) RN_CASE(4, 2) RN_CASE(4, 4)
 #undef RN_CASE
     sx_set_error("sx_resnet_flow: no kernel for %d x %d tiles", DT, HT);

@@ -8,7 +8,7 @@
 //   inverse != 0 (the implicit backward at x = x*):     w_0 = gin, w_{k+1} = gin - J_r(x*)^T w_k, `iterations` times;
 //                                                       gout = w_K;  G, db, gs at c = -w_K
 // Layout and arithmetic are sx_resnet.hip's (sx_resnet_common.h): one wave = 32 rows on the MFMA column, features on the C rows
-// in rn_kmap order, exact fp32 v_mfma_f32_32x32x2_f32, grid-stride over 32-row groups.  Per group a wave
+// in sx_kmap order, exact fp32 v_mfma_f32_32x32x2_f32, grid-stride over 32-row groups.  Per group a wave
 //   * recomputes a_l, h_l at x once (nothing is saved by the forward) and forms d_l once -- from the output where the output
 //     determines it, from the pre-activation for SiLU and GELU; s is folded into d_L;
 //   * runs the `iterations` transpose products from registers: a C tile of e_l is the B operand of W_l^T, whose A fragments come
@@ -19,8 +19,11 @@
 // waits in the gs rows: the iteration's registers hold only gin, w, d_L (.) s and the d_l.
 // A wave owns one partial (slot = 4 * block + wave).  The partial is the accumulator: the wave's first group writes it, each later
 // group adds to it in place (twelve accumulator tiles of a 64 / [64, 64] network do not fit the register file beside the sweep's
-// state), so nothing needs a zero-fill and no two waves ever touch the same word.  resnet_bwd_reduce_kernel then sums the partials
-// in slot order: no atomics anywhere, and two calls on the same inputs give the same bits.
+// state), so nothing needs a zero-fill and no two waves ever touch the same word.  tc_reduce_kernel then sums the partials in slot
+// order: no atomics anywhere, and two calls on the same inputs give the same bits.
+// The slots, the contraction, the in-place accumulation, the transposed stager and the ordered sum are sx_train_contract.h's
+// (shared with sx_cnf_train.hip and sx_equivariant.hip); this file's own are the recompute, the w iteration, the stash and the loop
+// nest of rb_contract.  The launcher is sx_common.h's.
 // Launches: ONE for the recompute, the w iteration and the contraction, plus the reduce when any dW / db is wanted: two in all
 // (one for a pure vector-Jacobian product).
 //
@@ -28,13 +31,9 @@
 // eight SX_ACT_* codes for both activations, and forward + transposed images + scratch within SX_RESNET_LDS_BYTES -- dim 64 with
 // [64, 64] takes 129.75 KiB; dim 64 with [64, 64, 64] would take 162 KiB and is outside.
 #include "sx_resnet_common.h"
+#include "sx_train_contract.h"
 
 #define SX_RESNET_BWD_MAX_BLOCKS 512     /* partial slots = 4 waves x min(row blocks, this) */
-#define RB_SLOT 1056                     /* one transposed tile: 32 features x (32 rows + 1) */
-// The A fragments of a layer depend on nothing, so the scheduler would lift every LDS read of an iteration to its top and keep
-// them all live: a compiler-only memory barrier per output tile keeps each tile's reads beside its MFMAs.
-#define RB_NO_HOIST() asm volatile("" ::: "memory")
-
 namespace {
 
 struct rb_args {
@@ -51,19 +50,6 @@ struct rb_args {
     int64_t n_rows;
     int iterations, inverse;
 };
-
-// image of W^T: MT x KT tiles (MT: the layer's INPUT tiles, KT: its output tiles); tile (m, c), float g*256 + lane*4 + j holds
-// W[32c + kmap(4g + j, lane >> 5)][32m + (lane & 31)]
-__device__ __forceinline__ void rb_stage_t(const float *__restrict__ W, int out_dim, int in_dim, int MT, int KT, int base) {
-    const int n_w = MT * KT * 1024;
-    for (int e = threadIdx.x; e < n_w; e += SX_RESNET_THREADS) {
-        const int tile = e >> 10, rem = e & 1023;
-        const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
-        const int m = tile / KT, c = tile - m * KT;
-        const int col = 32 * m + (lane & 31), row = 32 * c + rn_kmap(4 * g + j, lane >> 5);
-        rn_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * in_dim + col] : 0.f;
-    }
-}
 
 // h = phi(a) and d = phi'(a) of one tile, in place (v: a in, h out).  Once per layer and row group, so ONE rolled copy of the
 // activation code per layer: the tile goes through the wave's LDS slots (each lane reads back its own words: no barrier) and a
@@ -97,14 +83,14 @@ __device__ __forceinline__ void rb_act_dact(f32x16 &v, f32x16 &d, int act, float
 template <int KT, int MT>
 __device__ __forceinline__ void rb_forward(const rtile<KT> &in, rtile<MT> &h, rtile<MT> &d, int base, float scale, int act, float *sA,
                                            float *sB, int lane) {
-    RB_NO_HOIST();
+    SX_NO_HOIST();
     rn_layer<KT, MT>(in, h, base, scale, SX_ACT_IDENTITY, lane);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-        RB_NO_HOIST();
+        SX_NO_HOIST();
         rb_act_dact(h.v[m], d.v[m], act, sA, sB, lane);
     }
-    RB_NO_HOIST();
+    SX_NO_HOIST();
 }
 
 // p[m] = (W^T . e)[m] * scale (* d[m]), m < MT; W^T: the transposed image at float offset `base` (KT tiles of e)
@@ -113,7 +99,7 @@ __device__ __forceinline__ void rb_layer_t(const rtile<KT> &e, rtile<MT> &p, con
     const float *wb = rn_smem + base + lane * 4;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-        RB_NO_HOIST();
+        SX_NO_HOIST();
         f32x16 acc = {};
 #pragma unroll
         for (int c = 0; c < KT; ++c) {
@@ -131,41 +117,6 @@ __device__ __forceinline__ void rb_layer_t(const rtile<KT> &e, rtile<MT> &p, con
     }
 }
 
-// The wave's words of the partial buffer have loop-invariant addresses, which the compiler would compute once, outside the group
-// loop, and keep: two registers per word.  An address that passes through here is rebuilt where it is used.
-template <class T>
-__device__ __forceinline__ T *rb_here(T *p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
-// a tile into a scratch slot, feature-major: slot[feature * 33 + row]
-__device__ __forceinline__ void rb_put(float *slot, const f32x16 &x, int lane) {
-    const int h = lane >> 5, n = lane & 31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) slot[rn_kmap(r, h) * 33 + n] = x[r];
-}
-
-// acc[X feature kmap(r, h)][Y feature lane & 31] += sum over the 32 rows of X Y^T, X in slot sa, Y in slot sb
-__device__ __forceinline__ void rb_outer(f32x16 &acc, const float *sa, const float *sb, int lane) {
-    const int o = (lane & 31) * 33 + (lane >> 5);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sa[o + 2 * kk], sb[o + 2 * kk], acc, 0, 0, 0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
-// feature lane & 31 of the tile in `slot` summed over rows 16 h .. 16 h + 15 (the two halves meet in the reduction)
-__device__ __forceinline__ float rb_rowsum(const float *slot, int lane) {
-    const float *p = slot + (lane & 31) * 33 + 16 * (lane >> 5);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += p[i];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    return s;
-}
-
 // G += e h^T and db += sum e of one layer into the wave's partial; e (its MT output tiles) and h (its KT input tiles) come from the
 // wave's stash, one tile at a time: nothing else is live here
 template <int MT, int KT>
@@ -174,43 +125,33 @@ __device__ __forceinline__ void rb_contract(const float *est, const float *hst, 
     if (want_w) {
 #pragma unroll
         for (int c = 0; c < KT; ++c) {
-            RB_NO_HOIST();
+            SX_NO_HOIST();
             f32x16 t;
-            const float *hp = rb_here(hst + c * 1024);
+            const float *hp = tc_here(hst + c * 1024);
 #pragma unroll
             for (int r = 0; r < 16; ++r) t[r] = hp[r * 64];
-            rb_put(sB, t, lane);
+            tc_put(sB, t, lane);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                RB_NO_HOIST();
-                const float *ep = rb_here(est + m * 1024);
+                SX_NO_HOIST();
+                const float *ep = tc_here(est + m * 1024);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) t[r] = ep[r * 64];
-                rb_put(sA, t, lane);
-                float *dst = rb_here(pw + (m * KT + c) * 1024 + lane);
-                f32x16 acc = {};
-                if (!first) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = dst[r * 64];
-                }
-                rb_outer(acc, sA, sB, lane);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
+                tc_put(sA, t, lane);
+                tc_add_tile(pw + (m * KT + c) * 1024 + lane, sA, sB, first, lane);
             }
         }
     }
     if (want_b) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            RB_NO_HOIST();
+            SX_NO_HOIST();
             f32x16 t;
-            const float *ep = rb_here(est + m * 1024);
+            const float *ep = tc_here(est + m * 1024);
 #pragma unroll
             for (int r = 0; r < 16; ++r) t[r] = ep[r * 64];
-            rb_put(sA, t, lane);
-            const float sum = rb_rowsum(sA, lane);
-            float *dst = rb_here(pb + m * 64 + lane);
-            *dst = first ? sum : *dst + sum;
+            tc_put(sA, t, lane);
+            tc_add_rowsum(pb + m * 64 + lane, sA, first, lane);
         }
     }
 }
@@ -220,7 +161,7 @@ template <int T>
 __device__ __forceinline__ void rb_stash(float *dst, const rtile<T> &t) {
 #pragma unroll
     for (int m = 0; m < T; ++m) {
-        float *p = rb_here(dst + m * 1024);
+        float *p = tc_here(dst + m * 1024);
 #pragma unroll
         for (int r = 0; r < 16; ++r) p[r * 64] = t.v[m][r];
     }
@@ -229,7 +170,7 @@ template <int T>
 __device__ __forceinline__ void rb_unstash(rtile<T> &t, const float *src) {
 #pragma unroll
     for (int m = 0; m < T; ++m) {
-        const float *p = rb_here(src + m * 1024);
+        const float *p = tc_here(src + m * 1024);
 #pragma unroll
         for (int r = 0; r < 16; ++r) t.v[m][r] = p[r * 64];
     }
@@ -255,12 +196,13 @@ __global__ __launch_bounds__(SX_RESNET_THREADS) void resnet_bwd_kernel(const rb_
     for (int l = 0; l < NL; ++l) {
         const int KT = l == 0 ? DT : HT, MT = l == NL - 1 ? DT : HT;
         rn_stage_layer(a.net.layer[l].W, a.net.layer[l].b, a.net.layer[l].out_dim, a.net.layer[l].in_dim, MT, KT, a.base[l]);
-        rb_stage_t(a.net.layer[l].W, a.net.layer[l].out_dim, a.net.layer[l].in_dim, KT, MT, a.base_t[l]);
+        tc_stage_t(rn_smem + a.base_t[l], a.net.layer[l].W, a.net.layer[l].out_dim, a.net.layer[l].in_dim, a.net.layer[l].in_dim, 0, KT, MT,
+                   SX_RESNET_THREADS);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, D = a.net.dim;
     const int act = a.net.act, fact = a.net.final_act;
-    float *sA = rn_smem + a.base_scr + wave * 2 * RB_SLOT, *sB = sA + RB_SLOT;
+    float *sA = rn_smem + a.base_scr + wave * 2 * SX_TC_SLOT, *sB = sA + SX_TC_SLOT;
     float sc[NL];
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
@@ -384,7 +326,7 @@ __global__ __launch_bounds__(SX_RESNET_THREADS) void resnet_bwd_kernel(const rb_
         }
         // ---- G_l += e_l h_{l-1}^T, db_l += sum e_l: every operand from the stash, no other state left ----------------------------
         if (params) {
-            RB_NO_HOIST();
+            SX_NO_HOIST();
 #pragma unroll
             for (int l = 0; l < NL; ++l) {
                 constexpr int in0 = 0;
@@ -400,46 +342,6 @@ __global__ __launch_bounds__(SX_RESNET_THREADS) void resnet_bwd_kernel(const rb_
             first = false;
         }
     }
-}
-
-// ---- the partial sum: one thread per gradient element, the slots in order -------------------------------------------------------
-struct rb_reduce_args {
-    const float *partial;
-    float *dW[SX_RESNET_MAX_LAYERS], *db[SX_RESNET_MAX_LAYERS];
-    int out_dim[SX_RESNET_MAX_LAYERS], in_dim[SX_RESNET_MAX_LAYERS], kt[SX_RESNET_MAX_LAYERS];
-    int off_w[SX_RESNET_MAX_LAYERS], off_b[SX_RESNET_MAX_LAYERS];
-    int n_layers, n_slots, part_floats;
-};
-
-// float offset of element [X feature fx][Y feature fy] (both < 32) inside an accumulator tile as rb_contract wrote it
-__device__ __forceinline__ int rb_tile_off(int fx, int fy) { return ((fx & 3) + 4 * (fx >> 3)) * 64 + fy + 32 * ((fx >> 2) & 1); }
-
-__global__ void resnet_bwd_reduce_kernel(const rb_reduce_args a) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float *dst = nullptr;
-    int off = 0, pair = 0;          // pair: a bias entry, whose two row halves sit 32 floats apart
-    bool found = false;
-    for (int l = 0; l < a.n_layers && !found; ++l) {
-        const int nw = a.out_dim[l] * a.in_dim[l], nb = a.out_dim[l];
-        if (i < nw) {
-            const int fx = i / a.in_dim[l], fy = i - fx * a.in_dim[l];
-            dst = a.dW[l];
-            off = a.off_w[l] + ((fx >> 5) * a.kt[l] + (fy >> 5)) * 1024 + rb_tile_off(fx & 31, fy & 31);
-            found = true;
-        } else if ((i -= nw) < nb) {
-            dst = a.db[l];
-            off = a.off_b[l] + (i >> 5) * 64 + (i & 31);
-            pair = 1;
-            found = true;
-        } else {
-            i -= nb;
-        }
-    }
-    if (!found || dst == nullptr) return;
-    double s = 0.0;                 // up to 2048 slots in a row: the sum is carried in fp64 and rounded once
-    const float *p = a.partial + off;
-    for (int k = 0; k < a.n_slots; ++k, p += a.part_floats) s += pair ? (double)p[0] + (double)p[32] : (double)p[0];
-    dst[i] = (float)s;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
@@ -482,7 +384,7 @@ size_t rb_plan(const sx_resnet_net &net, rb_args &a, int &DT, int &HT) {
         poff += MT * 64;
     }
     a.base_scr = (int)off;
-    off += (size_t)SX_RESNET_WAVES * 2 * RB_SLOT;
+    off += (size_t)SX_RESNET_WAVES * 2 * SX_TC_SLOT;
     a.off_h = poff;
     poff += 2 * (DT + (net.n_layers - 1) * HT) * 1024;        // the layers' inputs x, h_1 .. h_{L-1}, then e_1 .. e_L
     a.part_floats = poff;
@@ -492,32 +394,6 @@ size_t rb_plan(const sx_resnet_net &net, rb_args &a, int &DT, int &HT) {
 int64_t rb_blocks(int64_t n_rows) {
     const int64_t want = ((n_rows + 31) / 32 + SX_RESNET_WAVES - 1) / SX_RESNET_WAVES;
     return want < SX_RESNET_BWD_MAX_BLOCKS ? want : SX_RESNET_BWD_MAX_BLOCKS;
-}
-
-inline bool rb_aligned(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-
-template <int DT, int HT, int NL>
-int rb_launch(const rb_args &a, size_t lds, int64_t blocks, int *grid_out, void *stream) {
-    auto kern = resnet_bwd_kernel<DT, HT, NL>;
-    static bool raised_on[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!raised_on[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SX_RESNET_LDS_BYTES);
-        if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        raised_on[dev & 63] = true;
-    }
-    int cus = 0, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, SX_RESNET_THREADS, lds);
-    if (cus < 1) cus = 1;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const int grid = (int)(blocks < cap ? blocks : cap);
-    *grid_out = grid;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SX_RESNET_THREADS), lds, sx_stream(stream), a);
-    SX_LAUNCH_CHECK();
-    return SX_OK;
 }
 
 }  // namespace
@@ -552,18 +428,18 @@ extern "C" int sx_resnet_flow_bwd(const sx_resnet_net *net_host, const float *x,
     SX_REQUIRE(n_rows >= 0 && iterations >= 0, "sx_resnet_flow_bwd: negative n_rows / iterations");
     bool wrapped = false;
     for (int l = 0; l < net.n_layers; ++l) {
-        SX_REQUIRE(net.layer[l].W != nullptr && rb_aligned(net.layer[l].W) && rb_aligned(net.layer[l].b),
+        SX_REQUIRE(net.layer[l].W != nullptr && sx_aligned4(net.layer[l].W) && sx_aligned4(net.layer[l].b),
                    "sx_resnet_flow_bwd: layer %d has no weight, or a pointer that is not 4-byte aligned", l);
         wrapped = wrapped || net.layer[l].sigma_col >= 0;
     }
     SX_REQUIRE(!wrapped || sigma != nullptr, "sx_resnet_flow_bwd: a wrapped network needs its sigma row");
     SX_REQUIRE(x != nullptr && gin != nullptr && gout != nullptr, "sx_resnet_flow_bwd: null x / gin / gout");
-    SX_REQUIRE(rb_aligned(x) && rb_aligned(s_rows) && rb_aligned(sigma) && rb_aligned(gin) && rb_aligned(gout) && rb_aligned(gs) &&
-               rb_aligned(partial), "sx_resnet_flow_bwd: every pointer must be 4-byte aligned");
+    SX_REQUIRE(sx_aligned4(x) && sx_aligned4(s_rows) && sx_aligned4(sigma) && sx_aligned4(gin) && sx_aligned4(gout) && sx_aligned4(gs) &&
+               sx_aligned4(partial), "sx_resnet_flow_bwd: every pointer must be 4-byte aligned");
     bool any = false;
     if (grads != nullptr)
         for (int l = 0; l < net.n_layers; ++l) {
-            SX_REQUIRE(rb_aligned(grads->dW[l]) && rb_aligned(grads->db[l]), "sx_resnet_flow_bwd: gradient %d is not 4-byte aligned", l);
+            SX_REQUIRE(sx_aligned4(grads->dW[l]) && sx_aligned4(grads->db[l]), "sx_resnet_flow_bwd: gradient %d is not 4-byte aligned", l);
             any = any || grads->dW[l] != nullptr || grads->db[l] != nullptr;
         }
     SX_REQUIRE(!any || n_rows == 0 || partial != nullptr,
@@ -574,19 +450,16 @@ extern "C" int sx_resnet_flow_bwd(const sx_resnet_net *net_host, const float *x,
     const size_t lds = rb_plan(net, a, DT, HT) * 4;
     SX_REQUIRE(lds <= SX_RESNET_LDS_BYTES, "sx_resnet_flow_bwd: the images and scratch need %zu bytes of LDS (budget %d)", lds,
                SX_RESNET_LDS_BYTES);
-    rb_reduce_args r{};
+    tc_reduce_args<2 * SX_RESNET_MAX_LAYERS> r{};              // dW_0, db_0, dW_1, db_1, ...
     int total = 0;
     for (int l = 0; l < net.n_layers; ++l) {
         a.want_w[l] = any && grads->dW[l] != nullptr;
         a.want_b[l] = any && grads->db[l] != nullptr;
-        r.dW[l] = any ? grads->dW[l] : nullptr;
-        r.db[l] = any ? grads->db[l] : nullptr;
-        r.out_dim[l] = net.layer[l].out_dim; r.in_dim[l] = net.layer[l].in_dim;
-        r.kt[l] = l == 0 ? DT : HT;
-        r.off_w[l] = a.off_w[l]; r.off_b[l] = a.off_b[l];
+        r.e[2 * l] = {any ? grads->dW[l] : nullptr, net.layer[l].out_dim, net.layer[l].in_dim, l == 0 ? DT : HT, a.off_w[l]};
+        r.e[2 * l + 1] = {any ? grads->db[l] : nullptr, net.layer[l].out_dim, 0, 0, a.off_b[l]};
         total += net.layer[l].out_dim * (net.layer[l].in_dim + 1);
     }
-    r.partial = partial; r.part_floats = a.part_floats; r.n_layers = net.n_layers;
+    r.partial = partial; r.part_floats = a.part_floats;
     int grid = 0;
     if (n_rows > 0) {
         a.any_param = any ? 1 : 0;
@@ -595,7 +468,7 @@ extern "C" int sx_resnet_flow_bwd(const sx_resnet_net *net_host, const float *x,
         const int64_t blocks = rb_blocks(n_rows);
         const int NL = net.n_layers;
         int rc = SX_E_BADARG;
-#define RB_CASE(D_, H_, N_) if (DT == D_ && HT == H_ && NL == N_) rc = rb_launch<D_, H_, N_>(a, lds, blocks, &grid, stream);
+#define RB_CASE(D_, H_, N_) if (DT == D_ && HT == H_ && NL == N_) rc = sx_launch_capped<resnet_bwd_kernel<D_, H_, N_>>("sx_resnet_flow_bwd", a, SX_RESNET_THREADS, lds, SX_RESNET_LDS_BYTES, blocks, stream, &grid);
         RB_CASE(1, 1, 1) RB_CASE(2, 1, 1)
         RB_CASE(1, 1, 2) RB_CASE(1, 2, 2) RB_CASE(2, 1, 2) RB_CASE(2, 2, 2)
         RB_CASE(1, 1, 3) RB_CASE(1, 2, 3) RB_CASE(2, 1, 3) RB_CASE(2, 2, 3)
@@ -607,8 +480,5 @@ extern "C" int sx_resnet_flow_bwd(const sx_resnet_net *net_host, const float *x,
     // every wave with a row group wrote its slot: slots 0 .. min(groups, 4 * grid) - 1 (no rows: no slots, the gradients are zero)
     const int64_t n_groups = (n_rows + 31) / 32, n_waves = (int64_t)grid * SX_RESNET_WAVES;
     r.n_slots = (int)(n_groups < n_waves ? n_groups : n_waves);
-    hipLaunchKernelGGL(resnet_bwd_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, sx_stream(stream), r);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { sx_set_error("sx_resnet_flow_bwd: reduce launch failed: %s", hipGetErrorString(err)); return (int)err; }
-    return SX_OK;
+    return tc_reduce("sx_resnet_flow_bwd", r, total, stream);
 }

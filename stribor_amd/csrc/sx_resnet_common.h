@@ -1,6 +1,7 @@
 // What the ResNet-flow kernels share (sx_resnet.hip: the map and its fixed-point inverse; sx_resnet_bwd.hip: their backward):
-// the wave layout -- 32 rows on the MFMA column, features on the C rows in rn_kmap order --, the activations, the LDS image of a
-// layer in A-fragment order and the layer itself on exact fp32 v_mfma_f32_32x32x2_f32.
+// the wave layout -- 32 rows on the MFMA column, features on the C rows in sx_kmap order (sx_common.h) --, the activations, the LDS
+// image of a layer in A-fragment order and the layer itself on exact fp32 v_mfma_f32_32x32x2_f32.  Both launch through sx_common.h's
+// sx_launch_capped; the backward's weight-gradient contraction is sx_train_contract.h's.
 #pragma once
 #include "sx_common.h"
 
@@ -8,8 +9,6 @@
 #define SX_RESNET_THREADS (SX_RESNET_WAVES * 64)
 
 namespace {
-
-__host__ __device__ inline int rn_kmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 extern __shared__ __attribute__((aligned(16))) float rn_smem[];
 
@@ -49,7 +48,7 @@ __device__ __forceinline__ void rn_stage_layer(const float *__restrict__ W, cons
         const int tile = e >> 10, rem = e & 1023;
         const int g = rem >> 8, lane = (rem >> 2) & 63, j = rem & 3;
         const int m = tile / KT, c = tile - m * KT;
-        const int row = 32 * m + (lane & 31), col = 32 * c + rn_kmap(4 * g + j, lane >> 5);
+        const int row = 32 * m + (lane & 31), col = 32 * c + sx_kmap(4 * g + j, lane >> 5);
         rn_smem[base + e] = (row < out_dim && col < in_dim) ? W[(int64_t)row * in_dim + col] : 0.f;
     }
     for (int i = threadIdx.x; i < MT * 32; i += SX_RESNET_THREADS)
