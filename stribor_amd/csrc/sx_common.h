@@ -135,6 +135,19 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // ---- fast fp32 transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32 are 1 ulp) --------------------
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
+// exp(x) on v_exp_f32 with the product x*log2(e) carried to double-float accuracy (error ~1e-7 relative for |x| < 88)
+__device__ __forceinline__ float comp_exp(float x) {
+    const float t = x * 1.44269504088896341f;
+    const float r = __builtin_fmaf(x, 1.44269504088896341f, -t) + x * 1.92596299e-8f;   // low part of x*log2(e)
+    return __builtin_amdgcn_exp2f(t) * (1.f + r * 0.69314718055994531f);
+}
+// F.softplus (threshold 20) and sigmoid on the hardware transcendentals: |abs err| <~ 1e-7
+__device__ __forceinline__ float fast_softplus(float x) { return x > 20.f ? x : fast_log(1.f + fast_exp(x)); }
+__device__ __forceinline__ float fast_sigmoid(float x) { return fast_rcp(1.f + fast_exp(-x)); }
+// ... and on libm with an IEEE division, where a kernel mirrors the reference's own rounding
+__device__ __forceinline__ float sx_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float sx_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 // tanh(x) = 1 - 2/(exp(2x)+1): saturates correctly at +-inf, |abs err| <~ 2e-7
 __device__ __forceinline__ float fast_tanh(float x) {
     float e = __builtin_amdgcn_exp2f(x * 2.88539008177792682f);

@@ -1,6 +1,7 @@
 // Monotone cubic spline (stribor/util/cubic_spline.py:21-251): the per-element arithmetic shared by the element-wise kernel
-// (sx_rqs.hip: cubic_kernel) and the fused flow kernel's cubic phases (sx_flow_kernel.h).
+// (sx_rqs.hip: cubic_kernel), the slab tiers (sx_rqs_slab.hip, sx_rqs_bwd.h) and the fused flow kernel's cubic phases (sx_flow_kernel.h).
 #pragma once
+#include "sx_common.h"
 #define CUBIC_MIN_BIN 1e-2f          // cubic_spline.py:13-14
 #define CUBIC_EPS 1e-5f              // :15
 #define CUBIC_QUAD_THRESHOLD 1e-3f   // :16
@@ -9,10 +10,6 @@
 // sequences (the kernel is VALU-bound: 1,489 -> ~900 VALU instructions per element in the inverse direction, 791 -> ~500
 // forward, tools/pmc_spline_kernels.sh).  Their errors (~1e-7 relative) are the size of the reference's own fp32 rounding;
 // the inverse ends in Newton steps on the bin's cubic, so its result does not depend on how exactly the closed form ran.
-__device__ __forceinline__ float cubic_fexp(float v) { return __builtin_amdgcn_exp2f(v * 1.44269504088896341f); }
-__device__ __forceinline__ float cubic_frcp(float v) { return __builtin_amdgcn_rcpf(v); }
-__device__ __forceinline__ float cubic_flog(float v) { return __builtin_amdgcn_logf(v) * 0.69314718055994531f; }
-__device__ __forceinline__ float cubic_fsigmoid(float v) { return cubic_frcp(1.f + cubic_fexp(-v)); }
 __device__ __forceinline__ float cubic_fcbrt(float v) {        // :18-20  sign(x) * exp(log|x| / 3)
     const float m = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(fabsf(v)) * (1.0f / 3.0f));
     return (v == 0.f) ? 0.f : copysignf(m, v);
@@ -22,25 +19,58 @@ __device__ __forceinline__ float cubic_fcbrt(float v) {        // :18-20  sign(x
 struct cubic_coef { float a, bb, c; };
 __device__ __forceinline__ cubic_coef cubic_bin_coef(int b, int K, float w_b, float h_b, float w_m, float h_m, float w_p, float h_p,
                                                      float dpar0, float dpar1) {
-    const float rwb = cubic_frcp(w_b);
+    const float rwb = fast_rcp(w_b);
     const float s_b = h_b * rwb;                                                           // :117
-    const float s_m = h_m * cubic_frcp(w_m), s_p = h_p * cubic_frcp(w_p);
-    const float mL = 0.5f * (w_b * s_m + w_m * s_b) * cubic_frcp(w_m + w_b);              // :120-123
-    const float mR = 0.5f * (w_p * s_b + w_b * s_p) * cubic_frcp(w_b + w_p);
-    const float dL = (b == 0) ? cubic_fsigmoid(dpar0) * 3.f * s_b : 2.f * fminf(fminf(s_m, s_b), mL);       // :126, :118-129
-    const float dR = (b == K - 1) ? cubic_fsigmoid(dpar1) * 3.f * s_b : 2.f * fminf(fminf(s_b, s_p), mR);   // :127
+    const float s_m = h_m * fast_rcp(w_m), s_p = h_p * fast_rcp(w_p);
+    const float mL = 0.5f * (w_b * s_m + w_m * s_b) * fast_rcp(w_m + w_b);              // :120-123
+    const float mR = 0.5f * (w_p * s_b + w_b * s_p) * fast_rcp(w_b + w_p);
+    const float dL = (b == 0) ? fast_sigmoid(dpar0) * 3.f * s_b : 2.f * fminf(fminf(s_m, s_b), mL);       // :126, :118-129
+    const float dR = (b == K - 1) ? fast_sigmoid(dpar1) * 3.f * s_b : 2.f * fminf(fminf(s_b, s_p), mR);   // :127
     cubic_coef q;
     q.a = (dL + dR - 2.f * s_b) * (rwb * rwb);                                             // :134
     q.bb = (3.f * s_b - 2.f * dL - dR) * rwb;                                              // :135
     q.c = dL;                                                                              // :136
     return q;
 }
+// log f'(x) in bin b from the sizes of bins b-1, b, b+1 (:117-137, :235-237)
+__device__ __forceinline__ float cubic_logderiv_at(int b, int K, float cw_b, float w_b, float h_b, float w_m, float h_m, float w_p,
+                                                   float h_p, float dpar0, float dpar1, float xin) {
+    const cubic_coef q = cubic_bin_coef(b, K, w_b, h_b, w_m, h_m, w_p, h_p, dpar0, dpar1);
+    const float t = xin - cw_b;
+    return fast_log(3.f * q.a * (t * t) + 2.f * q.bb * t + q.c);
+}
+// The forward log-derivative at normalised input `xin` from an element's exp'ed widths / heights in registers (ew(k), eh(k): how
+// entry k is read) and their softmax factors nw, nh: one unrolled sweep over sixteen entries, selects only; the bin is searched by
+// widths, as the forward pass does.  BOUNDED: K <= 16 entries count (k < K is tested); otherwise all sixteen do.  (The inverse
+// kernels' reference mode, where the inverted point does not land in the bin it was solved in.)
+template <bool BOUNDED, class GW, class GH>
+__device__ __forceinline__ float cubic_select_forward_logderiv(GW ew, GH eh, float nw, float nh, float dpar0, float dpar1, int K, float xin) {
+    int b = 0;
+    float cw_b = 0.f, w_b = 0.f, h_b = 0.f, w_m = 1.f, h_m = 1.f, w_p = 1.f, h_p = 1.f;
+    float cw = 0.f, w_last = 1.f, h_last = 1.f;
+    bool need_next = false;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool used = BOUNDED ? k < K : true;
+        const float wk = CUBIC_MIN_BIN + nw * ew(k);
+        const float hk = CUBIC_MIN_BIN + nh * eh(k);
+        const bool ge = used && xin >= cw;
+        const bool nx = used && !ge && need_next;
+        b = ge ? k : b; cw_b = ge ? cw : cw_b; w_b = ge ? wk : w_b; h_b = ge ? hk : h_b;
+        w_m = ge ? w_last : w_m; h_m = ge ? h_last : h_m;
+        w_p = nx ? wk : w_p; h_p = nx ? hk : h_p;
+        need_next = used ? ge : need_next;
+        w_last = wk; h_last = hk;
+        cw += wk;
+    }
+    return cubic_logderiv_at(b, K, cw_b, w_b, h_b, w_m, h_m, w_p, h_p, dpar0, dpar1, xin);
+}
 // The inverse of the bin's cubic f(t) = a t^3 + bb t^2 + c t + d at y = xin (:154-222): the reference's closed forms (one-root
 // Cardano form, three-root trigonometric form with the in-bin root picked in its order, quadratic formula where |a| < 1e-3),
 // then Newton steps inside the bin.  Returns t = root - cw_b in [0, rcw - cw_b].
 __device__ __forceinline__ float cubic_invert(float a, float bb, float c, float d, float xin, float cw_b, float rcw) {
             float o;
-            const float ra = cubic_frcp(a);
+            const float ra = fast_rcp(a);
             const float b_ = (bb * ra) * (1.0f / 3.0f);                                    // :154-156
             const float c_ = (c * ra) * (1.0f / 3.0f);
             const float d_ = (d - xin) * ra;
@@ -59,7 +89,7 @@ __device__ __forceinline__ float cubic_invert(float a, float bb, float c, float 
             // cos / sin on [0, pi/3] (< 4e-9) -- no range reduction is needed anywhere.
             const float ty = three ? sqd : 0.f, tx = -dep1;
             const float ax = fabsf(tx), hi_ = fmaxf(ax, ty), lo_ = fminf(ax, ty);
-            const float qa = (hi_ > 0.f) ? lo_ * cubic_frcp(hi_) : 0.f, q2 = qa * qa;
+            const float qa = (hi_ > 0.f) ? lo_ * fast_rcp(hi_) : 0.f, q2 = qa * qa;
             float at = -0.00405455706641078f;
             at = fmaf(at, q2, 0.021862920373678207f); at = fmaf(at, q2, -0.05591226741671562f); at = fmaf(at, q2, 0.09642192721366882f);
             at = fmaf(at, q2, -0.1390862762928009f); at = fmaf(at, q2, 0.19946564733982086f); at = fmaf(at, q2, -0.33329859375953674f);
@@ -89,7 +119,7 @@ __device__ __forceinline__ float cubic_invert(float a, float bb, float c, float 
                 // root, but the reference's form loses everything as bb -> 0 (a near-identity spline has bb ~ 1e-5: 5 % of t,
                 // 1e-2 of x in fp32 -- the reference's own fp32 path does that; its fp64 values are what this returns)
                 const float qc = d - xin;
-                o = (-2.f * qc) * cubic_frcp(c + __builtin_amdgcn_sqrtf(c * c - 4.f * bb * qc)) + cw_b;
+                o = (-2.f * qc) * fast_rcp(c + __builtin_amdgcn_sqrtf(c * c - 4.f * bb * qc)) + cw_b;
             }
             // Newton steps on f(t) = a t^3 + bb t^2 + c t + d - y inside the bin (f is monotone there): the closed forms above lose
             // up to 5e-3 of the bin in fp32 where the cubic degenerates (the reference's fp32 path does too); two steps from
@@ -103,7 +133,7 @@ __device__ __forceinline__ float cubic_invert(float a, float bb, float c, float 
             for (int it = 0; it < 2; ++it) {
                 const float fv = fmaf(fmaf(fmaf(a, so, bb), so, c), so, f0);
                 const float fd = fmaf(fmaf(3.f * a, so, 2.f * bb), so, c);
-                const float st = fv * cubic_frcp(fd);
+                const float st = fv * fast_rcp(fd);
                 so = (fd > 0.f) ? fminf(fmaxf(so - st, 0.f), t_hi) : so;
             }
             so = quad ? so_q : so;

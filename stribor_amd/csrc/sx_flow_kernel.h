@@ -30,6 +30,7 @@
 #include "sx_common.h"
 #include "sx_flow_types.h"
 #include "sx_cubic_core.h"
+#include "sx_rqs_core.h"
 #include "sx_pointwise_core.h"
 #include "sx_pointwise_time_core.h"
 #include <stdlib.h>

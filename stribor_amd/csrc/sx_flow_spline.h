@@ -1,5 +1,7 @@
 // Spline-coupling phases of the fused flow kernel (rational-quadratic and monotone cubic; kernel MODEs 3 / 10 / 12 - 14 / 16 - 19).
 // Part of sx_flow_kernel.h: included from there, inside namespace SX_PREC_NS, after the GEMM tile helpers -- not a header of its own.
+// The spline constants, the rational-quadratic closing form (rqs_close) and the transcendental helpers (fast_log, fast_softplus, ...)
+// are not defined here: sx_rqs_core.h, sx_cubic_core.h and sx_common.h, which sx_flow_kernel.h includes before the namespace opens.
 // (Split out in round 4: the one 3,700-line header had become hard to navigate.  The objects still instantiate every MODE of a
 //  (tiles, hidden-tiles) pair, so an edit here rebuilds them all; a per-family split of the OBJECTS is the open half)
 // ------------------------------------------------------------------------------------------------
@@ -12,7 +14,6 @@
 // before all four tiles were done): the 12 GiB [N, D*(3K-1)] parameter tensor of the reference (spline.py:82-86) only ever
 // exists 64 registers at a time, and an element's arithmetic can run beside the MFMAs of the next element's tile.
 // ------------------------------------------------------------------------------------------------
-#define RQS_MIN 1e-3f
 // One iteration of a K-generic sweep ends here: the running results pass through an empty volatile asm and a scheduling fence, so that
 // an iteration's compares are consumed by its own selects (VCC) instead of being hoisted sixteen or thirty-two deep -- interleaved, the
 // sweeps keep ~60 lane masks alive and the allocator spills them to VGPR lanes (v_writelane / v_readlane: vector instructions; the
@@ -66,7 +67,7 @@ __device__ __forceinline__ float rqs_softmax(tile<1> (&acc)[4], int K) {
             sum += e;
         }
     const float Kf = KC ? (float)KC : (float)K;
-    return (1.f - RQS_MIN * Kf) * fast_rcp(sum);         // :101-105
+    return (1.f - RQS_MIN_BIN * Kf) * fast_rcp(sum);         // :101-105
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -107,8 +108,8 @@ struct rqs16_c {            // per-phase constants (uniform; one set per phase s
 };
 __device__ __forceinline__ rqs16_c rqs16_consts(float lo, float hi, int K = 16) {
     rqs16_c c;
-    const float span = hi - lo, sm = RQS_MIN * span, inf = __builtin_inff();
-    c.lo = lo; c.hi = hi; c.cs = (1.f - (float)K * RQS_MIN) * span;
+    const float span = hi - lo, sm = RQS_MIN_BIN * span, inf = __builtin_inff();
+    c.lo = lo; c.hi = hi; c.cs = (1.f - (float)K * RQS_MIN_BIN) * span;
     c.sm1 = sm; c.sm2 = 2.f * sm; c.sm3 = 3.f * sm; c.sm4 = 4.f * sm;
     c.l4 = 4 < K ? lo + 4.f * sm : inf; c.l8 = 8 < K ? lo + 8.f * sm : inf; c.l12 = 12 < K ? lo + 12.f * sm : inf;
     c.Km1 = K - 1; c.glast = (K - 1) >> 2;
@@ -293,7 +294,7 @@ __device__ __forceinline__ void rqs_search(tile<1> (&acc)[4], rqs_elems &e, int 
 #pragma unroll
     for (int j = 1; j <= 16 * W; ++j) {
         if (KC ? (j <= KC) : true) {
-            cs += RQS_MIN + RQS_PW(acc, Q, j - 1) * inv;
+            cs += RQS_MIN_BIN + RQS_PW(acc, Q, j - 1) * inv;
             const bool last = (j == Kn);
             const bool used = KC ? true : (j <= K);
             const float knot = last ? hi : (hi - lo) * cs + lo;          // ends pinned
@@ -322,7 +323,7 @@ __device__ __forceinline__ void rqs_select(tile<1> (&acc)[4], rqs_elems &e, int 
 #pragma unroll
     for (int j = 1; j <= 16 * W; ++j) {
         if (KC ? (j < KC) : true) {                                      // knot K is `hi` (the default k_n)
-            cs += RQS_MIN + RQS_PW(acc, Q, j - 1) * inv;
+            cs += RQS_MIN_BIN + RQS_PW(acc, Q, j - 1) * inv;
             const bool used = KC ? true : (j < Kn);
             const bool is_b = used && j == b, is_n = used && j == b + 1;
             cs_b = is_b ? cs : cs_b;
@@ -337,62 +338,35 @@ __device__ __forceinline__ void rqs_select(tile<1> (&acc)[4], rqs_elems &e, int 
     e.c_b[Q] = k_b;
     e.c_w[Q] = k_n - k_b;
 }
-// F.softplus(v) = log1p(exp(v)) (threshold 20) on v_exp_f32 / v_log_f32: |abs err| <~ 1e-7, far below the 1e-4
-// conditioning noise of the spline's log-derivative
-__device__ __forceinline__ float fast_log(float v) { return __builtin_amdgcn_logf(v) * 0.69314718055994531f; }
-__device__ __forceinline__ float rqs_softplus(float v) { return v > 20.f ? v : fast_log(1.f + fast_exp(v)); }
-// phase 2: the two knot derivatives at the bin (:107,:206-207), then the rational-quadratic (:236-248) or its
-// inverse (:212-234; the returned log-derivative is already negated like the reference's).
-// the evaluation behind the derivative pick: softplus of the two picked parameters (:107), the rational-quadratic (:236-248) or its
-// inverse (:212-234; the returned log-derivative is already negated like the reference's), the linear tails (:86-87)
+// the evaluation behind the derivative pick: the closing form of sx_rqs_core.h (softplus of the two picked parameters, :107, the
+// rational-quadratic, :236-248, or its inverse, :212-234, whose log-derivative comes back negated like the reference's) and the
+// linear tails (:86-87).  F.softplus on v_exp_f32 / v_log_f32: |abs err| <~ 1e-7, far below the 1e-4 conditioning noise of the
+// spline's log-derivative.  The closing form's points are this block's points 6..10.
+template <bool REV, class H>
+struct rqs_close_pts {
+    H &hk;
+    template <int Y, class... T> __device__ __forceinline__ void at(T &...tie) {
+        constexpr int p = Y == (REV ? RQS_Y_Q : RQS_Y_THETA) ? 6 : Y == (REV ? RQS_Y_DISC : RQS_Y_NUM) ? 7
+                        : Y == RQS_Y_OUT ? 8 : (REV && Y == RQS_Y_DEN) ? 9 : Y == RQS_Y_DNUM ? (REV ? 10 : 9) : -1;
+        if constexpr (p >= 0) hk.template pt<p>(tie...);
+    }
+};
 template <int Q, bool REV, class H>
 __device__ __forceinline__ void rqs_eval_core(float r_b, float r_n, bool in, const rqs_elems &e, float &out, float &ljd, H &hk) {
-    float d_b = RQS_MIN + rqs_softplus(r_b);
+    float d_b = rqs_knot_deriv(r_b);
     hk.template pt<4>(d_b);
-    float d_n = RQS_MIN + rqs_softplus(r_n);
+    float d_n = rqs_knot_deriv(r_n);
     hk.template pt<5>(d_n);
     // REV: the searched block is the heights (codomain side), the selected one the widths
     const float cw_b = REV ? e.c_b[Q] : e.a_b[Q], w_b = REV ? e.c_w[Q] : e.a_w[Q];
     const float ch_b = REV ? e.a_b[Q] : e.c_b[Q], h_b = REV ? e.a_w[Q] : e.c_w[Q];
     const float s_b = h_b * fast_rcp(w_b);
     const float xin = in ? e.x[Q] : (REV ? ch_b : cw_b);
-    if constexpr (REV) {
-        const float dy = xin - ch_b;
-        float q = d_b + d_n - 2.f * s_b;
-        hk.template pt<6>(q);
-        const float a = dy * q + h_b * (s_b - d_b);
-        const float bb = h_b * d_b - dy * q;
-        const float c = -s_b * dy;
-        float disc = bb * bb - 4.f * a * c;
-        hk.template pt<7>(disc);
-        // (disc >= 0 in exact arithmetic -- the spline is monotone --; rounding can leave it a few ulps below zero where the root
-        //  sits on a knot and the reference's own fp32 evaluation stays at or above it: clamp instead of returning NaN, :223)
-        // the root is a position inside the bin: rounding can also leave it an ulp outside [0, 1], where a steep bin next
-        // to a flat one (slope ~1e3, knot derivative ~1e-3) turns the derivative's numerator negative and its log into NaN
-        const float root = __builtin_amdgcn_fmed3f((2.f * c) * fast_rcp(-bb - __builtin_amdgcn_sqrtf(__builtin_fmaxf(disc, 0.f))), 0.f, 1.f);
-        out = root * w_b + cw_b;
-        hk.template pt<8>(out);
-        const float tomt = root * (1.f - root), omr = 1.f - root;
-        float den = s_b + q * tomt;
-        hk.template pt<9>(den);
-        float dnum = (s_b * s_b) * (d_n * (root * root) + 2.f * s_b * tomt + d_b * (omr * omr));
-        hk.template pt<10>(dnum);
-        ljd = -fast_log(dnum) + 2.f * fast_log(den);
-    } else {
-        float theta = (xin - cw_b) * fast_rcp(w_b);
-        hk.template pt<6>(theta);
-        const float tomt = theta * (1.f - theta), omt = 1.f - theta;
-        float num = h_b * (s_b * (theta * theta) + d_b * tomt);
-        hk.template pt<7>(num);
-        float den = s_b + (d_b + d_n - 2.f * s_b) * tomt;
-        out = ch_b + num * fast_rcp(den);
-        hk.template pt<8>(out, den);
-        float dnum = (s_b * s_b) * (d_n * (theta * theta) + 2.f * s_b * tomt + d_b * (omt * omt));
-        hk.template pt<9>(dnum);
-        hk.template pt<10>();
-        ljd = fast_log(dnum) - 2.f * fast_log(den);
-    }
-    out = in ? out : e.x[Q];                                    // :86-87 linear tails
+    rqs_close_pts<REV, H> pts{hk};
+    const rqs_closed c = rqs_close<REV>(d_b, d_n, s_b, cw_b, w_b, ch_b, h_b, xin, pts);
+    if constexpr (!REV) hk.template pt<10>();
+    ljd = rqs_log_deriv<REV>(c.dnum, c.den);
+    out = in ? c.out : e.x[Q];                                  // :86-87 linear tails
     ljd = in ? ljd : 0.f;
     hk.template pt<11>(out, ljd);
 }
@@ -403,7 +377,7 @@ __device__ __forceinline__ void rqs_eval(const f32x16 &u, const rqs_elems &e, in
     if constexpr (KC != 16) SX_OPAQUE(b);
     const bool in = e.b[Q] < RQS_OUT;
     const int Kn = KC ? KC : K;
-    const float cst = 0.5397424172369522f;                      // log(exp(1 - 1e-3) - 1), :81 boundary derivative constant
+    const float cst = RQS_BOUNDARY_DERIV;
     float r_b = cst, r_n = cst;
     // derivative k sits between bins k and k+1: it is the RIGHT knot's of bin k and the LEFT knot's of bin k+1, so one
     // compare per bin index serves both selections
@@ -450,7 +424,7 @@ __device__ __forceinline__ void rqs_eval_wide(const f32x16 &u0, const f32x16 &u1
     int b = e.b[Q] & (RQS_OUT - 1);
     SX_OPAQUE(b);
     const bool in = e.b[Q] < RQS_OUT;
-    const float cst = 0.5397424172369522f;
+    const float cst = RQS_BOUNDARY_DERIV;
     float r_b = cst, r_n = cst;
     bool is_prev = (b == 0);
 #pragma unroll
@@ -631,8 +605,8 @@ struct rqs32_c {
 };
 __device__ __forceinline__ rqs32_c rqs32_consts(float lo, float hi, int K) {
     rqs32_c c;
-    const float span = hi - lo, sm = RQS_MIN * span, inf = __builtin_inff();
-    c.lo = lo; c.hi = hi; c.cs = (1.f - (float)K * RQS_MIN) * span;
+    const float span = hi - lo, sm = RQS_MIN_BIN * span, inf = __builtin_inff();
+    c.lo = lo; c.hi = hi; c.cs = (1.f - (float)K * RQS_MIN_BIN) * span;
     c.sm1 = sm; c.sm2 = 2.f * sm; c.sm3 = 3.f * sm; c.sm4 = 4.f * sm;
 #pragma unroll
     for (int j = 1; j <= 7; ++j) c.l[j - 1] = 4 * j < K ? lo + 4.f * (float)j * sm : inf;
@@ -751,7 +725,7 @@ __device__ __forceinline__ void rqs32_eval(const f32x16 &u0, const f32x16 &u1, c
     hk.template pt<0>();
     const int b = e.b[Q] & (RQS_OUT - 1), bl = b & 3;
     const bool in = e.b[Q] < RQS_OUT;
-    const float cst = 0.5397424172369522f;                      // log(exp(1 - 1e-3) - 1), :81 boundary derivative constant
+    const float cst = RQS_BOUNDARY_DERIV;
     bool m[7];
 #pragma unroll
     for (int j = 0; j < 7; ++j) m[j] = b >= 4 * (j + 1);
@@ -1006,9 +980,9 @@ __device__ __forceinline__ float cub_softmax(tile<1> (&acc)[4], int K) {
             sum += e;
         }
     const float Kf = KC ? (float)KC : (float)K;
-    return (1.f - CUBIC_MIN_BIN * Kf) * cubic_frcp(sum);         // :103-104, :110-111
+    return (1.f - CUBIC_MIN_BIN * Kf) * fast_rcp(sum);         // :103-104, :110-111
 }
-__device__ __forceinline__ float cub_norm(float xv, bool in, float lo, float hi) { return ((in ? xv : lo) - lo) * cubic_frcp(hi - lo); }   // :98-101
+__device__ __forceinline__ float cub_norm(float xv, bool in, float lo, float hi) { return ((in ? xv : lo) - lo) * fast_rcp(hi - lo); }   // :98-101
 // K = 16: two-level forms of the two sweeps below (as in rqs16_search): the group of four bins from the groups' sums, then the six
 // sizes around it (bins 4g-1 .. 4g+4) picked by the group index, the bin and its neighbours inside them
 #define CUB_CL(k) ((k) < 0 ? 0 : ((k) > 15 ? 15 : (k)))        /* (the out-of-range neighbours are never used) */
@@ -1126,13 +1100,13 @@ __device__ __forceinline__ void cub_eval(const f32x16 &u, const cubic_elems &e, 
         const bool in2 = (out >= lo) && (out <= hi);
         float t2 = cub_norm(out, in2, lo, hi) - cw_b;
         hk.template pt<10>(t2);
-        ljd = in2 ? -cubic_flog(3.f * a * (t2 * t2) + 2.f * bb * t2 + c) : 0.f;            // flow.py:42-47
+        ljd = in2 ? -fast_log(3.f * a * (t2 * t2) + 2.f * bb * t2 + c) : 0.f;            // flow.py:42-47
     } else {
         hk.template pt<3>(); hk.template pt<4>(); hk.template pt<5>();
         float t = xn - cw_b;                                                               // :229
         out = (a * (t * t * t) + bb * (t * t) + c * t + d) * span + lo;                    // :230-233, :238
         hk.template pt<6>(out, t); hk.template pt<7>(); hk.template pt<8>(); hk.template pt<9>(); hk.template pt<10>();
-        ljd = cubic_flog(3.f * a * (t * t) + 2.f * bb * t + c);                            // :235-237
+        ljd = fast_log(3.f * a * (t * t) + 2.f * bb * t + c);                            // :235-237
     }
     out = in ? out : e.x[Q];                                                               // :46-48 linear tails
     ljd = in ? ljd : 0.f;
@@ -1187,7 +1161,7 @@ __device__ __forceinline__ void cub16_sums(const f32x16 &u, const cub16_c &cc, f
     float g3 = (ev[12] + ev[13]) + (ev[14] + ev[15]);
     hk.template pt<4>(g3);
     const float G2 = g0 + g1, G3 = G2 + g2;
-    inv = cc.cK * cubic_frcp(G3 + g3);
+    inv = cc.cK * fast_rcp(G3 + g3);
     T1 = __builtin_fmaf(inv, g0, cc.t4);
     T2 = __builtin_fmaf(inv, G2, cc.t8);
     T3 = __builtin_fmaf(inv, G3, cc.t12);

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void cumsum_vec_pipe_kernel(const float *__res
 __device__ __forceinline__ float pw_grad(int kind, float param, float x, float gy, float gl) {
     switch (kind) {
         case SX_PW_SIGMOID: {
-            const float sg = 1.f / (1.f + expf(-x));
+            const float sg = sx_sigmoid(x);
             return gy * sg * (1.f - sg) + gl * (1.f - 2.f * sg);
         }
         case SX_PW_LOGIT: {

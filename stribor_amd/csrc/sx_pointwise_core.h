@@ -6,18 +6,11 @@
 #define PW_TINY 1.17549435e-38f          // torch.finfo(float32).tiny
 #define PW_ONE_MINUS_EPS 0.99999988f     // 1 - torch.finfo(float32).eps
 
-// exp(v) on v_exp_f32 with the product v*log2(e) carried to double-float accuracy (error ~1e-7 relative for |v| < 88)
-__device__ __forceinline__ float pw_exp(float v) {
-    const float t = v * 1.44269504088896341f;
-    const float r = __builtin_fmaf(v, 1.44269504088896341f, -t) + v * 1.92596299e-8f;   // low part of v*log2(e)
-    return __builtin_amdgcn_exp2f(t) * (1.f + r * 0.69314718055994531f);
-}
-__device__ __forceinline__ float pw_log(float v) { return __builtin_amdgcn_logf(v) * 0.69314718055994531f; }
 // softplus(-v) + softplus(v) = |v| + 2 log(1 + exp(-|v|)): one exp, one log (sigmoid.py:44 evaluates two softplus)
 __device__ __forceinline__ float pw_two_softplus(float v, float &t) {
     const float a = fabsf(v);
-    t = pw_exp(-a);
-    return a + 2.f * pw_log(1.f + t);
+    t = comp_exp(-a);
+    return a + 2.f * fast_log(1.f + t);
 }
 
 __device__ __forceinline__ void pw_eval(int kind, float param, float log_slope, float x, float &out, float &ld) {

@@ -69,7 +69,7 @@ __device__ __forceinline__ float pwt_act(int kind, float x, float &dact) {
         return th;
     }
     if (kind == SX_PWT_MIX_SIGMOID) {
-        const float sg = 1.f / (1.f + expf(-x));
+        const float sg = sx_sigmoid(x);
         dact = sg * (1.f - sg);
         return sg;
     }

@@ -12,10 +12,7 @@
 // lanes of a ds_read_b32 group hit 32 different banks.  No compaction: tails are predicated.  The per-row
 // log-det is a shuffle sum when a row's live columns sit inside one wave, float atomics otherwise.
 #include "sx_stream.h"
-
-#define RQS_MIN_BIN 1e-3f
-#define RQS_MIN_DERIV 1e-3f
-#define RQS_EPS 1e-6f
+#include "sx_rqs_core.h"
 
 extern __shared__ __attribute__((aligned(16))) float rqs_smem[];
 
@@ -39,9 +36,6 @@ __device__ __forceinline__ void rqs_dma_span(const float *__restrict__ g, float 
 }
 
 // ---- straight-line evaluation for K = 16 (the BASELINE configuration): parameters in registers, selects only ----
-__device__ __forceinline__ float rqs_fast_log(float v) { return __builtin_amdgcn_logf(v) * 0.69314718055994531f; }
-__device__ __forceinline__ float rqs_fast_softplus(float v) { return v > 20.f ? v : rqs_fast_log(1.f + fast_exp(v)); }
-
 // softmax numerators in place; returns the factor turning them into bin sizes (size_k = MIN + e_k * inv), :101-105
 __device__ __forceinline__ float rqs16_softmax(float (&u)[16]) {
     float mx = u[0];
@@ -68,6 +62,10 @@ __device__ __forceinline__ void rqs16_load(rqs16_regs &r, const float *__restric
 #pragma unroll
     for (int k = 0; k < 15; ++k) r.ud[k] = p[32 + k];
 }
+struct rqs16_disc_hook {      // for the error flag: a negative (or NaN) discriminant
+    bool neg = false;
+    template <int Y, class... T> __device__ __forceinline__ void at(float &v, T &...) { if constexpr (Y == RQS_Y_DISC) neg = !(v >= 0.f); }
+};
 template <bool INVERSE>
 __device__ __forceinline__ void rqs16_eval(rqs16_regs &r, float xv, float left, float right, float bottom,
                                            float top, float &out, float &ljd, bool &bad_disc) {
@@ -102,42 +100,34 @@ __device__ __forceinline__ void rqs16_eval(rqs16_regs &r, float xv, float left, 
         c_b = (j == b) ? knot : c_b;
         c_n = (j == b + 1) ? knot : c_n;
     }
-    const float cst = 0.5397424172369522f;       // log(exp(1 - 1e-3) - 1), :81
-    float r_b = cst, r_n = cst;
+    float r_b = RQS_BOUNDARY_DERIV, r_n = RQS_BOUNDARY_DERIV;
 #pragma unroll
     for (int k = 0; k < 15; ++k) {
         const float v = r.ud[k];
         r_b = (k == b - 1) ? v : r_b;
         r_n = (k == b) ? v : r_n;
     }
-    const float d_b = RQS_MIN_DERIV + rqs_fast_softplus(r_b), d_n = RQS_MIN_DERIV + rqs_fast_softplus(r_n);
+    const float d_b = rqs_knot_deriv(r_b), d_n = rqs_knot_deriv(r_n);
     const float cw_b = INVERSE ? c_b : a_b, w_b = INVERSE ? c_n - c_b : a_n - a_b;
     const float ch_b = INVERSE ? a_b : c_b, h_b = INVERSE ? a_n - a_b : c_n - c_b;
-    const float s_b = h_b * __builtin_amdgcn_rcpf(w_b);
+    const float s_b = h_b * fast_rcp(w_b);
     bad_disc = false;
     if constexpr (INVERSE) {
-        const float dy = xin - ch_b;
-        const float q = d_b + d_n - 2.f * s_b;
-        const float a = dy * q + h_b * (s_b - d_b);
-        const float bb = h_b * d_b - dy * q;
-        const float c = -s_b * dy;
-        const float disc = bb * bb - 4.f * a * c;
-        bad_disc = inside && !(disc >= 0.f);
-        // (clamped to the bin like the fused kernel's, sx_flow_spline.h rqs_eval_core)
-        const float root = __builtin_amdgcn_fmed3f((2.f * c) * __builtin_amdgcn_rcpf(-bb - __builtin_amdgcn_sqrtf(__builtin_fmaxf(disc, 0.f))), 0.f, 1.f);
-        out = root * w_b + cw_b;
-        const float tomt = root * (1.f - root), omr = 1.f - root;
-        const float den = s_b + q * tomt;
-        const float dnum = (s_b * s_b) * (d_n * (root * root) + 2.f * s_b * tomt + d_b * (omr * omr));
-        ljd = -rqs_fast_log(dnum) + 2.f * rqs_fast_log(den);
+        rqs16_disc_hook hk;
+        const rqs_closed c = rqs_close<true>(d_b, d_n, s_b, cw_b, w_b, ch_b, h_b, xin, hk);
+        bad_disc = inside && hk.neg;
+        out = c.out;
+        ljd = rqs_log_deriv<true>(c.dnum, c.den);
     } else {
-        const float theta = (xin - cw_b) * __builtin_amdgcn_rcpf(w_b);
+        // rqs_close<false>'s expressions, kept in place: behind a call this kernel's SLP packing comes out differently and the dense
+        // forward kernel goes from 141 to 163 VGPRs
+        const float theta = (xin - cw_b) * fast_rcp(w_b);
         const float tomt = theta * (1.f - theta), omt = 1.f - theta;
         const float num = h_b * (s_b * (theta * theta) + d_b * tomt);
         const float den = s_b + (d_b + d_n - 2.f * s_b) * tomt;
-        out = ch_b + num * __builtin_amdgcn_rcpf(den);
+        out = ch_b + num * fast_rcp(den);
         const float dnum = (s_b * s_b) * (d_n * (theta * theta) + 2.f * s_b * tomt + d_b * (omt * omt));
-        ljd = rqs_fast_log(dnum) - 2.f * rqs_fast_log(den);
+        ljd = rqs_log_deriv<false>(dnum, den);
     }
     out = inside ? out : xv;                     // :86-87
     ljd = inside ? ljd : 0.f;
@@ -161,7 +151,7 @@ __global__ __launch_bounds__(256) void rqs_kernel(const void *__restrict__ x, vo
     const sx_units units = sx_make_units(n_rows, n_live, ALIGNED);
     const int64_t n_groups = units.n_units;
     const float lo_in = INVERSE ? bottom : left, hi_in = INVERSE ? top : right;
-    const float bconst = logf(expf(1.f - RQS_MIN_DERIV) - 1.f);  // :81 boundary derivative constant
+    const float bconst = logf(expf(1.f - RQS_MIN_DERIV) - 1.f);  // :81 boundary derivative constant (RQS_BOUNDARY_DERIV as libm rounds it)
     const float norm = 1.f - RQS_MIN_BIN * (float)K;
     // rows of parameters back to back (stride = n_live * P) and a 16-byte aligned base: 64 elements = 64*P floats
     const bool contig = (pstride == (int64_t)n_live * P) && ((reinterpret_cast<uintptr_t>(params) & 15) == 0);
@@ -344,25 +334,11 @@ extern "C" int sx_rqs_coupling(const void *x, void *y, float *ldj, float *ldiag,
 // =====================================================================================================
 #include "sx_cubic_core.h"
 
-__device__ __forceinline__ float cubic_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-// exp(v) on v_exp_f32 with the product v*log2(e) carried to double-float accuracy (~1e-7 relative)
-__device__ __forceinline__ float cubic_exp(float v) {
-    const float t = v * 1.44269504088896341f;
-    const float r = fmaf(v, 1.44269504088896341f, -t) + v * 1.92596299e-8f;
-    return __builtin_amdgcn_exp2f(t) * (1.f + r * 0.69314718055994531f);
-}
 
 // Forward log-derivative log f'(x) of the monotone cubic spline at normalised input `xin` from the element's
 // (exp'ed) widths / heights ew[k], eh[k] with their softmax factors nw, nh and the two raw boundary-derivative parameters
 // (cubic_spline.py:103-137, 229-237): the bin is searched by widths, as the forward pass does.  Used by the inverse
 // kernel's reference mode when the inverted point does not land in the bin it was solved in (rare).
-// log f'(x) in bin b from the sizes of bins b-1, b, b+1 (:117-137, :235-237)
-__device__ __forceinline__ float cubic_logderiv_at(int b, int K, float cw_b, float w_b, float h_b, float w_m, float h_m, float w_p,
-                                                   float h_p, float dpar0, float dpar1, float xin) {
-    const cubic_coef q = cubic_bin_coef(b, K, w_b, h_b, w_m, h_m, w_p, h_p, dpar0, dpar1);
-    const float t = xin - cw_b;
-    return cubic_flog(3.f * q.a * (t * t) + 2.f * q.bb * t + q.c);
-}
 template <class GW, class GH>
 __device__ __forceinline__ float cubic_forward_logderiv(GW ew, GH eh, float nw, float nh, float dpar0, float dpar1, int K,
                                                         float xin) {
@@ -380,29 +356,6 @@ __device__ __forceinline__ float cubic_forward_logderiv(GW ew, GH eh, float nw, 
     }
     return cubic_logderiv_at(b, K, cw_b, w_b, h_b, w_m, h_m, w_p, h_p, dpar0, dpar1, xin);
 }
-// the same from the K = 16 register form (exp'ed widths / heights + softmax factors): selects only
-__device__ __forceinline__ float cubic16_forward_logderiv(const float (&rw)[16], const float (&rh)[16], float nw, float nh,
-                                                          float dpar0, float dpar1, float xin) {
-    int b = 0;
-    float cw_b = 0.f, w_b = 0.f, h_b = 0.f, w_m = 1.f, h_m = 1.f, w_p = 1.f, h_p = 1.f;
-    float cw = 0.f, w_last = 1.f, h_last = 1.f;
-    bool need_next = false;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const float wk = CUBIC_MIN_BIN + nw * rw[k];
-        const float hk = CUBIC_MIN_BIN + nh * rh[k];
-        const bool ge = xin >= cw;
-        const bool nx = !ge && need_next;
-        b = ge ? k : b; cw_b = ge ? cw : cw_b; w_b = ge ? wk : w_b; h_b = ge ? hk : h_b;
-        w_m = ge ? w_last : w_m; h_m = ge ? h_last : h_m;
-        w_p = nx ? wk : w_p; h_p = nx ? hk : h_p;
-        need_next = ge;
-        w_last = wk; h_last = hk;
-        cw += wk;
-    }
-    return cubic_logderiv_at(b, 16, cw_b, w_b, h_b, w_m, h_m, w_p, h_p, dpar0, dpar1, xin);
-}
-
 template <bool BF16, bool INVERSE, bool ALIGNED>
 __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ x, void *__restrict__ y,
                                                     float *__restrict__ ldj, float *__restrict__ ldiag,
@@ -525,13 +478,13 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
             for (int k = 1; k < KK; ++k) { mw = fmaxf(mw, get_w(k)); mh = fmaxf(mh, get_h(k)); }
             float sw = 0.f, sh = 0.f;
             for (int k = 0; k < KK; ++k) {      // exp once per parameter (v_exp_f32 with a compensated argument)
-                const float ew = cubic_fexp(get_w(k) - mw), eh = cubic_fexp(get_h(k) - mh);
+                const float ew = fast_exp(get_w(k) - mw), eh = fast_exp(get_h(k) - mh);
                 set_w(k, ew);
                 set_h(k, eh);
                 sw += ew;
                 sh += eh;
             }
-            const float nw = norm * cubic_frcp(sw), nh = norm * cubic_frcp(sh);         // one reciprocal per softmax
+            const float nw = norm * fast_rcp(sw), nh = norm * fast_rcp(sh);         // one reciprocal per softmax
             nw_k = nw; nh_k = nh;
             float cw = 0.f, ch = 0.f, w_last = 1.f, h_last = 1.f;
             bool need_next = false;
@@ -563,10 +516,10 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
             float sw = 0.f, sh = 0.f;
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
-                rw[k] = cubic_fexp(rw[k] - mw); rh[k] = cubic_fexp(rh[k] - mh);
+                rw[k] = fast_exp(rw[k] - mw); rh[k] = fast_exp(rh[k] - mh);
                 sw += rw[k]; sh += rh[k];
             }
-            const float nw = norm * cubic_frcp(sw), nh = norm * cubic_frcp(sh);
+            const float nw = norm * fast_rcp(sw), nh = norm * fast_rcp(sh);
             nw_k = nw; nh_k = nh;
             // Two-level search (as the fused kernel's cub_search16): the group of four bins from the groups' sums, then the bin and
             // its two neighbours among the six sizes around the group -- ~110 VALU instructions instead of ~260 for the 16-step
@@ -610,7 +563,7 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
             float so = cubic_invert(a, bb, c, d, xin, cw_b, rcw);
             float o;
             o = so + cw_b;
-            ljd = -cubic_flog(3.f * a * (so * so) + 2.f * bb * so + c);                    // :225-227
+            ljd = -fast_log(3.f * a * (so * so) + 2.f * bb * so + c);                    // :225-227
             // (an input inside the closed domain has its pre-image inside it too: without the clamp an input ON the bound -- common
             //  with bf16 storage, whose grid contains +-3 -- can come back one ulp outside, and the reference-mode log-det below
             //  would then be the tails' 0 instead of -log f')
@@ -629,14 +582,15 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
                 float lf;
                 {
                     const float t2 = xin2 - cw_b;
-                    lf = cubic_flog(3.f * a * (t2 * t2) + 2.f * bb * t2 + c);
+                    lf = fast_log(3.f * a * (t2 * t2) + 2.f * bb * t2 + c);
                 }
                 const bool slow = valid && in2 && !same_bin;
                 if (__builtin_amdgcn_ballot_w64(slow)) {
                     if (slow) {
                         if (K == 16) {          // the exp'ed widths / heights are still in registers (the LDS slice may already
                                                 // be receiving the next group)
-                            lf = cubic16_forward_logderiv(rw, rh, nw_k, nh_k, dpar0, dpar1, xin2);
+                            lf = cubic_select_forward_logderiv<false>([&](int k) { return rw[k]; }, [&](int k) { return rh[k]; }, nw_k, nh_k, dpar0,
+                                                                       dpar1, 16, xin2);
                         } else {                // the generic path left exp(u - max) in place of the raw widths / heights
                             lf = cubic_forward_logderiv([&](int k) { return p[k]; }, [&](int k) { return p[K + k]; }, nw_k, nh_k,
                                                         dpar0, dpar1, K, xin2);
@@ -649,7 +603,7 @@ __global__ __launch_bounds__(256, 4) void cubic_kernel(const void *__restrict__ 
         } else {
             const float t = xin - cw_b;                                                    // :229
             out = a * (t * t * t) + bb * (t * t) + c * t + d;                              // :230-233
-            ljd = cubic_flog(3.f * a * (t * t) + 2.f * bb * t + c);                        // :235-237
+            ljd = fast_log(3.f * a * (t * t) + 2.f * bb * t + c);                        // :235-237
             out = out * span + lower;                                                      // :238
             ljd = (ljd + log_span) - log_span;                                             // :239
         }
@@ -866,7 +820,7 @@ __global__ __launch_bounds__(256) void cubic_bwd_kernel(const float *__restrict_
         for (int k = 1; k < K; ++k) { mw = fmaxf(mw, p[k]); mh = fmaxf(mh, p[K + k]); }
         float sw = 0.f, sh = 0.f;
         for (int k = 0; k < K; ++k) {
-            const float ew = cubic_exp(p[k] - mw), eh = cubic_exp(p[K + k] - mh);
+            const float ew = comp_exp(p[k] - mw), eh = comp_exp(p[K + k] - mh);
             if (valid) { p[k] = ew; p[K + k] = eh; }
             sw += ew;
             sh += eh;
@@ -886,7 +840,7 @@ __global__ __launch_bounds__(256) void cubic_bwd_kernel(const float *__restrict_
         const bool has_m = b > 0, has_p = b < K - 1;
         const float w_m = has_m ? W(b - 1) : 1.f, h_m = has_m ? H(b - 1) : 1.f, s_m = h_m / w_m;
         const float w_p = has_p ? W(b + 1) : 1.f, h_p = has_p ? H(b + 1) : 1.f, s_p = h_p / w_p;
-        const float sgl = cubic_sigmoid(p[2 * K]), sgr = cubic_sigmoid(p[2 * K + 1]);
+        const float sgl = sx_sigmoid(p[2 * K]), sgr = sx_sigmoid(p[2 * K + 1]);
         // knot derivatives and which branch produced them
         float dL, dR;
         bool L_m1 = false, L_first = false, R_m1 = false, R_first = false;

@@ -6,19 +6,8 @@
 // piecewise constant: no gradient.  Elements in the linear tails pass dL/d(out) through and contribute nothing to the
 // parameters.  Ao = dL/d(out), Al = dL/d(log-derivative) of this element.
 #pragma once
-#ifndef RQS_MIN_BIN
-#define RQS_MIN_BIN 1e-3f
-#define RQS_MIN_DERIV 1e-3f
-#define RQS_EPS 1e-6f
-#endif
-__device__ __forceinline__ float rqsb_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-__device__ __forceinline__ float rqsb_softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }  // F.softplus
-// exp(v) on v_exp_f32 with the product v*log2(e) carried to double-float accuracy (~1e-7 relative)
-__device__ __forceinline__ float rqsb_exp(float v) {
-    const float t = v * 1.44269504088896341f;
-    const float r = fmaf(v, 1.44269504088896341f, -t) + v * 1.92596299e-8f;
-    return __builtin_amdgcn_exp2f(t) * (1.f + r * 0.69314718055994531f);
-}
+#include "sx_rqs_core.h"
+#include "sx_cubic_core.h"
 
 // The scalar part: from the bin's geometry (knots cw_b / ch_b are only used through w_b, h_b) and the two raw derivative
 // parameters to the adjoints of the four knots, the two derivative parameters and the input.
@@ -32,15 +21,9 @@ struct rqs_adj {
 template <bool FAST>
 __device__ __forceinline__ float rqsb_div(float a, float b) { return FAST ? a * __builtin_amdgcn_rcpf(b) : a / b; }
 template <bool FAST>
-__device__ __forceinline__ float rqsb_softplus_p(float v) {
-    if constexpr (FAST) return v > 20.f ? v : __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(v * 1.44269504088896341f)) * 0.69314718055994531f;
-    else return rqsb_softplus(v);
-}
+__device__ __forceinline__ float rqsb_softplus_p(float v) { return FAST ? fast_softplus(v) : sx_softplus(v); }
 template <bool FAST>
-__device__ __forceinline__ float rqsb_sigmoid_p(float v) {
-    if constexpr (FAST) return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
-    else return rqsb_sigmoid(v);
-}
+__device__ __forceinline__ float rqsb_sigmoid_p(float v) { return FAST ? fast_sigmoid(v) : sx_sigmoid(v); }
 template <bool FAST = false>
 __device__ __forceinline__ rqs_adj rqs_inverse_bwd_core(float xin, float w_b, float h_b, float ch_b, float u_b, float u_n,
                                                         float Ao, float Al) {
@@ -112,7 +95,7 @@ __device__ __forceinline__ rqs_adj rqs_inverse_bwd_core(float xin, float w_b, fl
 __device__ __forceinline__ rqs_adj rqs_forward_bwd_core(float xin, float w_b, float h_b, float cw_b, float u_b, float u_n, float Ao,
                                                         float Al) {
     const float s_b = h_b / w_b;
-    const float d_b = RQS_MIN_DERIV + rqsb_softplus(u_b), d_n = RQS_MIN_DERIV + rqsb_softplus(u_n);
+    const float d_b = RQS_MIN_DERIV + sx_softplus(u_b), d_n = RQS_MIN_DERIV + sx_softplus(u_n);
     const float th = (xin - cw_b) / w_b, omt = 1.f - th, tomt = th * omt;
     const float q = d_b + d_n - 2.f * s_b;
     const float inner = s_b * (th * th) + d_b * tomt;
@@ -145,8 +128,8 @@ __device__ __forceinline__ rqs_adj rqs_forward_bwd_core(float xin, float w_b, fl
     A.Acwb = Acwb - Awb;
     A.Achn = Ahb;
     A.Achb = Ao - Ahb;                 // out = ch_b + ...
-    A.g_ub = Adb * rqsb_sigmoid(u_b);
-    A.g_un = Adn * rqsb_sigmoid(u_n);
+    A.g_ub = Adb * sx_sigmoid(u_b);
+    A.g_un = Adn * sx_sigmoid(u_n);
     A.Axin = Axin;
     return A;
 }
@@ -171,7 +154,7 @@ __device__ __forceinline__ float rqs_bwd_element(float *uw, int K, float xv, flo
     for (int k = 1; k < K; ++k) { mw = fmaxf(mw, uw[k]); mh = fmaxf(mh, uh[k]); }
     float sw = 0.f, sh = 0.f;
     for (int k = 0; k < K; ++k) {          // exp once per parameter, kept in place (v_exp_f32, compensated argument)
-        const float ew = rqsb_exp(uw[k] - mw), eh = rqsb_exp(uh[k] - mh);
+        const float ew = comp_exp(uw[k] - mw), eh = comp_exp(uh[k] - mh);
         uw[k] = ew;
         uh[k] = eh;
         sw += ew;
@@ -247,7 +230,7 @@ __device__ __forceinline__ float rqs_inverse_bwd_regs(rqsb_f16v &Wp, rqsb_f16v &
                                                       Hook &&hook = Hook{}) {
     constexpr float LOG2E = 1.44269504088896341f;
     const int Kn = KC ? KC : K;
-    const float bconst = 0.5397424172369522f;                       // log(exp(1 - 1e-3) - 1), :81 boundary derivative constant
+    const float bconst = RQS_BOUNDARY_DERIV;
     const float norm = 1.f - RQS_MIN_BIN * (float)Kn;
     const float span_w = right - left, span_h = top - bottom;
     const bool inside = (xv >= bottom) && (xv <= top);
@@ -347,13 +330,12 @@ __device__ __forceinline__ float rqs_inverse_bwd_regs(rqsb_f16v &Wp, rqsb_f16v &
 // K widths / heights, Dp[0..1] its two boundary-derivative parameters (cubic_spline.py:103-137); the same mathematics as
 // cubic_bwd_kernel<true> (sx_rqs.hip: the solve differentiated implicitly at the forward's output `xo`, then reverse mode
 // through the Steffen knot derivatives, cumsums and softmax), static indices, hardware exp / rcp.
-#define CUBICB_MIN_BIN 1e-2f
 template <int KC>
 __device__ __forceinline__ float cubic_inverse_bwd_regs(rqsb_f16v &Wp, rqsb_f16v &Hp, rqsb_f16v &Dp, int K, float yv, float xo,
                                                         float Ao, float Al, float lower, float upper, bool valid) {
     constexpr float LOG2E = 1.44269504088896341f;
     const int Kn = KC ? KC : K;
-    const float norm = 1.f - CUBICB_MIN_BIN * (float)Kn;
+    const float norm = 1.f - CUBIC_MIN_BIN * (float)Kn;
     const float span = upper - lower, inv_span = __builtin_amdgcn_rcpf(span);
     const bool inside = (yv >= lower) && (yv <= upper);
     const float yn = ((inside ? yv : lower) - lower) * inv_span;
@@ -386,7 +368,7 @@ __device__ __forceinline__ float cubic_inverse_bwd_regs(rqsb_f16v &Wp, rqsb_f16v
     for (int k = 0; k < 16; ++k)
         if (KC ? (k < KC) : true) {
             const bool used = KC ? true : (k < K);
-            const float wk = fmaf(Wp[k], nw, CUBICB_MIN_BIN), hk = fmaf(Hp[k], nh, CUBICB_MIN_BIN);
+            const float wk = fmaf(Wp[k], nw, CUBIC_MIN_BIN), hk = fmaf(Hp[k], nh, CUBIC_MIN_BIN);
             const bool ge = used && yn >= ch;
             const bool nx = used && !ge && need_next;
             b = ge ? k : b;
@@ -401,7 +383,7 @@ __device__ __forceinline__ float cubic_inverse_bwd_regs(rqsb_f16v &Wp, rqsb_f16v
         }
     const bool has_m = b > 0, has_p = b < Kn - 1;
     const float s_b = h_b * __builtin_amdgcn_rcpf(w_b), s_m = h_m * __builtin_amdgcn_rcpf(w_m), s_p = h_p * __builtin_amdgcn_rcpf(w_p);
-    const float sgl = rqsb_sigmoid_p<true>(Dp[0]), sgr = rqsb_sigmoid_p<true>(Dp[1]);
+    const float sgl = fast_sigmoid(Dp[0]), sgr = fast_sigmoid(Dp[1]);
     float dL, dR;
     bool L_m1 = false, L_first = false, R_m1 = false, R_first = false;
     if (!has_m) dL = sgl * 3.f * s_b;                                                      // :126

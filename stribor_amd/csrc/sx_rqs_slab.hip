@@ -765,12 +765,20 @@ struct slabf_hook_seq {           // hk.at<B>(), hk.at<B + 1>() ... from an unro
         }
     }
 };
+// rqs_close's points -> the slots 43..46 of a slabf hook
+template <class Hook>
+struct slabf_close_hook {
+    Hook &hk;
+    template <int Y, class... T> __device__ __forceinline__ void at(float &v, T &...) {
+        constexpr int slot = (Y == RQS_Y_DISC || Y == RQS_Y_THETA) ? 43 : (Y == RQS_Y_ROOT || Y == RQS_Y_NUM) ? 44 : Y == RQS_Y_DEN ? 45 : Y == RQS_Y_DNUM ? 46 : -1;
+        if constexpr (slot >= 0) hk.template at<slot>(v);
+    }
+};
 template <int KC, bool REV, class Hook>
 __device__ __forceinline__ void rqs_slab_eval(rqsb_f16v &Sp, rqsb_f16v &Op, const rqsb_f16v &Dp, int K, float xv, float slo, float shi,
                                               float olo, float ohi, float &out, float &ljd, Hook &hk) {
     constexpr float LOG2E = 1.44269504088896341f, LN2 = 0.69314718055994531f;
     const int Kn = KC ? KC : K;
-    const float bconst = 0.5397424172369522f;                       // log(exp(1 - 1e-3) - 1), :81 boundary derivative constant
     const float norm = 1.f - RQS_MIN_BIN * (float)Kn;
     const float span_s = shi - slo, span_o = ohi - olo;
     const bool inside = (xv >= slo) && (xv <= shi);                 // :71 closed interval
@@ -825,7 +833,7 @@ __device__ __forceinline__ void rqs_slab_eval(rqsb_f16v &Sp, rqsb_f16v &Op, cons
     const bool first = (b == 0), lastbin = (b + 1 == Kn);
     const float ko_b = first ? olo : fmaf(span_o, co_b, olo);
     const float ko_n = lastbin ? ohi : fmaf(span_o, co_n, olo);
-    float u_b = bconst, u_n = bconst;
+    float u_b = RQS_BOUNDARY_DERIV, u_n = RQS_BOUNDARY_DERIV;
 #pragma unroll
     for (int k = 0; k < 15; ++k)
         if (KC ? (k < KC - 1) : true) {
@@ -834,57 +842,24 @@ __device__ __forceinline__ void rqs_slab_eval(rqsb_f16v &Sp, rqsb_f16v &Op, cons
             u_b = (used && b == k + 1) ? Dp[k] : u_b;
             if (k % 3 == 2) slabf_hook_seq<5, Hook>::template call<35>(hk, k / 3, u_n, u_b);
         }
-    float d_b = RQS_MIN_DERIV + rqsb_softplus_p<true>(u_b);                                                              // :107
+    float d_b = rqs_knot_deriv(u_b);                                                                                      // :107
     hk.template at<40>(d_b);
-    float d_n = RQS_MIN_DERIV + rqsb_softplus_p<true>(u_n);
+    float d_n = rqs_knot_deriv(u_n);
     hk.template at<41>(d_n);
     const float cw_b = REV ? ko_b : ks_b, w_b = REV ? ko_n - ko_b : ks_n - ks_b;
     const float ch_b = REV ? ks_b : ko_b, h_b = REV ? ks_n - ks_b : ko_n - ko_b;
-    float s_b = h_b * __builtin_amdgcn_rcpf(w_b);
+    float s_b = h_b * fast_rcp(w_b);
     hk.template at<42>(s_b);
-    float o, l;
-    if constexpr (REV) {                                            // :212-234
-        const float dy = xin - ch_b;
-        const float q = d_b + d_n - 2.f * s_b;
-        const float a = dy * q + h_b * (s_b - d_b);
-        const float bb = h_b * d_b - dy * q;
-        const float c = -s_b * dy;
-        float disc = bb * bb - 4.f * a * c;
-        hk.template at<43>(disc);
-        // (the clamps of the one-launch tier, sx_flow_spline.h rqs_eval_core: rounding can leave the discriminant a few ulps below
-        //  zero and the root an ulp outside its bin where the reference's own fp32 evaluation stays inside)
-        float root = __builtin_amdgcn_fmed3f((2.f * c) * __builtin_amdgcn_rcpf(-bb - __builtin_amdgcn_sqrtf(__builtin_fmaxf(disc, 0.f))), 0.f, 1.f);
-        hk.template at<44>(root);
-        o = root * w_b + cw_b;
-        const float tomt = root * (1.f - root), omr = 1.f - root;
-        float den = s_b + q * tomt;
-        hk.template at<45>(den);
-        float dnum = (s_b * s_b) * (d_n * (root * root) + 2.f * s_b * tomt + d_b * (omr * omr));
-        hk.template at<46>(dnum);
-        float l1 = __builtin_amdgcn_logf(den);
-        hk.template at<47>(l1);
-        float l2 = __builtin_amdgcn_logf(dnum);
-        hk.template at<48>(l2);
-        l = (2.f * l1 - l2) * LN2;
-    } else {                                                        // :236-248
-        float theta = (xin - cw_b) * __builtin_amdgcn_rcpf(w_b);
-        hk.template at<43>(theta);
-        const float tomt = theta * (1.f - theta), omt = 1.f - theta;
-        float num = h_b * (s_b * (theta * theta) + d_b * tomt);
-        hk.template at<44>(num);
-        float den = s_b + (d_b + d_n - 2.f * s_b) * tomt;
-        hk.template at<45>(den);
-        o = ch_b + num * __builtin_amdgcn_rcpf(den);
-        float dnum = (s_b * s_b) * (d_n * (theta * theta) + 2.f * s_b * tomt + d_b * (omt * omt));
-        hk.template at<46>(dnum);
-        float l1 = __builtin_amdgcn_logf(dnum);
-        hk.template at<47>(l1);
-        float l2 = __builtin_amdgcn_logf(den);
-        hk.template at<48>(l2);
-        l = (l1 - 2.f * l2) * LN2;
-    }
+    // the closing form of the one-launch tier with its clamps (sx_rqs_core.h); the two logs are combined BEFORE the ln 2 scaling here
+    slabf_close_hook<Hook> ch{hk};
+    const rqs_closed c = rqs_close<REV>(d_b, d_n, s_b, cw_b, w_b, ch_b, h_b, xin, ch);
+    float l1 = __builtin_amdgcn_logf(REV ? c.den : c.dnum);
+    hk.template at<47>(l1);
+    float l2 = __builtin_amdgcn_logf(REV ? c.dnum : c.den);
+    hk.template at<48>(l2);
+    float l = REV ? (2.f * l1 - l2) * LN2 : (l1 - 2.f * l2) * LN2;
     hk.template at<49>(l);
-    out = inside ? o : xv;                                          // :86-87 linear tails
+    out = inside ? c.out : xv;                                      // :86-87 linear tails
     ljd = inside ? l : 0.f;
 }
 
@@ -894,30 +869,6 @@ __device__ __forceinline__ void rqs_slab_eval(rqsb_f16v &Sp, rqsb_f16v &Op, cons
 // bins b - 1, b, b + 1 (the Steffen slopes need the neighbours, :117-132), then the bin's cubic forward or its inverse (closed forms +
 // Newton steps).  ref_ldj (a coupling's inverse_and_log_det_jacobian): the log-det is MINUS the FORWARD log-derivative re-evaluated
 // at the inverted point (flow.py:42-47), as cubic_kernel's reference mode.
-__device__ __forceinline__ float cubic_regs_forward_logderiv(const rqsb_f16v &ew, const rqsb_f16v &eh, float nw, float nh, float dpar0,
-                                                             float dpar1, int K, float xin) {
-    int b = 0;
-    float cw_b = 0.f, w_b = 0.f, h_b = 0.f, w_m = 1.f, h_m = 1.f, w_p = 1.f, h_p = 1.f;
-    float cw = 0.f, w_last = 1.f, h_last = 1.f;
-    bool need_next = false;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const bool used = k < K;
-        const float wk = CUBIC_MIN_BIN + nw * ew[k];
-        const float hk = CUBIC_MIN_BIN + nh * eh[k];
-        const bool ge = used && xin >= cw;
-        const bool nx = used && !ge && need_next;
-        b = ge ? k : b; cw_b = ge ? cw : cw_b; w_b = ge ? wk : w_b; h_b = ge ? hk : h_b;
-        w_m = ge ? w_last : w_m; h_m = ge ? h_last : h_m;
-        w_p = nx ? wk : w_p; h_p = nx ? hk : h_p;
-        need_next = used ? ge : need_next;
-        w_last = wk; h_last = hk;
-        cw += wk;
-    }
-    const cubic_coef q = cubic_bin_coef(b, K, w_b, h_b, w_m, h_m, w_p, h_p, dpar0, dpar1);
-    const float t = xin - cw_b;
-    return cubic_flog(3.f * q.a * (t * t) + 2.f * q.bb * t + q.c);
-}
 template <bool REV>
 __device__ __forceinline__ void cubic_slab_eval(rqsb_f16v &Wp, rqsb_f16v &Hp, const rqsb_f16v &Dp, int K, float xv, float lower, float upper,
                                                 float log_span, bool ref_ldj, bool valid, float &out, float &ljd) {
@@ -936,11 +887,11 @@ __device__ __forceinline__ void cubic_slab_eval(rqsb_f16v &Wp, rqsb_f16v &Hp, co
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const bool used = k < K;
-        const float ew = used ? cubic_fexp(Wp[k] - mw) : 0.f, eh = used ? cubic_fexp(Hp[k] - mh) : 0.f;
+        const float ew = used ? fast_exp(Wp[k] - mw) : 0.f, eh = used ? fast_exp(Hp[k] - mh) : 0.f;
         Wp[k] = ew; Hp[k] = eh;
         sw += ew; sh += eh;
     }
-    const float nw = norm * cubic_frcp(sw), nh = norm * cubic_frcp(sh);
+    const float nw = norm * fast_rcp(sw), nh = norm * fast_rcp(sh);
     // normalised sizes, running cumsums (:103-115) and the bin search (search_sorted.py:4-5) in one sweep that also keeps the sizes of
     // bins b - 1, b, b + 1: the lower knot of bin k is compared (knot 0 = 0: the knots only grow)
     int b = 0;
@@ -968,7 +919,7 @@ __device__ __forceinline__ void cubic_slab_eval(rqsb_f16v &Wp, rqsb_f16v &Hp, co
     if constexpr (REV) {
         const float so = cubic_invert(a, bb, c, d, xin, cw_b, rcw);
         const float o = so + cw_b;
-        ljd = -cubic_flog(3.f * a * (so * so) + 2.f * bb * so + c);                        // :225-227
+        ljd = -fast_log(3.f * a * (so * so) + 2.f * bb * so + c);                        // :225-227
         out = fminf(fmaxf(o * span + lower, lower), upper);                                // :235 (see cubic_kernel)
         ljd = (ljd - log_span) + log_span;                                                 // :236
         if (ref_ldj) {
@@ -976,10 +927,10 @@ __device__ __forceinline__ void cubic_slab_eval(rqsb_f16v &Wp, rqsb_f16v &Hp, co
             const float xin2 = ((in2 ? out : lower) - lower) * inv_span;
             const bool same_bin = (xin2 >= cw_b) && (b == K - 1 || xin2 < cw_b + w_b);
             const float t2 = xin2 - cw_b;
-            float lf = cubic_flog(3.f * a * (t2 * t2) + 2.f * bb * t2 + c);
+            float lf = fast_log(3.f * a * (t2 * t2) + 2.f * bb * t2 + c);
             const bool slow = valid && in2 && !same_bin;
             if (__builtin_amdgcn_ballot_w64(slow)) {
-                if (slow) lf = cubic_regs_forward_logderiv(Wp, Hp, nw, nh, dpar0, dpar1, K, xin2);
+                if (slow) lf = cubic_select_forward_logderiv<true>([&](int k) { return Wp[k]; }, [&](int k) { return Hp[k]; }, nw, nh, dpar0, dpar1, K, xin2);
             }
             lf = (lf + log_span) - log_span;                                               // :239
             ljd = in2 ? -lf : 0.f;                                                         // :46-48 tails; flow.py:47 negation
@@ -987,7 +938,7 @@ __device__ __forceinline__ void cubic_slab_eval(rqsb_f16v &Wp, rqsb_f16v &Hp, co
     } else {
         const float t = xin - cw_b;                                                        // :229
         out = a * (t * t * t) + bb * (t * t) + c * t + d;                                  // :230-233
-        ljd = cubic_flog(3.f * a * (t * t) + 2.f * bb * t + c);                            // :235-237
+        ljd = fast_log(3.f * a * (t * t) + 2.f * bb * t + c);                            // :235-237
         out = out * span + lower;                                                          // :238
         ljd = (ljd + log_span) - log_span;                                                 // :239
     }

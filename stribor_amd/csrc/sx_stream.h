@@ -2,7 +2,6 @@
 // already in HBM, one lane per element (or per 4 / 8 consecutive elements of a row):
 //   * element access in a storage type (fp32 or bf16; all arithmetic is fp32): scalar, and 4- / 8-wide as ONE 8- or 16-byte access,
 //     plain or streaming (non-temporal).  A launcher issues only accesses as wide as the alignment it checked;
-//   * sx_softplus, the reference's F.softplus;
 //   * sx_row_ldj, the per-row log-det sum: fixed-order shuffle sums, no atomics -- aligned lane groups for power-of-two widths <= 64
 //     (ldj_mode 1), the row-aligned units of sx_common.h for every other width (ldj_mode 2);
 //   * on the host: the ldj_mode rule, the grid cap, the dispatch of runtime bools to template arguments, and the launch plan of the
@@ -69,8 +68,6 @@ __device__ __forceinline__ void sx_stv(void *p, int64_t off, const f32x4 *v) {
         st_stream<NT>(reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(p) + off), v[0]);
     }
 }
-
-__device__ __forceinline__ float sx_softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }   // F.softplus (threshold 20)
 
 // ---- per-row log-det sums --------------------------------------------------------------------------------------------------
 // One object per work unit.  ldj[r] = (acc ? ldj[r] : 0) + scale * s, in exactly this order (a kernel without a scale passes 1).
