@@ -34,12 +34,6 @@
 
 namespace {
 
-// (inlined on purpose: an out-of-line call would spill the live stage vectors around it)
-__device__ __forceinline__ void cn_dact_tile(f32x16 *v, int act) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) (*v)[r] = cnf_dact((*v)[r], act);
-}
-
 struct cn_args : cnf_dense_args {
     int base_tr;            // LDS float offset of c (one hidden layer) or C (two, when c_in_lds)
     const float *x;
@@ -65,7 +59,7 @@ __device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xi
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
                 f32x16 d = h1.v[m];
-                if (act != SX_ACT_IDENTITY) cn_dact_tile(&d, act);
+                if (act != SX_ACT_IDENTITY) cnf_dact_tile(d, act);
                 else d = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s += d[r] * cnf_vec(cv, m, r);
@@ -79,7 +73,7 @@ __device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xi
             // h1 <- d1, v = C d1, s = d2 . v
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
-                if (act != SX_ACT_IDENTITY) cn_dact_tile(&h1.v[m], act);
+                if (act != SX_ACT_IDENTITY) cnf_dact_tile(h1.v[m], act);
                 else h1.v[m] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
             }
             // v = C d1 one 32-row tile at a time, consumed at once: s += d2 . v
@@ -89,7 +83,7 @@ __device__ __forceinline__ void cn_eval(const cn_args &a, const cnf_tile<DT> &xi
                 if (a.c_in_lds) cnf_mma<HT>(v, h1, cnf_smem + a.base_tr + m * HT * 1024 + lane * 4);
                 else cnf_mma_global<HT>(v, h1, a.net.trace + (int64_t)m * 32 * (HT * 32), lane);
                 f32x16 d = h2.v[m];
-                if (act != SX_ACT_IDENTITY) cn_dact_tile(&d, act);
+                if (act != SX_ACT_IDENTITY) cnf_dact_tile(d, act);
                 else d = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s += d[r] * v[r];

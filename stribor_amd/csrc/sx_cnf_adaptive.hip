@@ -16,7 +16,7 @@
 //
 // Coverage: dim <= 32, 1 + dim + latent_dim <= 128, one or two hidden layers of <= 64 units, the activations of sx_cnf_flow.
 //
-// The trace (ca_eval) restates cn_eval of sx_cnf.hip with C always in LDS: that function stays in its file because moving it
+// The trace (ad_eval) restates cn_eval of sx_cnf.hip with C always in LDS: that function stays in its file because moving it
 // changes the register allocation of cnf_flow_kernel<1, 4, 2> (see the header of sx_cnf.hip).
 #include "sx_cnf_dense.h"
 
@@ -29,7 +29,7 @@ namespace {
 // The tableau (DESIGN.md "CNF").  Row st = the weights of k1 .. k6 in the input of stage st + 1; row 6 is b (a7 = b: FSAL), so the
 // input of the seventh evaluation is the step itself.  Each entry is the fp32 rounding of the fp64 quotient.
 #define F(x) ((float)(x))
-__device__ const float ca_a[7][6] = {
+__device__ const float ad_a[7][6] = {
     {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
     {F(1.0 / 5.0), 0.f, 0.f, 0.f, 0.f, 0.f},
     {F(3.0 / 40.0), F(9.0 / 40.0), 0.f, 0.f, 0.f, 0.f},
@@ -38,13 +38,13 @@ __device__ const float ca_a[7][6] = {
     {F(9017.0 / 3168.0), F(-355.0 / 33.0), F(46732.0 / 5247.0), F(49.0 / 176.0), F(-5103.0 / 18656.0), 0.f},
     {F(35.0 / 384.0), 0.f, F(500.0 / 1113.0), F(125.0 / 192.0), F(-2187.0 / 6784.0), F(11.0 / 84.0)},
 };
-__device__ const float ca_c[7] = {0.f, F(1.0 / 5.0), F(3.0 / 10.0), F(4.0 / 5.0), F(8.0 / 9.0), 1.f, 1.f};
+__device__ const float ad_c[7] = {0.f, F(1.0 / 5.0), F(3.0 / 10.0), F(4.0 / 5.0), F(8.0 / 9.0), 1.f, 1.f};
 // e = b - b*: the weights of k1 .. k7 in the error estimate
-__device__ const float ca_e[7] = {F(35.0 / 384.0 - 5179.0 / 57600.0), 0.f, F(500.0 / 1113.0 - 7571.0 / 16695.0), F(125.0 / 192.0 - 393.0 / 640.0),
+__device__ const float ad_e[7] = {F(35.0 / 384.0 - 5179.0 / 57600.0), 0.f, F(500.0 / 1113.0 - 7571.0 / 16695.0), F(125.0 / 192.0 - 393.0 / 640.0),
                                   F(-2187.0 / 6784.0 + 92097.0 / 339200.0), F(11.0 / 84.0 - 187.0 / 2100.0), F(-1.0 / 40.0)};
 #undef F
 
-struct ca_args : cnf_dense_args {
+struct ad_args : cnf_dense_args {
     int base_tr;            // LDS float offset of c (one hidden layer) or C (two)
     const float *x;
     const float *latent;
@@ -56,19 +56,13 @@ struct ca_args : cnf_dense_args {
     float t0, t1, rtol, atol, first_step;
 };
 
-// (inlined on purpose: an out-of-line call would spill the live stage vectors around it)
-__device__ __forceinline__ void ca_dact_tile(f32x16 *v, int act) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) (*v)[r] = cnf_dact((*v)[r], act);
-}
-
 // max / min that keep a NaN (fmaxf / fminf drop it): a row whose error ratio is not a number must fail, not pass
-__device__ __forceinline__ float ca_nmax(float a, float b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ float ca_nmin(float a, float b) { return (a < b || a != a) ? a : b; }
+__device__ __forceinline__ float ad_nmax(float a, float b) { return (a > b || a != a) ? a : b; }
+__device__ __forceinline__ float ad_nmin(float a, float b) { return (a < b || a != a) ? a : b; }
 
 // k = sgn f(t, xin) and -- when `want` -- tr = sgn tr df/dx for the wave's 32 rows, t PER LANE (cn_eval of sx_cnf.hip otherwise)
 template <int DT, int HT, int NH>
-__device__ __forceinline__ void ca_eval(const ca_args &a, const cnf_tile<DT> &xin, float t, const cnf_tile<HT> &lat, float sgn, cnf_tile<DT> &k,
+__device__ __forceinline__ void ad_eval(const ad_args &a, const cnf_tile<DT> &xin, float t, const cnf_tile<HT> &lat, float sgn, cnf_tile<DT> &k,
                                         bool want, float &tr, int lane) {
     const int h = lane >> 5, act = a.net.act;
     const f32x16 ones = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
@@ -81,7 +75,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const cnf_tile<DT> &xi
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
                 f32x16 d = h1.v[m];
-                if (act != SX_ACT_IDENTITY) ca_dact_tile(&d, act);
+                if (act != SX_ACT_IDENTITY) cnf_dact_tile(d, act);
                 else d = ones;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s += d[r] * cnf_vec(cv, m, r);
@@ -95,7 +89,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const cnf_tile<DT> &xi
             // h1 <- d1, then v = C d1 one 32-row tile at a time, consumed at once: s += d2 . v
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
-                if (act != SX_ACT_IDENTITY) ca_dact_tile(&h1.v[m], act);
+                if (act != SX_ACT_IDENTITY) cnf_dact_tile(h1.v[m], act);
                 else h1.v[m] = ones;
             }
 #pragma unroll
@@ -103,7 +97,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const cnf_tile<DT> &xi
                 f32x16 v = {};
                 cnf_mma<HT>(v, h1, cnf_smem + a.base_tr + m * HT * 1024 + lane * 4);
                 f32x16 d = h2.v[m];
-                if (act != SX_ACT_IDENTITY) ca_dact_tile(&d, act);
+                if (act != SX_ACT_IDENTITY) cnf_dact_tile(d, act);
                 else d = ones;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s += d[r] * v[r];
@@ -121,7 +115,7 @@ __device__ __forceinline__ void ca_eval(const ca_args &a, const cnf_tile<DT> &xi
 
 // rms over the row's D features of num / den (the padded features stay out; both lane halves of a row get the same bits)
 template <int DT>
-__device__ __forceinline__ float ca_rms(const cnf_tile<DT> &num, const cnf_tile<DT> &den, int D, int h) {
+__device__ __forceinline__ float ad_rms(const cnf_tile<DT> &num, const cnf_tile<DT> &den, int D, int h) {
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < DT; ++c)
@@ -135,7 +129,7 @@ __device__ __forceinline__ float ca_rms(const cnf_tile<DT> &num, const cnf_tile<
 }
 
 template <int DT, int HT, int NH>
-__global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_args a) {
+__global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ad_args a) {
     const sx_cnf_net &net = a.net;
     const int D = net.dim, H1 = net.layer[0].out_dim;
     cnf_dense_stage<DT, HT, NH>(a);
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_a
         const bool live = row < a.n_rows;
         cnf_tile<DT> y, xs, k, K[7];
         cnf_tile<HT> lat;
-        cnf_dense_load<DT>(y, a.x, row, D, live, h);
+        cnf_load_row<DT>(y, a.x, row, D, live, h);
         cnf_dense_latent<HT>(a, lat, a.latent, row, live, lane);
         float Q[7], q = 0.f;
 #pragma unroll
@@ -161,7 +155,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_a
 #pragma unroll
             for (int c = 0; c < DT; ++c) K[j].v[c] = f32x16{};
         }
-        ca_eval<DT, HT, NH>(a, y, a.t0, lat, sgn, K[0], want, Q[0], lane);
+        ad_eval<DT, HT, NH>(a, y, a.t0, lat, sgn, K[0], want, Q[0], lane);
         float l = 0.f, s = 0.f, dt = a.first_step;
         if (!(a.first_step > 0.f)) {
             // the first step by Hairer's rule: scale = atol + rtol |y0| (the trace share starts at 0: its scale is atol)
@@ -170,21 +164,21 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_a
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sc.v[c][r] = atol + rtol * fabsf(y.v[c][r]);
-            const float d0 = ca_rms<DT>(y, sc, D, h);
-            const float d1 = ca_nmax(ca_rms<DT>(K[0], sc, D, h), want ? fabsf(Q[0]) / atol : 0.f);
+            const float d0 = ad_rms<DT>(y, sc, D, h);
+            const float d1 = ad_nmax(ad_rms<DT>(K[0], sc, D, h), want ? fabsf(Q[0]) / atol : 0.f);
             const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
 #pragma unroll
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) xs.v[c][r] = y.v[c][r] + h0 * K[0].v[c][r];
-            ca_eval<DT, HT, NH>(a, xs, a.t0 + sgn * h0, lat, sgn, k, want, q, lane);
+            ad_eval<DT, HT, NH>(a, xs, a.t0 + sgn * h0, lat, sgn, k, want, q, lane);
 #pragma unroll
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) k.v[c][r] = k.v[c][r] - K[0].v[c][r];
-            const float d2 = ca_nmax(ca_rms<DT>(k, sc, D, h), want ? fabsf(q - Q[0]) / atol : 0.f) / h0;
-            const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, 1e-3f * h0) : powf(0.01f / ca_nmax(d1, d2), 0.2f);
-            dt = ca_nmin(100.f * h0, h1);
+            const float d2 = ad_nmax(ad_rms<DT>(k, sc, D, h), want ? fabsf(q - Q[0]) / atol : 0.f) / h0;
+            const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, 1e-3f * h0) : powf(0.01f / ad_nmax(d1, d2), 0.2f);
+            dt = ad_nmin(100.f * h0, h1);
         }
         int n_att = 0, n_acc = 0, n_rej = 0, status = 0;
         bool done = !live || !(T > 0.f);
@@ -205,36 +199,36 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_a
                 for (int c = 0; c < DT; ++c)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float acc = ca_a[st][0] * K[0].v[c][r];
+                        float acc = ad_a[st][0] * K[0].v[c][r];
 #pragma unroll
-                        for (int j = 1; j < 6; ++j) acc = acc + ca_a[st][j] * K[j].v[c][r];
+                        for (int j = 1; j < 6; ++j) acc = acc + ad_a[st][j] * K[j].v[c][r];
                         xs.v[c][r] = y.v[c][r] + hs * acc;
                     }
-                ca_eval<DT, HT, NH>(a, xs, a.t0 + sgn * (s + ca_c[st] * hs), lat, sgn, k, want, q, lane);
+                ad_eval<DT, HT, NH>(a, xs, a.t0 + sgn * (s + ad_c[st] * hs), lat, sgn, k, want, q, lane);
 #pragma unroll
                 for (int j = 1; j < 7; ++j)
                     if (st == j) { K[j] = k; Q[j] = q; }
             }
             // xs is the step (row 6 of the table is b); the trace's step, the error estimate and its ratio to the tolerance
-            float qa = ca_a[6][0] * Q[0], qe = ca_e[0] * Q[0];
+            float qa = ad_a[6][0] * Q[0], qe = ad_e[0] * Q[0];
 #pragma unroll
-            for (int j = 1; j < 6; ++j) qa = qa + ca_a[6][j] * Q[j];
+            for (int j = 1; j < 6; ++j) qa = qa + ad_a[6][j] * Q[j];
 #pragma unroll
-            for (int j = 1; j < 7; ++j) qe = qe + ca_e[j] * Q[j];
+            for (int j = 1; j < 7; ++j) qe = qe + ad_e[j] * Q[j];
             const float l1 = l + hs * qa, err_a = hs * qe;
             cnf_tile<DT> tol;
 #pragma unroll
             for (int c = 0; c < DT; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    float acc = ca_e[0] * K[0].v[c][r];
+                    float acc = ad_e[0] * K[0].v[c][r];
 #pragma unroll
-                    for (int j = 1; j < 7; ++j) acc = acc + ca_e[j] * K[j].v[c][r];
+                    for (int j = 1; j < 7; ++j) acc = acc + ad_e[j] * K[j].v[c][r];
                     k.v[c][r] = hs * acc;
                     tol.v[c][r] = atol + rtol * fmaxf(fabsf(y.v[c][r]), fabsf(xs.v[c][r]));
                 }
             const float ra = want ? fabsf(err_a) / (atol + rtol * fmaxf(fabsf(l), fabsf(l1))) : 0.f;
-            const float ratio = ca_nmax(ca_rms<DT>(k, tol, D, h), ra);
+            const float ratio = ad_nmax(ad_rms<DT>(k, tol, D, h), ra);
             const bool finite = ratio - ratio == 0.f;
             const bool accept = act && finite && ratio <= 1.f;
             float factor = 10.f;
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_a
 #pragma unroll
                 for (int r = 0; r < 16; ++r) y.v[c][r] = __builtin_nanf("");
         }
-        cnf_dense_store<DT>(a.y, y, row, D, live, h);
+        cnf_store_row<DT>(a.y, y, row, D, live, h);
         if (live && h == 0) {
             if (want) a.ldj[row] = l;
             a.stats[row * 3 + 0] = n_acc;
@@ -273,7 +267,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_adaptive_kernel(const ca_a
 }
 
 // the LDS plan: the forward images, then c / C (always in LDS: at most 64 x 64 floats).  -> floats used
-size_t ca_plan(const sx_cnf_net &net, ca_args &a) {
+size_t ad_plan(const sx_cnf_net &net, ad_args &a) {
     const int NH = net.n_layers - 1, HT = cnf_dense_hidden_tiles(net);
     size_t off = cnf_dense_plan(net, a);
     a.base_tr = (int)off;
@@ -281,22 +275,22 @@ size_t ca_plan(const sx_cnf_net &net, ca_args &a) {
     return off;
 }
 
-int ca_check_net(const sx_cnf_net *net_host) {
+int ad_check_net(const sx_cnf_net *net_host) {
     return cnf_dense_check_net("sx_cnf_adaptive_flow", net_host, SX_CNF_ADAPTIVE_MAX_DIM, 128, SX_CNF_ADAPTIVE_MAX_HIDDEN);
 }
 
 }  // namespace
 
 extern "C" size_t sx_cnf_adaptive_lds_bytes(const sx_cnf_net *net_host) {
-    if (ca_check_net(net_host) != SX_OK) return 0;
-    ca_args a{};
-    return ca_plan(*net_host, a) * 4;
+    if (ad_check_net(net_host) != SX_OK) return 0;
+    ad_args a{};
+    return ad_plan(*net_host, a) * 4;
 }
 
 extern "C" int sx_cnf_adaptive_flow(const sx_cnf_net *net_host, const float *x, const float *latent, float *y, float *ldj, int32_t *stats,
                                     int64_t n_rows, float t0, float t1, float rtol, float atol, float first_step, int32_t max_num_steps,
                                     int32_t want_trace, void *stream) {
-    const int rc = ca_check_net(net_host);
+    const int rc = ad_check_net(net_host);
     if (rc != SX_OK) return rc;
     const sx_cnf_net &net = *net_host;
     SX_REQUIRE(n_rows >= 0, "sx_cnf_adaptive_flow: negative n_rows");
@@ -308,9 +302,9 @@ extern "C" int sx_cnf_adaptive_flow(const sx_cnf_net *net_host, const float *x, 
     SX_REQUIRE(first_step == first_step, "sx_cnf_adaptive_flow: first_step is not a number");
     SX_REQUIRE(max_num_steps >= 1 && max_num_steps <= SX_CNF_ADAPTIVE_MAX_STEPS, "sx_cnf_adaptive_flow: max_num_steps must be in 1..%d (got %d)",
                SX_CNF_ADAPTIVE_MAX_STEPS, max_num_steps);
-    ca_args a{};
+    ad_args a{};
     a.net = net;
-    const size_t lds = ca_plan(net, a) * 4;
+    const size_t lds = ad_plan(net, a) * 4;
     SX_REQUIRE(lds <= SX_CNF_LDS_BYTES, "sx_cnf_adaptive_flow: the padded weights need %zu bytes of LDS (budget %d)", lds, SX_CNF_LDS_BYTES);
     if (n_rows == 0) return SX_OK;
     a.x = x; a.latent = latent; a.y = y; a.ldj = ldj; a.stats = stats; a.n_rows = n_rows;

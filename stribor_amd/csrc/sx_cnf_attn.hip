@@ -308,19 +308,18 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_attn_flow_kernel(const ca_
     const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
     const bool want = a.want_ldj != 0;
     const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
-    const int rows_per_pass = cnf_rows_per_pass(N);
-    const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
+    const int64_t n_passes = cnf_set_passes(N, a.n_rows);
     int *flags = reinterpret_cast<int *>(cnf_smem + a.base_flag);
+    cnf_set_pos sp;
     ca_pos p;
-    p.rho = wave * 32 + (lane & 31);
+    p.rho = sp.rho = wave * 32 + (lane & 31);          // (cnf_set_slot, spelt with this kernel's `wave`: the call compiles to other code)
     int area = 0;
-    // (every bound of this loop is uniform over the workgroup: all four waves make every pass and meet at every barrier)
     for (int64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const int64_t base = pass * rows_per_pass, left = a.n_rows - base;
-        const int n_here = left < rows_per_pass ? (int)left : rows_per_pass;
-        const bool live = p.rho < n_here;
-        const int64_t row = base + p.rho;
-        p.first = live ? (p.rho / N) * N : p.rho;
+        cnf_set_pass(sp, pass, N, a.n_rows);
+        const int n_here = sp.n_here;
+        const bool live = sp.live;
+        const int64_t row = sp.row;
+        p.first = sp.first;
         p.n = live ? N : 1;
         if (32 * wave < n_here) {
             const int last = 32 * wave + 31 < n_here - 1 ? 32 * wave + 31 : n_here - 1;

@@ -39,7 +39,7 @@ __device__ __forceinline__ f32x16 ca_scores(const f32x16 &qm, const float *kb, i
 __device__ __forceinline__ void ca_pv(f32x16 &acc, const f32x16 &w, const float *vb, bool e_in) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const float v = vb[((r & 3) + 8 * (r >> 2)) * CA_LD];
+        const float v = vb[sx_kmap(r, 0) * CA_LD];
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(e_in ? v : 0.f, w[r], acc, 0, 0, 0);
     }
 }

@@ -1,18 +1,23 @@
-// What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip, sx_cnf_attn.hip) and the training
-// kernels of the dense CNF (sx_cnf_train.hip) have in common:
+// What the one-launch CNF kernels (sx_cnf.hip, sx_cnf_adaptive.hip, sx_cnf_exact.hip, sx_cnf_set.hip, sx_cnf_exact_set.hip, sx_cnf_attn.hip,
+// sx_cnf_exact_attn.hip), the training kernels of the dense CNF (sx_cnf_train.hip) and the Deep Sets conditioner (sx_equivariant.hip)
+// have in common:
 //   * the layout: a workgroup of 4 waves, one wave = 32 rows on the MFMA column (lane & 31), features on the C rows, a 32-feature tile
 //     of a row = one f32x16 C fragment = the B operand of the next GEMM; feature sx_kmap(r, h) (sx_common.h) sits in register r of
 //     lane half h;
-//   * the seven activations whose derivative is a function of the activation's OUTPUT;
+//   * the seven activations whose derivative is a function of the activation's OUTPUT, and their sweeps over tiles;
+//   * a row's load and store in C-fragment order;
 //   * LDS images in A-fragment order, their staging, and the exact-fp32 product against them (v_mfma_f32_32x32x2_f32);
 //   * the fixed grid and the euler / midpoint / rk4 (3/8 rule) tableau.  The files that include this header are compiled with
 //     -ffp-contract=off: the tableau's parenthesisation is the reference solver's sequence of roundings;
+//   * sets: a workgroup's pass over whole sets, where a lane stands in it (cnf_set_pos, cnf_set_pass) and the ordered set sum through
+//     LDS (cnf_setsum) -- the set CNF kernels and both Deep Sets kernels;
 //   * the per-call argument checks, and cnf_launch: sx_common.h's sx_launch_capped at this family's workgroup size and LDS limit.
 // The weight-gradient contraction of the training kernels is not here: sx_train_contract.h.
-// sx_cnf.hip and sx_cnf_train.hip take it through sx_cnf_dense.h, which adds what the two dense files share with each other alone;
+// sx_cnf.hip, sx_cnf_adaptive.hip and sx_cnf_train.hip take it through sx_cnf_dense.h, which adds what the dense files share with each other alone;
 // they use all of it but cnf_act_all (sx_cnf_dense.h's sweep keeps the widest dense kernel free of spills) and cnf_latent_packed.
-// sx_cnf_exact.hip and sx_cnf_exact_set.hip take it through sx_cnf_exact_common.h, which does the same for the two exact-trace files.
-// Everything here has internal linkage: seven translation units include it (the six above, and sx_base.hip for the MFMA layout).
+// sx_cnf_exact.hip, sx_cnf_exact_set.hip and sx_cnf_exact_attn.hip take it through sx_cnf_exact_common.h, which does the same for the
+// exact-trace files; the two attention files add sx_cnf_attn_common.h.
+// Everything here has internal linkage: ten translation units include it (the nine above, and sx_base.hip for the MFMA layout).
 #pragma once
 #include "sx_common.h"
 
@@ -67,6 +72,18 @@ __device__ __forceinline__ void cnf_act_all(cnf_tile<T> &v, int act) {
         for (int r = 0; r < 16; ++r) v.v[m][r] = cnf_act(v.v[m][r], act);
 }
 
+// v <- act'(v) from v = act(v): one tile (inlined on purpose: an out-of-line call would spill the live stage vectors around it), T tiles
+__device__ __forceinline__ void cnf_dact_tile(f32x16 &v, int act) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = cnf_dact(v[r], act);
+}
+
+template <int T>
+__device__ __forceinline__ void cnf_dact_all(cnf_tile<T> &v, int act) {
+#pragma unroll
+    for (int m = 0; m < T; ++m) cnf_dact_tile(v.v[m], act);
+}
+
 // feature 32m + kmap(r, h) of a padded vector at `vb` (already offset by 4 * h)
 __device__ __forceinline__ float cnf_vec(const float *vb, int m, int r) { return vb[32 * m + 8 * (r >> 2) + (r & 3)]; }
 
@@ -84,6 +101,32 @@ __device__ __forceinline__ float cnf_pick(const f32x16 &v, int i) {
 #pragma unroll
     for (int r = 1; r < 16; ++r) s = (i == r) ? v[r] : s;
     return s;
+}
+
+// ---- rows in C-fragment order ------------------------------------------------------------------------------------------------------
+// the lane's row of a [n, D] array as a state of T tiles: register r of tile c <- feature 32c + sx_kmap(r, h) (h = lane >> 5), 0
+// beyond D and on a row that is not live; and back (a row that is not live is not stored)
+template <int T>
+__device__ __forceinline__ void cnf_load_row(cnf_tile<T> &v, const float *p, int64_t row, int D, bool live, int h) {
+#pragma unroll
+    for (int c = 0; c < T; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int f = 32 * c + sx_kmap(r, h);
+            v.v[c][r] = (live && f < D) ? p[row * D + f] : 0.f;
+        }
+}
+
+template <int T>
+__device__ __forceinline__ void cnf_store_row(float *p, const cnf_tile<T> &v, int64_t row, int D, bool live, int h) {
+    if (!live) return;
+#pragma unroll
+    for (int c = 0; c < T; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int f = 32 * c + sx_kmap(r, h);
+            if (f < D) p[row * D + f] = v.v[c][r];
+        }
 }
 
 // LDS image of a matrix block: MT x KT A-operand tiles of 1024 floats (tile (m, c), float g*256 + lane*4 + j holds
@@ -169,7 +212,7 @@ __device__ __forceinline__ void cnf_latent_packed(cnf_tile<HT> &lat, const float
     if (L > 0) {
         const int LT = (L + 31) >> 5;
         for (int c = 0; c < LT; ++c) {
-            f32x16 lb;
+            f32x16 lb;          // (sx_kmap(r, h) by hand: with the call, or a shared tile load, every exact-trace kernel is allocated differently)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int f = 32 * c + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -261,10 +304,92 @@ __device__ __forceinline__ void cnf_tableau(int solver, int st, float ta, float 
     }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------------------
-// workgroups that cover n_rows: independent rows (a wave per 32), or whole sets (floor(128 / set_size) sets per pass)
-inline int64_t cnf_row_blocks(int64_t n_rows) { return ((n_rows + 31) / 32 + SX_CNF_WAVES - 1) / SX_CNF_WAVES; }
+// ---- sets --------------------------------------------------------------------------------------------------------------------------
+// A workgroup's 128 row slots take floor(128 / N) WHOLE sets of N = set_size contiguous rows per pass: sets never straddle
+// workgroups, they may straddle waves.  Slots past the last set are padding: they compute on zeros and are never stored.
 __host__ __device__ inline int cnf_rows_per_pass(int set_size) { return (SX_CNF_ROWS / set_size) * set_size; }
+__device__ __forceinline__ int64_t cnf_set_passes(int N, int64_t n_rows) {
+    const int rows_per_pass = cnf_rows_per_pass(N);
+    return (n_rows + rows_per_pass - 1) / rows_per_pass;
+}
+
+// where a lane stands in its workgroup's pass
+struct cnf_set_pos {
+    int rho;            // row slot 0 .. SX_CNF_ROWS - 1
+    int first;          // the first slot of the row's set (a padding slot: itself)
+    int n_here;         // rows of this pass
+    int n_sets;         // whole sets of this pass (n_here / N)
+    bool live;          // the slot holds a row
+    int64_t row;        // that row
+};
+
+// the lane's row slot: the same in every pass
+__device__ __forceinline__ int cnf_set_slot(int lane) { return (threadIdx.x >> 6) * 32 + (lane & 31); }
+
+// the lane's place in pass `pass`, from p.rho = cnf_set_slot(lane) (for pass = blockIdx.x; pass < cnf_set_passes(); pass += gridDim.x:
+// every bound of that loop is uniform over the workgroup, so all four waves make every pass and meet at every barrier); -> the rows
+// of the pass
+__device__ __forceinline__ void cnf_set_pass(cnf_set_pos &p, int64_t pass, int N, int64_t n_rows) {
+    const int rows_per_pass = cnf_rows_per_pass(N);
+    const int64_t base = pass * rows_per_pass, left = n_rows - base;
+    p.n_here = left < rows_per_pass ? (int)left : rows_per_pass;
+    p.live = p.rho < p.n_here;
+    p.row = base + p.rho;
+    p.first = p.live ? (p.rho / N) * N : p.rho;
+    p.n_sets = p.n_here / N;
+}
+
+// The ordered set sum: out = the sum of `in` over the rows of the lane's set, e_out = that of the per-row scalar e_in (both lane
+// halves pass the same e_in).  Every lane writes its row's features to the LDS scratch at float offset `scratch`, [SX_CNF_ROWS][LD]
+// with LD >= 32 T + 4 (the column after the features carries the scalar along), one thread per (set, column) adds the set's N rows
+// IN ROW ORDER into the set's first row, and every lane reads its set's first row back.  The order of the additions depends on the
+// position inside the set only, so a set's result depends neither on its slot nor on its neighbours.
+//   * three workgroup barriers: EVERY thread of the workgroup must call it, padding waves included, under workgroup-uniform control;
+//   * `out` may alias `in`;
+//   * N == 1 needs no exchange (and meets no barrier).
+template <int T, int LD>
+__device__ __forceinline__ void cnf_setsum(int scratch, int N, const cnf_set_pos &p, const cnf_tile<T> &in, cnf_tile<T> &out, float e_in, float &e_out,
+                                           int lane) {
+    if (N == 1) {
+        out = in;
+        e_out = e_in;
+        return;
+    }
+    float *xs = cnf_smem + scratch;
+    const int h = lane >> 5;
+    __syncthreads();                    // the reads of the previous exchange are over
+    float *mine = xs + p.rho * LD + 4 * h;
+#pragma unroll
+    for (int m = 0; m < T; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<f32x4 *>(mine + 32 * m + 8 * g) = f32x4{in.v[m][4 * g], in.v[m][4 * g + 1], in.v[m][4 * g + 2], in.v[m][4 * g + 3]};
+    if (h == 0) xs[p.rho * LD + 32 * T] = e_in;
+    __syncthreads();
+    constexpr int COLS = 32 * T + 1;
+    const int n_pairs = p.n_sets * COLS;
+    for (int q = threadIdx.x; q < n_pairs; q += SX_CNF_THREADS) {
+        const int s = q / COLS, f = q - s * COLS;
+        float *col = xs + (s * N) * LD + f;
+        float acc = col[0];
+        for (int j = 1; j < N; ++j) acc = acc + col[j * LD];
+        col[0] = acc;
+    }
+    __syncthreads();
+    const float *src = xs + p.first * LD + 4 * h;
+#pragma unroll
+    for (int m = 0; m < T; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 32 * m + 8 * g);
+            out.v[m][4 * g] = v.x; out.v[m][4 * g + 1] = v.y; out.v[m][4 * g + 2] = v.z; out.v[m][4 * g + 3] = v.w;
+        }
+    e_out = xs[p.first * LD + 32 * T];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+// workgroups that cover n_rows: independent rows (a wave per 32), or whole sets (a pass each)
+inline int64_t cnf_row_blocks(int64_t n_rows) { return ((n_rows + 31) / 32 + SX_CNF_WAVES - 1) / SX_CNF_WAVES; }
 inline int64_t cnf_set_blocks(int64_t n_rows, int set_size) { return (n_rows + cnf_rows_per_pass(set_size) - 1) / cnf_rows_per_pass(set_size); }
 
 // the per-call arguments every flow call takes; `fn`: the entry point's name (set_size 1: rows are independent)

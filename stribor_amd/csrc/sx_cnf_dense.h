@@ -4,7 +4,8 @@
 // y is sx_cnf_flow's by construction:
 //   * device: the hidden-layer evaluation and the output layer (macros, which both files expand: see there), the activation sweep;
 //     and, as functions that sx_cnf_train.hip alone calls (sx_cnf.hip keeps the same statements inline, see its header), the staging
-//     of the forward images, biases and time column, the row load / store of a state and the latent share of the first layer;
+//     of the forward images, biases and time column and the latent share of the first layer (a state's row load / store is
+//     sx_cnf_common.h's cnf_load_row / cnf_store_row);
 //   * host: the network validator (the entry point's name and its three limits are arguments), the hidden-tile count and the LDS plan
 //     of the forward images, to which each file appends its own parts.
 // The flavour of every device function is the one with which all instantiations of both files build without scratch (they sit at the
@@ -77,30 +78,6 @@ __device__ __forceinline__ void cnf_dense_stage(const cnf_dense_args &a) {
     }
     cnf_stage(net.layer[NH].W, D, Hl, Hl, 0, DT, HT, a.base_w[NH]);
     cnf_stage_vec(net.layer[NH].b, D, 1, DT * 32, a.base_b[NH]);
-}
-
-// the lane's row of a [n, D] array as a state of DT tiles (0 beyond the live rows and features), and back
-template <int DT>
-__device__ __forceinline__ void cnf_dense_load(cnf_tile<DT> &v, const float *p, int64_t row, int D, bool live, int h) {
-#pragma unroll
-    for (int c = 0; c < DT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int f = 32 * c + sx_kmap(r, h);
-            v.v[c][r] = (live && f < D) ? p[row * D + f] : 0.f;
-        }
-}
-
-template <int DT>
-__device__ __forceinline__ void cnf_dense_store(float *p, const cnf_tile<DT> &v, int64_t row, int D, bool live, int h) {
-    if (!live) return;
-#pragma unroll
-    for (int c = 0; c < DT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int f = 32 * c + sx_kmap(r, h);
-            if (f < D) p[row * D + f] = v.v[c][r];
-        }
 }
 
 // the latent share of the first layer: W1[:, 1 + D ..] . latent_row, once per row (its A fragments come straight from global memory:

@@ -18,7 +18,7 @@
 //   * the embedding's last layer puts slot kk at position kmap(kk >> 1, kk & 1): register c of lane half hh holds slot 2c + hh of the
 //     row -- the slot pair the MADE output keeps in tile c (register d, the two lane halves), so p is added to a tile's registers
 //     without a shuffle;
-//   * one exchange per evaluation (xs_pool; barriers as cs_setsum's): every lane writes its slots to a scratch [128][16], one thread
+//   * one exchange per evaluation (xs_pool; barriers as cnf_setsum's): every lane writes its slots to a scratch [128][16], one thread
 //     per (set, slot) walks the set's rows IN ELEMENT ORDER -- sum / mean: adds them into the set's first row; max: keeps the two
 //     largest values, duplicates counted -- and every lane reads its set's first row back: sum - own (mean: / max(N - 1, 1), a true
 //     division), or own == first ? second : first.  The order depends on the position inside the set only, so a set's result does not
@@ -62,18 +62,10 @@ __host__ __device__ constexpr xs_plan xs_make_plan(int HT, int NH, int OT) {
 
 struct xs_args : cnf_exact_args<sx_cnf_exact_set_net> {};
 
-// where a lane stands in its workgroup's pass
-struct xs_pos {
-    int rho;            // row slot 0 .. SX_CNF_ROWS - 1
-    int first;          // the first slot of the row's set (a padding slot: itself)
-    int n_sets;         // whole sets of this pass
-    bool live;          // the slot holds a row
-};
-
 // out[c] = the pooling over the OTHER rows of the lane's set of slot 2c + (lane >> 5), from the lane's own e[c].  `xs`: the exchange
 // scratch.  Uniform over the workgroup: every thread must call it.
 template <int OT>
-__device__ __forceinline__ void xs_pool(const xs_args &a, const xs_pos &p, float *xs, const float (&e)[OT], float (&out)[OT], int lane) {
+__device__ __forceinline__ void xs_pool(const xs_args &a, const cnf_set_pos &p, float *xs, const float (&e)[OT], float (&out)[OT], int lane) {
     const int N = a.net.set_size, pooling = a.net.pooling, h = lane >> 5;
     if (N == 1) {
 #pragma unroll
@@ -157,7 +149,7 @@ __device__ __forceinline__ void xs_embed(const cnf_tile<1> &xi, float t, float (
 
 // f(t, x) -> k (dimension i at register i of the lower lane half) and -- when `want` -- tr = sum_i jac_i, for the wave's 32 rows
 template <int HT, int NH, int OT>
-__device__ __forceinline__ void xs_eval(const xs_args &a, const xs_pos &pos, const f32x16 &xin, float t, const cnf_tile<HT> &lat, f32x16 &k, bool want, float &tr,
+__device__ __forceinline__ void xs_eval(const xs_args &a, const cnf_set_pos &pos, const f32x16 &xin, float t, const cnf_tile<HT> &lat, f32x16 &k, bool want, float &tr,
                                         int lane) {
     constexpr xs_plan p = xs_make_plan(HT, NH, OT);
     const int act = a.net.act;
@@ -191,19 +183,13 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_exact_set_kernel(const xs_
     const int lane = threadIdx.x & 63, h = lane >> 5, D = a.net.dim, L = a.net.latent_dim, N = a.net.set_size;
     const bool want = a.want_ldj != 0;
     const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
-    const int rows_per_pass = cnf_rows_per_pass(N);
-    const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
-    xs_pos p;
-    p.rho = (threadIdx.x >> 6) * 32 + (lane & 31);
-    // (every bound of this loop is uniform over the workgroup: all four waves make every pass and meet at every barrier)
+    const int64_t n_passes = cnf_set_passes(N, a.n_rows);
+    cnf_set_pos p;
+    p.rho = cnf_set_slot(lane);
     for (int64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const int64_t base = pass * rows_per_pass, left = a.n_rows - base;
-        const int n_here = left < rows_per_pass ? (int)left : rows_per_pass;
-        const bool live = p.rho < n_here;
-        const int64_t row = base + p.rho;
-        p.live = live;
-        p.first = live ? (p.rho / N) * N : p.rho;
-        p.n_sets = n_here / N;
+        cnf_set_pass(p, pass, N, a.n_rows);
+        const bool live = p.live;
+        const int64_t row = p.row;
         CNF_EXACT_SOLVE_ROWS(HT, a, row, live, h, D, L, want, sgn, lane, xs_eval<HT, NH, OT>(a, p, xs.v[0], ts, lat, k.v[0], want, q, lane))
     }
 }

@@ -13,11 +13,9 @@
 //     the same solvers, grid, tableau roundings (-ffp-contract=off) and activations;
 //   * a workgroup of 4 waves owns 128 row slots and takes floor(128 / N) WHOLE sets per pass: sets never straddle workgroups, they
 //     may straddle waves.  Slots past the last set are padding: they compute on zeros and are never stored;
-//   * a set sum (cs_setsum): every lane writes its row's features to an LDS scratch [128][32 HT + 4] (the column after the features
-//     carries one scalar along), one thread per (set, column) adds the set's N rows IN ROW ORDER into the set's first row, every
-//     lane reads its set's first row back.  Three workgroup barriers; every wave reaches them (padding waves included) because the
-//     pass loop, the stage loop and `want` are uniform over the workgroup.  The order of the additions depends on the position
-//     inside the set only, so a set's result does not depend on its slot or on its neighbours.  N = 1 needs no exchange;
+//   * a set sum is sx_cnf_common.h's cnf_setsum through an LDS scratch [128][32 HT + 4], its additions in row order.  Every wave
+//     reaches its three barriers (padding waves included) because the pass loop, the stage loop and `want` are uniform over the
+//     workgroup;
 //   * per evaluation the sums taken are: x, h1(, h2) for the l2 branches, and for the trace d1 and d2 (two hidden layers; the scalar
 //     sum_j d2_j^T C_e d1_j rides with d2) or one scalar riding with h1 (one hidden layer);
 //   * time: per stage the first layer's bias is bias_1 + t_stage (A1[:, 0] + B1[:, 0]); the latent columns of A1 and G1 are constant
@@ -30,14 +28,6 @@
 #include "sx_cnf_common.h"
 
 namespace {
-
-template <int T>
-__device__ __forceinline__ void cs_dact_all(cnf_tile<T> &v, int act) {
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v.v[m][r] = cnf_dact(v.v[m][r], act);
-}
 
 struct cs_args {
     sx_cnf_set_net net;
@@ -55,56 +45,6 @@ struct cs_args {
     float t0, t1, step_size;
 };
 
-// where a lane stands in its workgroup's pass
-struct cs_pos {
-    int rho;            // row slot 0 .. SX_CNF_ROWS - 1
-    int first;          // the first slot of the row's set (a padding slot: itself)
-    int n_sets;         // whole sets of this pass
-};
-
-// out = the sum of `in` over the rows of the lane's set, e_out = that of the per-row scalar e_in (both lane halves pass the same
-// e_in).  LD = the scratch's row stride (floats).  Uniform over the workgroup: every thread must call it.
-template <int T, int LD>
-__device__ __forceinline__ void cs_setsum(const cs_args &a, const cs_pos &p, const cnf_tile<T> &in, cnf_tile<T> &out, float e_in, float &e_out,
-                                          int lane) {
-    const int N = a.net.set_size;
-    if (N == 1) {
-        out = in;
-        e_out = e_in;
-        return;
-    }
-    float *xs = cnf_smem + a.base_x;
-    const int h = lane >> 5;
-    __syncthreads();                    // the reads of the previous exchange are over
-    float *mine = xs + p.rho * LD + 4 * h;
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<f32x4 *>(mine + 32 * m + 8 * g) = f32x4{in.v[m][4 * g], in.v[m][4 * g + 1], in.v[m][4 * g + 2], in.v[m][4 * g + 3]};
-    if (h == 0) xs[p.rho * LD + 32 * T] = e_in;
-    __syncthreads();
-    constexpr int COLS = 32 * T + 1;
-    const int n_pairs = p.n_sets * COLS;
-    for (int q = threadIdx.x; q < n_pairs; q += SX_CNF_THREADS) {
-        const int s = q / COLS, f = q - s * COLS;
-        float *col = xs + (s * N) * LD + f;
-        float acc = col[0];
-        for (int j = 1; j < N; ++j) acc = acc + col[j * LD];
-        col[0] = acc;
-    }
-    __syncthreads();
-    const float *src = xs + p.first * LD + 4 * h;
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 32 * m + 8 * g);
-            out.v[m][4 * g] = v.x; out.v[m][4 * g + 1] = v.y; out.v[m][4 * g + 2] = v.z; out.v[m][4 * g + 3] = v.w;
-        }
-    e_out = xs[p.first * LD + 32 * T];
-}
-
 // acc += (rows 32m .. 32m + 31 of C matrix `ci`) . in
 template <int HT>
 __device__ __forceinline__ void cs_mma_c(f32x16 &acc, const cnf_tile<HT> &in, const cs_args &a, int ci, int m, int lane) {
@@ -121,7 +61,7 @@ __device__ __forceinline__ float cs_dot(const f32x16 &p, const f32x16 &q) {
 
 // f(t, x) and -- when `want` -- tr = the row's share of the set's divergence, for the wave's 32 rows
 template <int HT, int NH>
-__device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const f32x16 &xin, float t, const cnf_tile<HT> &lat, f32x16 &k, bool want,
+__device__ __forceinline__ void cs_eval(const cs_args &a, const cnf_set_pos &p, const f32x16 &xin, float t, const cnf_tile<HT> &lat, f32x16 &k, bool want,
                                         float &tr, int lane) {
     constexpr int LD = 32 * HT + 4;
     const int h = lane >> 5, act = a.net.act;
@@ -130,7 +70,7 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
     float unused;
     cnf_tile<1> xi, mx;
     xi.v[0] = xin;
-    cs_setsum<1, LD>(a, p, xi, mx, 0.f, unused, lane);
+    cnf_setsum<1, LD>(a.base_x, a.net.set_size, p, xi, mx, 0.f, unused, lane);
     const float *b1 = cnf_smem + a.base_b[0] + 4 * h, *w0 = cnf_smem + a.base_w0 + 4 * h;
     cnf_tile<HT> h1, m1;
 #pragma unroll
@@ -156,7 +96,7 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
                 }
             e = e + __shfl_xor(e, 32, 64);
         }
-        cs_setsum<HT, LD>(a, p, h1, m1, e, e_set, lane);
+        cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h1, m1, e, e_set, lane);
         f32x16 acc = {};
         cnf_mma<HT>(acc, h1, cnf_smem + a.base_a[1] + lane * 4);
         cnf_mma<HT>(acc, m1, cnf_smem + a.base_g[1] + lane * 4);
@@ -166,7 +106,7 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
         if (want) tr = (s + __shfl_xor(s, 32, 64)) + e_set;
     } else {
         cnf_tile<HT> h2, m2;
-        cs_setsum<HT, LD>(a, p, h1, m1, 0.f, unused, lane);
+        cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h1, m1, 0.f, unused, lane);
         const float *b2 = cnf_smem + a.base_b[1] + 4 * h;
 #pragma unroll
         for (int m = 0; m < HT; ++m) {
@@ -177,7 +117,7 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
             for (int r = 0; r < 16; ++r) h2.v[m][r] = acc[r] + cnf_vec(b2, m, r);
         }
         cnf_act_all<HT>(h2, act);
-        cs_setsum<HT, LD>(a, p, h2, m2, 0.f, unused, lane);
+        cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h2, m2, 0.f, unused, lane);
         {
             f32x16 acc = {};
             cnf_mma<HT>(acc, h2, cnf_smem + a.base_a[2] + lane * 4);
@@ -188,9 +128,9 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
         }
         if (want) {
             // h1 <- d1, m1 <- s1, h2 <- d2, m2 <- s2
-            cs_dact_all<HT>(h1, act);
-            cs_setsum<HT, LD>(a, p, h1, m1, 0.f, unused, lane);
-            cs_dact_all<HT>(h2, act);
+            cnf_dact_all<HT>(h1, act);
+            cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h1, m1, 0.f, unused, lane);
+            cnf_dact_all<HT>(h2, act);
             float s = 0.f, e = 0.f, e_set = 0.f;
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
@@ -202,7 +142,7 @@ __device__ __forceinline__ void cs_eval(const cs_args &a, const cs_pos &p, const
                 s += cs_dot(h2.v[m], v);
             }
             e = e + __shfl_xor(e, 32, 64);
-            cs_setsum<HT, LD>(a, p, h2, m2, e, e_set, lane);
+            cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h2, m2, e, e_set, lane);
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
                 f32x16 w = {};
@@ -246,18 +186,14 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_a
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const bool want = a.want_ldj != 0;
     const float sgn = a.t1 < a.t0 ? -1.f : 1.f;
-    const int rows_per_pass = cnf_rows_per_pass(N);
-    const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
-    cs_pos p;
-    p.rho = (threadIdx.x >> 6) * 32 + (lane & 31);
-    // (every bound of this loop is uniform over the workgroup: all four waves make every pass and meet at every barrier)
+    const int64_t n_passes = cnf_set_passes(N, a.n_rows);
+    cnf_set_pos p;
+    p.rho = cnf_set_slot(lane);
     for (int64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const int64_t base = pass * rows_per_pass, left = a.n_rows - base;
-        const int n_here = left < rows_per_pass ? (int)left : rows_per_pass;
-        const bool live = p.rho < n_here;
-        const int64_t row = base + p.rho;
-        p.first = live ? (p.rho / N) * N : p.rho;
-        p.n_sets = n_here / N;
+        cnf_set_pass(p, pass, N, a.n_rows);
+        const bool live = p.live;
+        const int64_t row = p.row;
+        // (the row loads and the store are written out: through cnf_load_row / cnf_store_row all four kernels are allocated differently)
         cnf_tile<1> y;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -276,7 +212,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_set_flow_kernel(const cs_a
                 const int f = 32 * c + sx_kmap(r, h);
                 lb.v[0][r] = (live && f < L) ? a.latent[row * L + f] : 0.f;
             }
-            cs_setsum<1, LD>(a, p, lb, ml, 0.f, unused, lane);
+            cnf_setsum<1, LD>(a.base_x, a.net.set_size, p, lb, ml, 0.f, unused, lane);
 #pragma unroll
             for (int m = 0; m < HT; ++m) {
                 const int wr = 32 * m + (lane & 31);

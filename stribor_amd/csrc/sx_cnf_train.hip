@@ -55,7 +55,8 @@ struct ct_args : cnf_dense_args {
     float t0, t1, step_size;
 };
 
-// d = act'(v) of a whole tile from a = act(v): one wave-uniform switch around the sweep, not one per element
+// d = act'(v) of a whole tile from a = act(v): one wave-uniform switch around the sweep, not one per element (sx_cnf_common.h's
+// cnf_dact_tile switches per element: other code here, see cnf_dense_act for the same choice)
 __device__ __forceinline__ void ct_dact_tile(const f32x16 &a, f32x16 &d, int act) {
     switch (act) {
         case SX_ACT_TANH:
@@ -171,8 +172,8 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_
         const int64_t row = grp * 32 + (lane & 31);
         const bool live = row < a.n_rows;
         ct_tile y, e, lat, u1, v;
-        cnf_dense_load<1>(y, a.x, row, D, live, h);
-        cnf_dense_load<1>(e, a.e, row, D, live, h);
+        cnf_load_row<1>(y, a.x, row, D, live, h);
+        cnf_load_row<1>(e, a.e, row, D, live, h);
         cnf_dense_latent<1>(a, lat, a.latent, row, live, lane);
         ct_row_constants<NH>(a, e, u1, v, lane);
         float l = 0.f;
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_
             float ta, tb;
             cnf_grid(a, sgn, i, ta, tb);
             const float dt = tb - ta, half = 0.5f * dt;
-            if (a.ckpt != nullptr) cnf_dense_store<1>(a.ckpt + (int64_t)i * a.n_rows * D, y, row, D, live, h);
+            if (a.ckpt != nullptr) cnf_store_row<1>(a.ckpt + (int64_t)i * a.n_rows * D, y, row, D, live, h);
             ct_tile k1, k2, xs = y;
             float q1 = 0.f, q2 = 0.f, ts = ta;
             for (int st = 0; st < n_stages; ++st) {
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void cnf_train_fwd_kernel(const ct_
                 cnf_tableau<1>(a.solver, st, ta, tb, dt, half, third, two_thirds, k, q, k1, k2, q1, q2, xs, ts, y, l);
             }
         }
-        cnf_dense_store<1>(a.y, y, row, D, live, h);
+        cnf_store_row<1>(a.y, y, row, D, live, h);
         if (live && h == 0) a.ldj[row] = l;
     }
 }
@@ -224,7 +225,7 @@ __device__ __forceinline__ void ct_take(f32x16 &v, const float *slot, int ld, in
     const int room = ld - c0 - 4 * (lane >> 5);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int f = (r & 3) + 8 * (r >> 2);
+        const int f = sx_kmap(r, 0);
         const float t = pr[f];                       // (inside the wave's scratch whatever f is)
         v[r] = (live && f < room) ? t : 0.f;
     }

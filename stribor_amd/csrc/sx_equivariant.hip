@@ -11,10 +11,8 @@
 //     the C rows, exact fp32 (v_mfma_f32_32x32x2_f32), weights in LDS in A-fragment order, cnf_launch and its pass loop;
 //   * a workgroup takes floor(128 / N) WHOLE sets per pass: sets never straddle workgroups, they may straddle waves.  Slots past
 //     the last set are padding: they compute on zeros (m = 1, c = 1) and are never stored;
-//   * a set sum (eq_setsum) is sx_cnf_set.hip's exchange: every lane writes its row to an LDS scratch [128][LD] (the column after the
-//     features carries one scalar along: the mask on the first exchange, so c costs nothing), one thread per (set, column) adds the
-//     set's N rows IN ROW ORDER into the set's first row, every lane reads its set's first row back.  The order of the additions
-//     depends on the position inside the set only: a set's result depends neither on its slot nor on its neighbours;
+//   * a set sum is sx_cnf_common.h's cnf_setsum through an LDS scratch [128][LD], its additions in row order; the scalar it carries
+//     along is the mask on the first exchange, so c costs nothing;
 //   * the descriptor holds the module's parameters themselves.  The A and B images of the layers go into LDS in layer order while
 //     they fit SX_CNF_LDS_BYTES beside the vectors and the scratch; an image that does not fit is not staged, and its A fragments are
 //     read from the parameter in global memory (bounds-checked scalar loads: the parameters are not padded, so cnf_mma_global's
@@ -57,59 +55,11 @@ struct eq_args {
 };
 
 // where a lane stands in its workgroup's pass
-struct eq_row {
-    int rho;            // row slot 0 .. SX_CNF_ROWS - 1
-    int first;          // the first slot of the row's set (a padding slot: itself)
-    int n_sets;         // whole sets of this pass
-    bool live;
-    int64_t row;
+struct eq_row : cnf_set_pos {
     float mi, c;        // the row's mask value (1 without a mask) and its set's divisor: sum of the mask, or N
 };
 
 __device__ __forceinline__ int eq_in_dim(const sx_equivariant_net &net, int l) { return l == 0 ? net.in_dim : net.out_dim[l - 1]; }
-
-// out = the sum of `in` over the rows of the lane's set, e_out = that of the per-row scalar e_in (both lane halves pass the same
-// e_in).  Uniform over the workgroup: every thread must call it.  `out` may be `in`.
-template <int T, int LD>
-__device__ __forceinline__ void eq_setsum(const eq_args &a, const eq_row &p, const cnf_tile<T> &in, cnf_tile<T> &out, float e_in, float &e_out,
-                                          int lane) {
-    const int N = a.net.set_size;
-    if (N == 1) {
-        out = in;
-        e_out = e_in;
-        return;
-    }
-    float *xs = cnf_smem + a.base_x;
-    const int h = lane >> 5;
-    __syncthreads();                    // the reads of the previous exchange are over
-    float *mine = xs + p.rho * LD + 4 * h;
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<f32x4 *>(mine + 32 * m + 8 * g) = f32x4{in.v[m][4 * g], in.v[m][4 * g + 1], in.v[m][4 * g + 2], in.v[m][4 * g + 3]};
-    if (h == 0) xs[p.rho * LD + 32 * T] = e_in;
-    __syncthreads();
-    constexpr int COLS = 32 * T + 1;
-    const int n_pairs = p.n_sets * COLS;
-    for (int q = threadIdx.x; q < n_pairs; q += SX_CNF_THREADS) {
-        const int s = q / COLS, f = q - s * COLS;
-        float *col = xs + (s * N) * LD + f;
-        float acc = col[0];
-        for (int j = 1; j < N; ++j) acc = acc + col[j * LD];
-        col[0] = acc;
-    }
-    __syncthreads();
-    const float *src = xs + p.first * LD + 4 * h;
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 32 * m + 8 * g);
-            out.v[m][4 * g] = v.x; out.v[m][4 * g + 1] = v.y; out.v[m][4 * g + 2] = v.z; out.v[m][4 * g + 3] = v.w;
-        }
-    e_out = xs[p.first * LD + 32 * T];
-}
 
 // acc += (rows 32m .. 32m + 31 of W) . in -- from the LDS image at `base`, or (base < 0) from the parameter W [out_dim, in_dim] itself
 template <int KT, bool G>
@@ -187,15 +137,10 @@ __device__ __forceinline__ void eq_hidden(const eq_args &a, int l, const cnf_til
 // the lane's place in pass `pass`, its x row (zeros on padding) and its mask value
 template <int KT0>
 __device__ __forceinline__ void eq_begin(const eq_args &a, int64_t pass, eq_row &p, cnf_tile<KT0> &x, int lane) {
-    const int N = a.net.set_size, rows_per_pass = cnf_rows_per_pass(N), h = lane >> 5, D = a.net.in_dim;
-    const int64_t base = pass * rows_per_pass, left = a.n_rows - base;
-    const int n_here = left < rows_per_pass ? (int)left : rows_per_pass;
-    p.rho = (threadIdx.x >> 6) * 32 + (lane & 31);
-    p.live = p.rho < n_here;
-    p.row = base + p.rho;
-    p.first = p.live ? (p.rho / N) * N : p.rho;
-    p.n_sets = n_here / N;
-    const float *xr = a.x + p.row * a.x_rs;
+    const int N = a.net.set_size, h = lane >> 5, D = a.net.in_dim;
+    p.rho = cnf_set_slot(lane);
+    cnf_set_pass(p, pass, N, a.n_rows);
+    const float *xr = a.x + p.row * a.x_rs;          // (cnf_load_row reads rows of stride D)
 #pragma unroll
     for (int c = 0; c < KT0; ++c)
 #pragma unroll
@@ -214,25 +159,24 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_fwd_kernel(const e
     eq_stage(a, KT0, HT, OT, false);
     __syncthreads();
     const int lane = threadIdx.x & 63, h = lane >> 5;
-    const int rows_per_pass = cnf_rows_per_pass(a.net.set_size);
-    const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
+    const int64_t n_passes = cnf_set_passes(a.net.set_size, a.n_rows);
     // (every bound of this loop is uniform over the workgroup: all four waves make every pass and meet at every barrier)
     for (int64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
         eq_row p;
         cnf_tile<KT0> x, S0;
         eq_begin<KT0>(a, pass, p, x, lane);
         float c;
-        eq_setsum<KT0, LD>(a, p, x, S0, p.mi, c, lane);
+        cnf_setsum<KT0, LD>(a.base_x, a.net.set_size, p, x, S0, p.mi, c, lane);
         if (a.mask != nullptr) p.c = c;
         cnf_tile<HT> hl, Sl;
         eq_hidden<KT0, HT, true>(a, 0, x, S0, p, hl, lane);
         float unused;
         if (NL == 3) {
             cnf_tile<HT> h1 = hl;
-            eq_setsum<HT, LD>(a, p, h1, Sl, 0.f, unused, lane);
+            cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h1, Sl, 0.f, unused, lane);
             eq_hidden<HT, HT, true>(a, 1, h1, Sl, p, hl, lane);
         }
-        eq_setsum<HT, LD>(a, p, hl, Sl, 0.f, unused, lane);
+        cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, hl, Sl, 0.f, unused, lane);
         float *yr = a.y + p.row * out_dim;
 #pragma nounroll
         for (int m = 0; m < OT; ++m) {
@@ -289,7 +233,7 @@ __device__ __forceinline__ void eq_bwd_layer(const eq_args &a, int l, const eq_r
 #pragma unroll
         for (int q = 0; q < 16; ++q) r.v[m][q] = masked ? (e.v[m][q] / p.c) * p.mi : e.v[m][q] / p.c;
     float unused;
-    eq_setsum<MT, LD>(a, p, r, r, 0.f, unused, lane);
+    cnf_setsum<MT, LD>(a.base_x, a.net.set_size, p, r, r, 0.f, unused, lane);
     if (masked) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
@@ -319,6 +263,7 @@ __device__ __forceinline__ void eq_bwd_layer(const eq_args &a, int l, const eq_r
     }
 }
 
+// dh <- act'(h) dh from hout = act(h) (a product, not cnf_dact_all's sweep in place)
 template <int T>
 __device__ __forceinline__ void eq_times_dact(cnf_tile<T> &dh, const cnf_tile<T> &hout, int act) {
 #pragma unroll
@@ -336,8 +281,7 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     float *sA = cnf_smem + a.base_scr + wave * 2 * SX_TC_SLOT, *sB = sA + SX_TC_SLOT;
     float *part = a.partial + ((int64_t)blockIdx.x * SX_CNF_WAVES + wave) * a.part_floats;
-    const int rows_per_pass = cnf_rows_per_pass(a.net.set_size);
-    const int64_t n_passes = (a.n_rows + rows_per_pass - 1) / rows_per_pass;
+    const int64_t n_passes = cnf_set_passes(a.net.set_size, a.n_rows);
     bool first = true;
     // (every bound of this loop, and every want flag, is uniform over the workgroup: all four waves meet at every barrier)
     for (int64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
@@ -345,17 +289,17 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
         cnf_tile<KT0> x, S0;
         eq_begin<KT0>(a, pass, p, x, lane);
         float c, unused;
-        eq_setsum<KT0, LD>(a, p, x, S0, p.mi, c, lane);
+        cnf_setsum<KT0, LD>(a.base_x, a.net.set_size, p, x, S0, p.mi, c, lane);
         if (a.mask != nullptr) p.c = c;
         // ---- the forward again: h_1 (, h_2), y
         cnf_tile<HT> h1, h2, Sl;
         eq_hidden<KT0, HT, false>(a, 0, x, S0, p, h1, lane);
         if (NL == 3) {
-            eq_setsum<HT, LD>(a, p, h1, Sl, 0.f, unused, lane);
+            cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h1, Sl, 0.f, unused, lane);
             eq_hidden<HT, HT, false>(a, 1, h1, Sl, p, h2, lane);
         }
         const cnf_tile<HT> &hl = NL == 3 ? h2 : h1;
-        eq_setsum<HT, LD>(a, p, hl, Sl, 0.f, unused, lane);
+        cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, hl, Sl, 0.f, unused, lane);
         // ---- e_L = final_act'(y) gy (zero on padding rows and padded features)
         cnf_tile<OT> e;
         const float *gr = tc_here(a.gy + p.row * out_dim);
@@ -374,13 +318,13 @@ __global__ __launch_bounds__(SX_CNF_THREADS) void equivariant_bwd_kernel(const e
         eq_bwd_layer<HT, OT, LD>(a, NL - 1, p, e, hl, Sl, dh, true, part, first, sA, sB, lane);
         if (NL == 3) {
             eq_times_dact<HT>(dh, h2, act);
-            if (a.want_b[1]) eq_setsum<HT, LD>(a, p, h1, Sl, 0.f, unused, lane);
+            if (a.want_b[1]) cnf_setsum<HT, LD>(a.base_x, a.net.set_size, p, h1, Sl, 0.f, unused, lane);
             cnf_tile<HT> e2 = dh;
             eq_bwd_layer<HT, HT, LD>(a, 1, p, e2, h1, Sl, dh, true, part, first, sA, sB, lane);
         }
         eq_times_dact<HT>(dh, h1, act);
         cnf_tile<KT0> dx;
-        if (a.want_b[0]) eq_setsum<KT0, LD>(a, p, x, S0, 0.f, unused, lane);
+        if (a.want_b[0]) cnf_setsum<KT0, LD>(a.base_x, a.net.set_size, p, x, S0, 0.f, unused, lane);
         eq_bwd_layer<KT0, HT, LD>(a, 0, p, dh, x, S0, dx, a.dx != nullptr, part, first, sA, sB, lane);
         if (a.dx != nullptr && p.live) {
             float *dr = tc_here(a.dx + p.row * D);

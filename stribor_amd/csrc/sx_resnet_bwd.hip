@@ -179,7 +179,7 @@ __device__ __forceinline__ void rb_unstash(rtile<T> &t, const float *src) {
 // Rows move between global memory and the tiles through ONE 64-bit address per lane and array (rb_row_off) plus compile-time
 // element offsets: per-element addresses would cost two registers each, for every array, across the whole iteration.
 // element (c, r) of a lane: feature fo + 4 h, fo = rb_feat(c, r), at p[rb_row_off + fo]
-__device__ __forceinline__ constexpr int rb_feat(int c, int r) { return 32 * c + (r & 3) + 8 * (r >> 2); }
+__device__ __forceinline__ constexpr int rb_feat(int c, int r) { return 32 * c + sx_kmap(r, 0); }
 
 template <int DT>
 __device__ __forceinline__ void rb_load_rows(rtile<DT> &t, const float *src, int64_t off, bool live, int D4) {
