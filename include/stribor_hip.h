@@ -1184,6 +1184,58 @@ size_t sx_equivariant_bwd_partial_floats(const sx_equivariant_net *net_host, int
 int sx_equivariant_bwd(const sx_equivariant_net *net_host, const float *x, int64_t x_rs, const float *mask, int64_t mask_rs,
                        const float *gy, float *dx, float *partial, const sx_equivariant_grads *grads, int64_t n_rows, void *stream);
 
+/* ---- Training the time-conditioned affine coupling (ContinuousAffineCoupling, stribor/flows/coupling.py:98-213, with the time nets
+ * of stribor/net/time_net.py:6-47; csrc/sx_time_coupling_bwd.hip) --------------------------------------------------------------
+ * The layer, for one row (m: the 0/1 mask, live = 1 - m; coupling.py:147-154, 199-209):
+ *   z = [x (.) m (zeros when dim == 1), latent, t (concat_time)],  h = act(W1 z + b1),  (ls | sh) = W2 h + b2,
+ *   (ts | th) = time_net(t) (chunk(2); a half of width 1 broadcasts over the columns),  a = ls (.) ts,  c = sh (.) th,
+ *   reverse == 0:  y = live (.) (x e^a + c) + m (.) x        reverse != 0:  y = live (.) (x - c) e^-a + m (.) x
+ *   ldj = ldj_scale * sum live (.) a   (ldj_scale: +1 for forward_and_log_det_jacobian in both directions, -1 for
+ *   inverse_and_log_det_jacobian, coupling.py:211-213)
+ * The forward is the fused program's (sx_flow_run); this is its backward, which recomputes h, ls, sh and a from x, latent and t in
+ * exact fp32 (v_mfma_f32_32x32x2_f32).  Only the columns of x with m = 1 reach the conditioner and only the live rows of W2 matter:
+ * the kernel stages pruned images, and writes zeros to the gradient entries pruning skipped. */
+#define SX_TIME_COUPLING_BWD_MAX_DIM    64
+#define SX_TIME_COUPLING_BWD_MAX_IN     64      /* dim + latent_dim */
+#define SX_TIME_COUPLING_BWD_MAX_HIDDEN 64
+typedef struct {
+    const float *W1;          /* [hidden, dim + latent_dim + concat_time] row-major; the time column is the last                  */
+    const float *b1;          /* [hidden]                                                                                       */
+    const float *W2;          /* [2 dim, hidden]: the log-scale rows, then the shift rows (chunk(2), coupling.py:199)           */
+    const float *b2;          /* [2 dim]                                                                                        */
+    const float *time_scale;  /* the time net's `scale`, [2 time_half]; NULL for SX_TIME_IDENTITY                               */
+    uint32_t mask[2];         /* bit c & 31 of word c >> 5: m_c = 1 (the column passes through and conditions)                  */
+    int32_t dim;              /* 1..SX_TIME_COUPLING_BWD_MAX_DIM                                                                */
+    int32_t latent_dim;       /* 0..; dim + latent_dim <= SX_TIME_COUPLING_BWD_MAX_IN                                           */
+    int32_t hidden;           /* 1..SX_TIME_COUPLING_BWD_MAX_HIDDEN (one hidden layer)                                          */
+    int32_t act;              /* SX_ACT_IDENTITY .. SX_ACT_LEAKYRELU (the derivative is taken from the activation's output)     */
+    int32_t time_kind;        /* SX_TIME_IDENTITY .. SX_TIME_LOG                                                                */
+    int32_t time_half;        /* width of a half of the time embedding: dim or 1                                                */
+    int32_t concat_time;      /* 1: t is the conditioner's last input (coupling.py:152-153)                                     */
+    int32_t pad_;
+} sx_time_coupling_net;
+typedef struct {
+    float *dW1, *db1, *dW2, *db2;      /* the shapes of W1, b1, W2, b2; NULL: not wanted                                         */
+    float *dtime;                      /* [2 dim]: per column, the gradient of the scale entry it reads (time_half == 1: the     */
+} sx_time_coupling_grads;              /* caller sums each half); NULL: not wanted                                              */
+
+/* Bytes of LDS a launch stages for this layer: the pruned images of W1 and W2, their transposed images, the vectors and the
+ * contraction slots; 0 for a layer outside the coverage (the bounds above, a mask bit beyond dim, no live column) or beyond
+ * SX_CNF_LDS_BYTES.  Reads the integer fields only. */
+size_t sx_time_coupling_bwd_lds_bytes(const sx_time_coupling_net *net_host);
+
+/* The backward at gy = dloss/dy [n_rows, dim] and gl = dloss/dldj [n_rows] (either may be NULL: zeros; not both), from the saved
+ * x [n_rows, dim], latent [n_rows, latent_dim] and t [n_rows], all contiguous fp32:
+ *   gx [n_rows, dim], glatent [n_rows, latent_dim], gt [n_rows] and the parameter gradients of `grads` (NULL, or NULL entries: not
+ *   wanted; dW1 / db1 / dW2 / db2 in the parameter's own layout).
+ * partial: sx_time_coupling_bwd_partial_floats(net, n_rows) floats of scratch when a parameter gradient is wanted (needs no
+ * initialisation).  Two launches (the kernel and the ordered sum of its per-wave partials), one when no parameter gradient is
+ * wanted; no atomics: the same inputs give the same bits. */
+size_t sx_time_coupling_bwd_partial_floats(const sx_time_coupling_net *net_host, int64_t n_rows);
+int sx_time_coupling_bwd(const sx_time_coupling_net *net_host, const float *x, const float *latent, const float *t, const float *gy,
+                         const float *gl, float *gx, float *glatent, float *gt, float *partial, const sx_time_coupling_grads *grads,
+                         int64_t n_rows, int32_t reverse, float ldj_scale, void *stream);
+
 /* LDS bytes and grid the launcher will use for a program (introspection for tests/bench). */
 int sx_flow_launch_info(const sx_program *prog_host, int64_t n_rows, int32_t *grid, int32_t *block,
                         int32_t *lds_bytes);

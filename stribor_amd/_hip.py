@@ -73,6 +73,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_cnf_train_lds_bytes', 'sx_cnf_train_partial_floats', 'sx_cnf_train_fwd', 'sx_cnf_train_bwd',
            'sx_cnf_adaptive_lds_bytes', 'sx_cnf_adaptive_flow',
            'sx_equivariant_lds_bytes', 'sx_equivariant_bwd_partial_floats', 'sx_equivariant_fwd', 'sx_equivariant_bwd',
+           'sx_time_coupling_bwd_lds_bytes', 'sx_time_coupling_bwd_partial_floats', 'sx_time_coupling_bwd',
            'sx_base_logprob', 'sx_normal_bwd_partial_floats', 'sx_normal_logprob_bwd', 'sx_mvn_lds_bytes', 'sx_mvn_logprob']
 
 # base densities (include/stribor_hip.h: sx_base_logprob / sx_mvn_logprob)
@@ -105,6 +106,9 @@ ATTENTION_MAX_HEAD_DIM = 128
 # Deep Sets conditioner (include/stribor_hip.h: sx_equivariant_fwd / sx_equivariant_bwd)
 EQUIVARIANT_MAX_SIZE, EQUIVARIANT_MAX_IN, EQUIVARIANT_MAX_HIDDEN, EQUIVARIANT_MAX_OUT = 128, 64, 64, 128
 EQUIVARIANT_BWD_MAX_IN, EQUIVARIANT_BWD_MAX_HIDDEN, EQUIVARIANT_BWD_MAX_OUT = 32, 64, 64
+
+# training the time-conditioned affine coupling (include/stribor_hip.h: sx_time_coupling_bwd)
+TIME_COUPLING_BWD_MAX_DIM, TIME_COUPLING_BWD_MAX_IN, TIME_COUPLING_BWD_MAX_HIDDEN = 64, 64, 64
 
 
 class HipLibraryMissing(RuntimeError):
@@ -206,6 +210,16 @@ class sx_equivariant_net(C.Structure):
 
 class sx_equivariant_grads(C.Structure):
     _fields_ = [('dA', C.c_void_p * 3), ('da', C.c_void_p * 3), ('dB', C.c_void_p * 3), ('db', C.c_void_p * 3)]
+
+
+class sx_time_coupling_net(C.Structure):
+    _fields_ = [('W1', C.c_void_p), ('b1', C.c_void_p), ('W2', C.c_void_p), ('b2', C.c_void_p), ('time_scale', C.c_void_p),
+                ('mask', C.c_uint32 * 2), ('dim', C.c_int32), ('latent_dim', C.c_int32), ('hidden', C.c_int32), ('act', C.c_int32),
+                ('time_kind', C.c_int32), ('time_half', C.c_int32), ('concat_time', C.c_int32), ('pad_', C.c_int32)]
+
+
+class sx_time_coupling_grads(C.Structure):
+    _fields_ = [('dW1', C.c_void_p), ('db1', C.c_void_p), ('dW2', C.c_void_p), ('db2', C.c_void_p), ('dtime', C.c_void_p)]
 
 
 class sx_sn_layer(C.Structure):
@@ -393,6 +407,13 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_equivariant_fwd.argtypes = [C.POINTER(sx_equivariant_net), vp, i64, vp, i64, vp, i64, vp]
     lib.sx_equivariant_bwd.restype = i32
     lib.sx_equivariant_bwd.argtypes = [C.POINTER(sx_equivariant_net), vp, i64, vp, i64, vp, vp, vp, C.POINTER(sx_equivariant_grads), i64, vp]
+    lib.sx_time_coupling_bwd_lds_bytes.restype = C.c_size_t
+    lib.sx_time_coupling_bwd_lds_bytes.argtypes = [C.POINTER(sx_time_coupling_net)]
+    lib.sx_time_coupling_bwd_partial_floats.restype = C.c_size_t
+    lib.sx_time_coupling_bwd_partial_floats.argtypes = [C.POINTER(sx_time_coupling_net), i64]
+    lib.sx_time_coupling_bwd.restype = i32
+    lib.sx_time_coupling_bwd.argtypes = [C.POINTER(sx_time_coupling_net), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sx_time_coupling_grads),
+                                         i64, i32, f32, vp]
     lib.sx_flow_launch_info.restype = i32
     lib.sx_flow_launch_info.argtypes = [C.POINTER(sx_program), i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
 

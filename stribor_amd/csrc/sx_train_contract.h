@@ -1,5 +1,5 @@
 // The weight-gradient contraction of the one-launch training backward kernels (sx_cnf_train.hip, sx_resnet_bwd.hip,
-// sx_equivariant.hip; included by nothing else).  A wave holds 32 rows on the MFMA column; dW = sum over those rows of X Y^T needs
+// sx_equivariant.hip, sx_time_coupling_bwd.hip; included by nothing else).  A wave holds 32 rows on the MFMA column; dW = sum over those rows of X Y^T needs
 // the rows on the K index of BOTH operands, so the two tiles turn through two per-wave LDS slots (feature-major, stride 33) and meet
 // in v_mfma_f32_32x32x2_f32; a bias gradient is a row sum of the same slot.  A wave owns one partial; tc_reduce_kernel sums the
 // partials in slot order, without atomics.  Operands are f32x16, float * and ints: nothing here knows a tile type, an LDS array or
@@ -12,6 +12,8 @@
 #include "sx_common.h"
 
 #define SX_TC_SLOT 1056                  /* one transposed tile: 32 features x (32 rows + 1) */
+#define SX_TC_PRUNE_ROWS 1               /* tc_reduce_entry::prune */
+#define SX_TC_PRUNE_COLS 2
 // Loads whose address depends on nothing in the loop around them would all be lifted to its top and kept live: a compiler-only
 // memory barrier per output tile keeps each tile's reads beside its MFMAs.
 #define SX_NO_HOIST() asm volatile("" ::: "memory")
@@ -94,16 +96,30 @@ __device__ __forceinline__ void tc_stage_t(float *dst, const float *__restrict__
 
 // ---- the partial sum: one thread per gradient element, the slots in order ---------------------------------------------------------
 // A template over the table's size, N <= 16: a file that includes this header and sums its partials otherwise gets no kernel.
+// A kernel that contracted PRUNED operands (sx_time_coupling_bwd.hip) names the rows / columns it kept: element (fx, fy) of the
+// gradient then sits at (its rank among the kept rows, its rank among the kept columns) of the partial, and an element of a row or
+// column that was not kept is written as zero.
 struct tc_reduce_entry {
     float *dst;                          // NULL: not wanted
     int rows, cols, kt, off;             // cols == 0: a vector of `rows` entries (64 floats per tile: the two row halves);
-};                                       // else a [rows, cols] matrix of kt column tiles per tile row; off: inside a partial
+                                         // else a [rows, cols] matrix of kt column tiles per tile row; off: inside a partial
+    int ld;                              // dst's row stride (a vector: its element stride); 0: dense
+    int prune;                           // SX_TC_PRUNE_ROWS | SX_TC_PRUNE_COLS: keep_r / keep_c below name the kept ones
+    uint64_t keep_r, keep_c;             // bit i: row / column i (< 64) was kept
+};
 template <int N>
 struct tc_reduce_args {
     const float *partial;
     tc_reduce_entry e[N];                // in the order of the flat thread index; unused entries: rows == 0
     int n_slots, part_floats;
 };
+
+// index i -> its rank among the kept ones, or -1 when it was not kept
+__device__ __forceinline__ int tc_rank(bool pruned, uint64_t keep, int i) {
+    if (!pruned) return i;
+    if (!((keep >> i) & 1)) return -1;
+    return __popcll(keep & ((1ull << i) - 1));
+}
 
 template <int N>
 __global__ void tc_reduce_kernel(const tc_reduce_args<N> a) {
@@ -113,17 +129,18 @@ __global__ void tc_reduce_kernel(const tc_reduce_args<N> a) {
         const int n = t.cols ? t.rows * t.cols : t.rows;
         if (i >= n) { i -= n; continue; }
         if (t.dst == nullptr) return;
-        int off;
-        if (t.cols) {
-            const int fx = i / t.cols, fy = i - fx * t.cols;
-            off = t.off + ((fx >> 5) * t.kt + (fy >> 5)) * 1024 + tc_tile_off(fx & 31, fy & 31);
-        } else {
-            off = t.off + (i >> 5) * 64 + (i & 31);
-        }
+        int off, fx = i, fy = 0;
+        if (t.cols) { fx = i / t.cols; fy = i - fx * t.cols; }
+        float *dst = t.dst + (t.ld ? (int64_t)fx * t.ld + fy : (int64_t)i);
+        fx = tc_rank(t.prune & SX_TC_PRUNE_ROWS, t.keep_r, fx);
+        fy = tc_rank(t.prune & SX_TC_PRUNE_COLS, t.keep_c, fy);
+        if (fx < 0 || fy < 0) { *dst = 0.f; return; }
+        if (t.cols) off = t.off + ((fx >> 5) * t.kt + (fy >> 5)) * 1024 + tc_tile_off(fx & 31, fy & 31);
+        else off = t.off + (fx >> 5) * 64 + (fx & 31);
         double s = 0.0;                 // up to 2048 slots in a row: the sum is carried in fp64 and rounded once
         const float *p = a.partial + off;
         for (int q = 0; q < a.n_slots; ++q, p += a.part_floats) s += t.cols ? (double)p[0] : (double)p[0] + (double)p[32];
-        t.dst[i] = (float)s;
+        *dst = (float)s;
         return;
     }
 }

@@ -18,21 +18,25 @@ Three execution tiers, fastest first (the first that applies is used; all give t
 * ``Coupling(Spline(quadratic, latent_net=MLP))`` runs the conditioner with the MFMA kernel (pruned to the
   transformed columns) and the spline in ``sx_rqs_coupling`` (parameters staged through LDS per wavefront).
 """
+import ctypes
 import os
 from typing import Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import _hip, debug
 from ..flow import Transform, flatten_rows, graph_rows, graph_wanted
 from ..fused import ProgramBuilder, ProgramCache, _STRUCT_EPOCH
+from ..net.cover import ACTS, kernel_activation, kernel_tensors, linear_stack
 from ..net.mlp import MLP, _chunk_mlp_program
+from ..net.time_net import TimeIdentity, TimeLinear, TimeTanh, TimeLog
 from ..util.mask import get_mask
 from .affine import Affine
 
-__all__ = ['Coupling', 'ContinuousAffineCoupling']
+__all__ = ['Coupling', 'ContinuousAffineCoupling', 'time_coupling_closed_form']
 
 
 def _ceil32(n: int) -> int:
@@ -832,13 +836,155 @@ class Coupling(Transform):
         return True
 
 
+def _time_terms(kind: int, scale, t):
+    """The time nets of net/time_net.py at t [n, 1]: (tau, dtau/dscale, dtau/dt), each [n, 2 * half] (kind 0: half = 1)."""
+    if kind == 0:
+        tau = t.expand(-1, 2)
+        return tau, torch.zeros_like(tau), torch.ones_like(tau)
+    s = scale.reshape(1, -1)
+    if kind == 1:
+        tau = s * t
+        return tau, t.expand_as(tau), s.expand_as(tau)
+    if kind == 2:
+        tau = torch.tanh(s * t)
+        q = 1 - tau * tau
+        return tau, q * t, s * q
+    if kind == 3:
+        es = s.exp()
+        den = es * t + 1
+        return torch.log(den), es * t / den, es / den
+    raise ValueError(f'time kind {kind}')
+
+
+def time_coupling_closed_form(x, t, latent, W1, b1, W2, b2, scale, mask, activation: str, time_kind: int,
+                              concatenate_time: bool, reverse: bool, ldj_scale: float, gy=None, gl=None):
+    """The backward of one ``ContinuousAffineCoupling`` call in closed form, as ``sx_time_coupling_bwd`` computes it (DESIGN.md
+    section 4.20), in torch ops of any dtype on any device: the role ``flows.cnf.hutchinson_closed_form`` plays for the CNF.
+
+    x [n, D], t [n] or [n, 1], latent [n, L] | None, the conditioner's W1 [H, D + L (+ 1)], b1, W2 [2 D, H], b2, the time net's
+    ``scale`` ([1, 2 D] or [1, 2]; None for kind 0), mask [D] of 0 / 1, gy [n, D] | None, gl [n] or [n, 1] | None (None: zeros).
+    -> dict: gx, gt [n], glatent (None without a latent), dW1, db1, dW2, db2, dtime [2 D] (per column) and dscale (dtime folded
+    to the shape of ``scale``; None for kind 0)."""
+    n, D = x.shape
+    m = mask.to(x).reshape(1, D)
+    live = 1 - m
+    L = 0 if latent is None else latent.shape[1]
+    t = t.reshape(n, 1).to(x)
+    parts = [x * m * (0 if D == 1 else 1)]                                          # coupling.py:147-149
+    if L:
+        parts.append(latent)
+    if concatenate_time:
+        parts.append(t)
+    z = torch.cat(parts, -1)
+    act, dact, _ = ACTS[activation]
+    h = act(z @ W1.T + b1)
+    p = h @ W2.T + b2
+    ls, sh = p[:, :D], p[:, D:]
+    tau, tau_s, tau_t = _time_terms(time_kind, scale, t)
+    half = tau.shape[1] // 2
+    ts, th = tau[:, :half], tau[:, half:]
+    a, c = ls * ts, sh * th
+    gy = torch.zeros_like(x) if gy is None else gy
+    sgl = 0 if gl is None else float(ldj_scale) * gl.reshape(n, 1)
+    if reverse:
+        E = torch.exp(-a)
+        g_a = live * (-gy * (x - c) * E + sgl)
+        g_c = -live * gy * E
+    else:
+        E = torch.exp(a)
+        g_a = live * (gy * x * E + sgl)
+        g_c = live * gy
+    gx = live * gy * E + m * gy
+    g_ts, g_th = g_a * ls, g_c * sh
+    e2 = torch.cat([g_a * ts, g_c * th], -1)
+    dW2, db2 = e2.T @ h, e2.sum(0)
+    e1 = dact(h) * (e2 @ W2)
+    dW1, db1 = e1.T @ z, e1.sum(0)
+    gz = e1 @ W1
+    if D != 1:
+        gx = gx + m * gz[:, :D]
+    gt = (g_ts * tau_t[:, :half] + g_th * tau_t[:, half:]).sum(-1)
+    if concatenate_time:
+        gt = gt + gz[:, D + L]
+    dtime = torch.cat([(g_ts * tau_s[:, :half]).sum(0), (g_th * tau_s[:, half:]).sum(0)])
+    return {'gx': gx, 'gt': gt, 'glatent': gz[:, D:D + L] if L else None, 'dW1': dW1, 'db1': db1, 'dW2': dW2, 'db2': db2,
+            'dtime': dtime, 'dscale': None if time_kind == 0 else _fold_dtime(dtime, scale.shape)}
+
+
+def _fold_dtime(dtime, shape):
+    """dtime [2 D] (per column) -> the shape of the time net's ``scale``: [1, 2 D], or [1, 2] (each half summed)."""
+    if int(np.prod(shape)) == dtime.numel():
+        return dtime.reshape(shape)
+    D = dtime.numel() // 2
+    return torch.stack([dtime[:D].sum(), dtime[D:].sum()]).reshape(shape)
+
+
+class _TimeCouplingFn(torch.autograd.Function):
+    """One ``ContinuousAffineCoupling`` call on fp32 rows with a graph.  Forward: the fused one-step program of the no-graph call
+    (the same bits).  Backward: one ``sx_time_coupling_bwd`` call, which recomputes the conditioner from the saved x, t and latent.
+    The parameters are saved too, although the kernel reads them through the plan's descriptor: a parameter changed in place between
+    forward and backward then raises autograd's error, as on the composed path, instead of giving gradients of other weights.
+    Differentiable once, as ``AffineCouplingOp`` is."""
+
+    @staticmethod
+    def forward(ctx, plan, prog, reverse, ldj_scale, x2, t2, lat2, W1, b1, W2, b2, scale):
+        # the log-det is computed for forward() / inverse() too, whose callers drop it: deliberate, one program per direction
+        # serves every method, and y has the no-graph call's bits either way
+        y, ldj, _ = prog.run(x2, lat2, True, True, False, row_t=t2)
+        ctx.plan, ctx.reverse, ctx.ldj_scale = plan, bool(reverse), float(ldj_scale)
+        ctx.scale_shape = None if scale is None else scale.shape
+        ctx.save_for_backward(x2, t2, lat2, W1, b1, W2, b2, scale)
+        ctx.set_materialize_grads(False)
+        return y, ldj
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, gl):
+        x2, t2, lat2 = ctx.saved_tensors[:3]           # (reading the parameters back runs their version check)
+        desc = ctx.plan[0]                              # (ctx.plan keeps the tensors behind its pointers alive)
+        n, D = x2.shape
+        need = ctx.needs_input_grad[4:]                 # x2, t2, lat2, W1, b1, W2, b2, scale
+        out = [None] * 8
+        if (gy is None and gl is None) or not any(need):
+            return (None,) * 4 + tuple(out)
+        dev = x2.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        gy = None if gy is None else gy.to(torch.float32).contiguous()
+        gl = None if gl is None else gl.to(torch.float32).reshape(-1).contiguous()
+        H, in1 = desc.hidden, D + desc.latent_dim + desc.concat_time
+        shapes = [(n, D), (n,), (n, desc.latent_dim), (H, in1), (H,), (2 * D, H), (2 * D,), (2 * D,)]
+        for i, shape in enumerate(shapes):
+            if need[i] and not (i == 2 and lat2 is None):
+                out[i] = new(*shape)
+        if all(g is None for g in out):
+            return (None,) * 4 + tuple(out)
+        rec = _hip.sx_time_coupling_grads()
+        rec.dW1, rec.db1, rec.dW2, rec.db2, rec.dtime = (_hip.ptr(g) for g in out[3:])
+        partial = None
+        if any(g is not None for g in out[3:]):
+            partial = new(_hip.lib().sx_time_coupling_bwd_partial_floats(desc, n))
+        _hip.call('sx_time_coupling_bwd', x2, ctypes.byref(desc), x2.data_ptr(), _hip.ptr(lat2), t2.data_ptr(), _hip.ptr(gy),
+                  _hip.ptr(gl), _hip.ptr(out[0]), _hip.ptr(out[2]), _hip.ptr(out[1]), _hip.ptr(partial), ctypes.byref(rec), n,
+                  int(ctx.reverse), ctx.ldj_scale)
+        if out[7] is not None:
+            out[7] = _fold_dtime(out[7], ctx.scale_shape)
+        return (None,) * 4 + tuple(out)
+
+
 class ContinuousAffineCoupling(Transform):
     """Time-conditioned affine coupling (reference: stribor/flows/coupling.py:98-213): identity at t = 0.
 
     ``latent_net`` (a ``net.MLP``) sees ``cat[x * mask, latent, t]`` (``concatenate_time``) and outputs ``2 * dim``
     values, ``time_net`` (``net.TimeIdentity / TimeLinear / TimeTanh / TimeLog``) embeds t; the conditioner runs as a pruned
     MFMA program, the time embedding, the affine map, the blend and the masked log-det are one pass of
-    ``sx_time_affine_coupling``."""
+    ``sx_time_affine_coupling``.
+
+    With an autograd graph (training) a layer inside the coverage of ``sx_time_coupling_bwd`` -- one hidden layer, ``dim``,
+    ``dim + latent`` and the hidden width at most 64, one of the seven activations whose derivative comes from the output, an
+    in-kernel time net of kind 0..3 -- runs the same fused one-step program forward and ONE backward call (``_TimeCouplingFn``):
+    the conditioner's activations, the ``[n, 2 * live]`` parameter tensor and their cotangents never reach HBM, and every parameter
+    gradient is summed in a fixed order.  Any other layer composes torch ops around ``AffineCouplingOp`` (``_run_composed``).
+    ``_last_path`` says which of the two ('kernel' / 'composed') the last graph-building call took."""
 
     def __init__(self, latent_net: nn.Module, time_net: nn.Module, mask: str, concatenate_time: Optional[bool] = True,
                  **kwargs):
@@ -853,6 +999,7 @@ class ContinuousAffineCoupling(Transform):
         self._masks = {}
         self._masks_epoch = -1
         self._programs = ProgramCache()
+        self._last_path = None                 # 'kernel' | 'composed': what the last graph-building call ran on
 
     def mask_vector(self, dim: int) -> np.ndarray:
         if self._masks_epoch != _STRUCT_EPOCH[0]:
@@ -923,13 +1070,64 @@ class ContinuousAffineCoupling(Transform):
         idx = torch.from_numpy(live.astype(np.int64)).to(device) if half == dim else torch.zeros(len(live), dtype=torch.long, device=device)
         return torch.cat([sc[:half].index_select(0, idx), sc[half:2 * half].index_select(0, idx)]).contiguous()
 
-    def _run(self, x, t, latent, reverse, want_ldj, ldj_scale):
+    # ---- training: the kernel plan of a graph-building call -------------------------------------------------------------------
+    def _train_plan(self, dim: int, latent_dim: int, device):
+        """(sx_time_coupling_net, keep-alive list) for ``sx_time_coupling_bwd`` when it covers this layer at this width, else None
+        (the call then composes torch ops).  Host only: works on CPU modules."""
+        net, tn = self.latent_net, self.time_net
+        if type(net) is not MLP or not net.fusable():
+            return None
+        lins = linear_stack(net.net)
+        if lins is None or len(lins) != 2 or type(tn) not in (TimeIdentity, TimeLinear, TimeTanh, TimeLog):
+            return None
+        kind = tn.kind
+        tensors = [lins[0].weight, lins[0].bias, lins[1].weight, lins[1].bias] + ([tn.scale] if kind else [])
+
+        def build():
+            if not kernel_activation(net.activation_name, [m for m in net.net if not isinstance(m, nn.Linear)]):
+                return None
+            if any(p is None for p in tensors):
+                return None
+            keep = [p.detach() for p in tensors]
+            if not kernel_tensors(keep, torch.device(device)):
+                return None
+            W1, b1, W2, b2 = keep[:4]
+            H, in1 = W1.shape
+            concat = bool(self.concatenate_time)
+            if in1 != dim + latent_dim + int(concat) or tuple(W2.shape) != (2 * dim, H) or b1.numel() != H or b2.numel() != 2 * dim:
+                return None
+            half = 1
+            if kind:
+                if keep[4].numel() not in (2, 2 * dim):
+                    return None
+                half = keep[4].numel() // 2
+            m = self.mask_vector(dim)
+            if m.shape != (dim,) or dim > 64:
+                return None
+            bits = sum(1 << c for c in range(dim) if m[c] > 0.5)
+            d = _hip.sx_time_coupling_net()
+            d.W1, d.b1, d.W2, d.b2 = (p.data_ptr() for p in keep[:4])
+            d.time_scale = keep[4].data_ptr() if kind else None
+            d.mask[0], d.mask[1] = bits & 0xffffffff, bits >> 32
+            d.dim, d.latent_dim, d.hidden, d.act = dim, latent_dim, H, net.act_code
+            d.time_kind, d.time_half, d.concat_time = kind, half, int(concat)
+            if _hip.lib().sx_time_coupling_bwd_lds_bytes(d) == 0:
+                return None
+            return d, keep
+        return self._programs.get(('train-plan', dim, latent_dim, str(device)), build, guards=[p for p in tensors if p is not None])
+
+    def _rows(self, x, t):
         _hip.require_device(x, 'x')
         x2, lead = flatten_rows(x)
-        n, d = x2.shape
+        n = x2.shape[0]
         t2 = t.reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
         if t2.numel() != n:
             t2 = t.expand(*lead, 1).reshape(-1).to(torch.float32).contiguous()
+        return x2, lead, t2
+
+    def _run(self, x, t, latent, reverse, want_ldj, ldj_scale):
+        x2, lead, t2 = self._rows(x, t)
+        n, d = x2.shape
         needs_graph = torch.is_grad_enabled() and (x.requires_grad or t.requires_grad or
                                                     (latent is not None and latent.requires_grad) or
                                                     any(p.requires_grad for p in self.parameters()))
@@ -940,6 +1138,31 @@ class ContinuousAffineCoupling(Transform):
             if prog is not None:
                 y, ldj, _ = prog.run(x2, lat_only, True, want_ldj, False, row_t=t2)
                 return y.reshape(*lead, d), (None if ldj is None else ldj.reshape(*lead, 1))
+        if needs_graph:
+            # training: the fused forward and one backward call where sx_time_coupling_bwd covers the layer
+            ld = 0 if latent is None else latent.shape[-1]
+            plan = self._train_plan(d, ld, x.device) if n > 0 and x.is_cuda and self._fusable() else None
+            prog = self._fused_program(reverse, ldj_scale, d, ld, x.device) if plan is not None else None
+            self._last_path = 'composed' if prog is None else 'kernel'
+            if prog is not None:
+                lat2 = None if latent is None else latent.reshape(n, -1).to(torch.float32).contiguous()
+                lins = linear_stack(self.latent_net.net)
+                y, ldj = _TimeCouplingFn.apply(plan, prog, bool(reverse), float(ldj_scale), x2.to(torch.float32), t2, lat2,
+                                               lins[0].weight, lins[0].bias, lins[1].weight, lins[1].bias,
+                                               self.time_net.scale if self.time_net.kind else None)
+                return y.reshape(*lead, d), (ldj.reshape(*lead, 1) if want_ldj else None)
+        return self._run_composed(x, t, latent, reverse, want_ldj, ldj_scale, rows=(x2, lead, t2))
+
+    def _run_composed(self, x, t, latent, reverse, want_ldj, ldj_scale, rows=None):
+        """The tiers below the one-launch paths: with a graph (or a conditioner / time net that is called as a module) torch ops
+        around ``AffineCouplingOp``; without one, the pruned MFMA program and ``sx_time_affine_coupling``.  `rows`: what
+        ``_rows(x, t)`` gave the caller (``_run``); tests and tools/bench_neural_flow_train.py call it directly, without, on layers
+        the kernel path covers."""
+        x2, lead, t2 = self._rows(x, t) if rows is None else rows
+        n, d = x2.shape
+        needs_graph = torch.is_grad_enabled() and (x.requires_grad or t.requires_grad or
+                                                    (latent is not None and latent.requires_grad) or
+                                                    any(p.requires_grad for p in self.parameters()))
         parts = [] if latent is None else [latent.reshape(n, -1).to(torch.float32)]
         if self.concatenate_time:
             parts.append(t2.reshape(n, 1))                                           # coupling.py:155-156
