@@ -247,6 +247,29 @@ int sx_rqs_slab_fwd(const float *x, const float *h, int64_t ld_h, int32_t hidden
                     float bottom, float top, int64_t n_rows, int32_t dim, int32_t reverse, float ldj_scale, int32_t ldj_accumulate,
                     int32_t h_fragments, int32_t cubic, float *scratch, uint32_t *err_flag, void *stream);
 
+/* The WIDE form of sx_rqs_slab_fwd: rational-quadratic couplings of 17 <= n_bins <= 32 (flows/spline.py:76-87 takes any n_bins,
+ * net/mlp.py:48-58 any width), Coupling(Spline(spline_type='quadratic')).forward / inverse with their log-dets
+ * (flows/coupling.py:69-95, util/rational_quadratic_spline.py:11-251).  ONE transformed column per slab (n_slabs = n_live):
+ *   slots: sx_rqs_slab_wide_slots(n_live) = n_live * 96 rows of the w_fwd pack; slot 32 t + R of slab s carries parameter
+ *   16 ((R>>2)&1) + (R&3) + 4 (R>>3) of tile t (widths | heights | knot derivatives, flows/spline.py:82-86) of column s, so the
+ *   two lanes that hold a sample each receive 16 bins of its element (rational_quadratic_spline.py:101-107);
+ *   x, h, ld_h, hidden, h_fragments, w_fwd, y, live_idx / live_start / n_live, pass_idx / n_pass, left .. top, n_rows, dim,
+ *   err_flag, stream: as sx_rqs_slab_fwd (flows/coupling.py:61-65, 69-95);
+ *   reverse = 0: forward (rational_quadratic_spline.py:236-248), 1: inverse (:212-234); the bin search is search_sorted.py:4-5;
+ *   ldj (nullable) [n_rows] = (ldj_accumulate ? ldj : 0) + ldj_scale * sum over the transformed columns of log|d y / d x|
+ *   (flows/coupling.py:84-95), one partial per column and row, added in column order without atomics: two calls return the same bits;
+ *   scratch: sx_rqs_slab_wide_fwd_scratch_floats(n_rows, n_live) = n_live * n_rows floats (needed when ldj is not NULL). */
+int32_t sx_rqs_slab_wide_slots(int32_t n_live);                                            /* flows/spline.py:82-86 */
+size_t sx_rqs_slab_wide_fwd_scratch_floats(int64_t n_rows, int32_t n_live);                /* flows/coupling.py:84-95 (row log-det) */
+int sx_rqs_slab_wide_fwd(const float *x, const float *h, int64_t ld_h, int32_t hidden,     /* coupling.py:61-65, net/mlp.py:48-58 */
+                         const float *w_fwd, float *y, float *ldj,                         /* spline.py:82-86; coupling.py:69-95 */
+                         const int32_t *live_idx, int32_t live_start, int32_t n_live,      /* coupling.py:61-63 (mask = 0 columns) */
+                         const int32_t *pass_idx, int32_t n_pass,                          /* coupling.py:78, 95 (y = x where mask = 1) */
+                         int32_t n_bins, float left, float right, float bottom, float top, /* spline.py:76-87; rational_quadratic_spline.py:11-20 */
+                         int64_t n_rows, int32_t dim, int32_t reverse,                     /* rational_quadratic_spline.py:212-248 */
+                         float ldj_scale, int32_t ldj_accumulate,                          /* flow.py:42-47 (sign and sum of the log-dets) */
+                         int32_t h_fragments, float *scratch, uint32_t *err_flag, void *stream);   /* net/mlp.py:65 (any finite fp32 row) */
+
 /* Monotone cubic spline, element-wise part -- spline_type='cubic', the reference's default
  * (stribor/util/cubic_spline.py:21-251, util/search_sorted.py:3-5, flows/spline.py:59-61,82-86).
  *   params[n, i*(2K+2) + 0:K]      unnormalised widths  of live dim i

@@ -65,6 +65,7 @@ EXPORTS = ['sx_abi_version', 'sx_fragment_mode', 'sx_last_error', 'sx_build_id',
            'sx_wgrad_scratch_floats', 'sx_wgrad_layer_scratch_floats', 'sx_flow_bwd_max_steps', 'sx_flow_bwd_partials',
            'sx_flow_bwd_run', 'sx_wgrad_reduce', 'sx_wgrad_reduce_batch', 'sx_rqs_slab_slots', 'sx_rqs_slab_scratch_floats', 'sx_rqs_slab_bwd', 'sx_rqs_slab_l1_scratch_floats', 'sx_rqs_slab_l1_bwd',
            'sx_rqs_slab_fwd_scratch_floats', 'sx_rqs_slab_fwd', 'sx_rqs_slab_hidden_floats', 'sx_rqs_slab_hidden',
+           'sx_rqs_slab_wide_slots', 'sx_rqs_slab_wide_fwd_scratch_floats', 'sx_rqs_slab_wide_fwd',
            'sx_resnet_lds_bytes', 'sx_resnet_flow', 'sx_spectral_sigma', 'sx_resnet_bwd_lds_bytes', 'sx_resnet_bwd_partial_floats',
            'sx_resnet_flow_bwd', 'sx_attention_fwd', 'sx_attention_bwd', 'sx_cnf_lds_bytes',
            'sx_cnf_flow', 'sx_cnf_exact_lds_bytes', 'sx_cnf_exact_flow', 'sx_cnf_set_lds_bytes', 'sx_cnf_set_flow',
@@ -270,6 +271,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.sx_rqs_slab_fwd_scratch_floats.argtypes = [i64, i32]
     lib.sx_rqs_slab_fwd.restype = i32
     lib.sx_rqs_slab_fwd.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, f32, f32, f32, f32, i64, i32, i32, f32, i32, i32, i32, vp, vp, vp]
+    lib.sx_rqs_slab_wide_slots.restype = i32
+    lib.sx_rqs_slab_wide_slots.argtypes = [i32]
+    lib.sx_rqs_slab_wide_fwd_scratch_floats.restype = C.c_size_t
+    lib.sx_rqs_slab_wide_fwd_scratch_floats.argtypes = [i64, i32]
+    lib.sx_rqs_slab_wide_fwd.restype = i32             # sx_rqs_slab_fwd's list without `cubic`
+    lib.sx_rqs_slab_wide_fwd.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, f32, f32, f32, f32, i64, i32, i32, f32, i32, i32, vp, vp, vp]
     lib.sx_rqs_slab_hidden_floats.restype = C.c_size_t
     lib.sx_rqs_slab_hidden_floats.argtypes = [i64, i32]
     lib.sx_rqs_slab_hidden.restype = i32

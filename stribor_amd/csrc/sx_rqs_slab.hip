@@ -863,6 +863,136 @@ __device__ __forceinline__ void rqs_slab_eval(rqsb_f16v &Sp, rqsb_f16v &Op, cons
     ljd = inside ? l : 0.f;
 }
 
+// The WIDE form, 17 <= K <= 32 bins: ONE transformed column per slab, its element in a lane PAIR -- lane (sample, half hh) holds bins
+// 16 hh .. 16 hh + 15 of both sides in Sp / Op and knot derivatives 16 hh .. 16 hh + 15 (of the K - 1) in Dp.  rqs_slab_eval's
+// arithmetic, split where the two halves meet:
+//   * the soft-max maximum and sum are taken over both halves (max and + commute: both lanes hold the same bits);
+//   * half 1's cumulative sums START from half 0's total, so every knot is the sequential cumsum's (a first sweep forms the totals);
+//   * each half sweeps its own 16 knots with selects; the pair then exchanges b, co_b, ks_b, co_n, ks_n (the sweep's `have_next`
+//     rides in b's bit 8) and the two derivatives each half picked for the combined bin -- thirteen 32-lane exchanges in all --,
+//     and BOTH lanes run the closing form on identical values.
+// The hooks are rqs_slab_eval's, at the same points.
+template <bool REV, class Hook>
+__device__ __forceinline__ void rqs_slab_eval_wide(rqsb_f16v &Sp, rqsb_f16v &Op, const rqsb_f16v &Dp, int K, int hh, float xv, float slo,
+                                                   float shi, float olo, float ohi, float &out, float &ljd, Hook &hk) {
+    constexpr float LOG2E = 1.44269504088896341f, LN2 = 0.69314718055994531f;
+    const int k0 = 16 * hh;                                         // this half's first bin (and first knot derivative)
+    const float norm = 1.f - RQS_MIN_BIN * (float)K;
+    const float span_s = shi - slo, span_o = ohi - olo;
+    const bool inside = (xv >= slo) && (xv <= shi);                 // :71 closed interval
+    const float xin = inside ? xv : slo;
+    float ms = Sp[0], mo = Op[0];                                   // (bin 16 exists: K >= 17)
+#pragma unroll
+    for (int k = 1; k < 16; ++k) {
+        const bool used = k0 + k < K;
+        ms = used ? fmaxf(ms, Sp[k]) : ms;
+        mo = used ? fmaxf(mo, Op[k]) : mo;
+        if (k % 5 == 0) slabf_hook_seq<3, Hook>::template call<0>(hk, k / 5 - 1, ms, mo);
+    }
+    ms = fmaxf(ms, __shfl_xor(ms, 32, 64));
+    mo = fmaxf(mo, __shfl_xor(mo, 32, 64));
+    float ss = 0.f, so = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool used = k0 + k < K;
+        const float es = used ? __builtin_amdgcn_exp2f((Sp[k] - ms) * LOG2E) : 0.f;
+        const float eo = used ? __builtin_amdgcn_exp2f((Op[k] - mo) * LOG2E) : 0.f;
+        Sp[k] = es;
+        Op[k] = eo;
+        ss += es;
+        so += eo;
+        slabf_hook_seq<16, Hook>::template call<3>(hk, k, ss, so);
+    }
+    ss += __shfl_xor(ss, 32, 64);
+    so += __shfl_xor(so, 32, 64);
+    const float ns = norm * __builtin_amdgcn_rcpf(ss), no = norm * __builtin_amdgcn_rcpf(so);    // bin size_k = MIN + e_k n (:101-105)
+    // where this half's cumulative sums start: half 0's total over its 16 bins, in the order the sweep below adds them
+    float cs = 0.f, co = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        cs += fmaf(Sp[k], ns, RQS_MIN_BIN);
+        co += fmaf(Op[k], no, RQS_MIN_BIN);
+    }
+    {
+        const float cs0 = __shfl_xor(cs, 32, 64), co0 = __shfl_xor(co, 32, 64);
+        cs = hh ? cs0 : 0.f;
+        co = hh ? co0 : 0.f;
+    }
+    // this half's knots 16 hh + 1 .. 16 hh + 16: rqs_slab_eval's sweep
+    int b = 0;
+    float co_b = 0.f, co_n = 0.f, ks_b = slo, ks_n = shi;
+    bool have_next = false;
+#pragma unroll
+    for (int j = 1; j <= 16; ++j) {
+        const bool used = k0 + j <= K;
+        const bool last = (k0 + j == K);
+        cs += fmaf(Sp[j - 1], ns, RQS_MIN_BIN);
+        co += fmaf(Op[j - 1], no, RQS_MIN_BIN);
+        const float ks = last ? shi : fmaf(span_s, cs, slo);        // ends pinned (:186-192)
+        const bool ge = xin >= (last ? ks + RQS_EPS : ks);
+        const bool take = used && ge && !last;
+        const bool nxt = used && !ge && !have_next;
+        b = take ? k0 + j : b;
+        co_b = take ? co : co_b;
+        ks_b = take ? ks : ks_b;
+        co_n = nxt ? co : co_n;
+        ks_n = nxt ? ks : ks_n;
+        have_next = have_next || nxt;
+        slabf_hook_seq<16, Hook>::template call<19>(hk, j - 1, cs, co, co_b, ks_b, co_n, ks_n, b);
+    }
+    // the pair: the bin is the LAST knot taken (half 1's where it took one), the knot behind it the FIRST not taken (half 0's where it
+    // has one) -- what one sweep over all the knots keeps
+    {
+        const int bx = b | (have_next ? 256 : 0);
+        const int bx_o = __shfl_xor(bx, 32, 64);
+        const float cob_o = __shfl_xor(co_b, 32, 64), ksb_o = __shfl_xor(ks_b, 32, 64);
+        const float con_o = __shfl_xor(co_n, 32, 64), ksn_o = __shfl_xor(ks_n, 32, 64);
+        const int bx0 = hh ? bx_o : bx, bx1 = hh ? bx : bx_o;
+        const bool took1 = (bx1 & 255) != 0, next0 = (bx0 & 256) != 0;
+        const bool b_own = took1 ? hh != 0 : hh == 0, n_own = next0 ? hh == 0 : hh != 0;
+        b = (took1 ? bx1 : bx0) & 255;
+        co_b = b_own ? co_b : cob_o;
+        ks_b = b_own ? ks_b : ksb_o;
+        co_n = n_own ? co_n : con_o;
+        ks_n = n_own ? ks_n : ksn_o;
+    }
+    const bool first = (b == 0), lastbin = (b + 1 == K);
+    const float ko_b = first ? olo : fmaf(span_o, co_b, olo);
+    const float ko_n = lastbin ? ohi : fmaf(span_o, co_n, olo);
+    // knot derivatives b - 1 and b of the K - 1: each from the half that holds it (index >> 4), the boundary value where there is none
+    float u_b = RQS_BOUNDARY_DERIV, u_n = RQS_BOUNDARY_DERIV;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool used = k0 + k < K - 1;
+        u_n = (used && b == k0 + k) ? Dp[k] : u_n;
+        u_b = (used && b == k0 + k + 1) ? Dp[k] : u_b;
+        if (k % 3 == 2) slabf_hook_seq<5, Hook>::template call<35>(hk, k / 3, u_n, u_b);
+    }
+    {
+        const float un_o = __shfl_xor(u_n, 32, 64), ub_o = __shfl_xor(u_b, 32, 64);
+        u_n = ((b >> 4) == hh) ? u_n : un_o;
+        u_b = (((b - 1) >> 4) == hh) ? u_b : ub_o;
+    }
+    float d_b = rqs_knot_deriv(u_b);                                                                                      // :107
+    hk.template at<40>(d_b);
+    float d_n = rqs_knot_deriv(u_n);
+    hk.template at<41>(d_n);
+    const float cw_b = REV ? ko_b : ks_b, w_b = REV ? ko_n - ko_b : ks_n - ks_b;
+    const float ch_b = REV ? ks_b : ko_b, h_b = REV ? ks_n - ks_b : ko_n - ko_b;
+    float s_b = h_b * fast_rcp(w_b);
+    hk.template at<42>(s_b);
+    slabf_close_hook<Hook> ch{hk};
+    const rqs_closed c = rqs_close<REV>(d_b, d_n, s_b, cw_b, w_b, ch_b, h_b, xin, ch);
+    float l1 = __builtin_amdgcn_logf(REV ? c.den : c.dnum);
+    hk.template at<47>(l1);
+    float l2 = __builtin_amdgcn_logf(REV ? c.dnum : c.den);
+    hk.template at<48>(l2);
+    float l = REV ? (2.f * l1 - l2) * LN2 : (l1 - 2.f * l2) * LN2;
+    hk.template at<49>(l);
+    out = inside ? c.out : xv;                                      // :86-87 linear tails
+    ljd = inside ? l : 0.f;
+}
+
 // The monotone CUBIC spline (util/cubic_spline.py:21-251, the reference's default spline_type) of one element on registers: Wp / Hp
 // hold its K widths / heights (K <= 16, entries beyond K ignored), Dp[0..1] its two boundary-derivative parameters -- cubic_kernel's
 // arithmetic (sx_rqs.hip, sx_cubic_core.h) with the parameters in MFMA accumulators: one sweep with selects keeps the sizes of
@@ -1025,8 +1155,11 @@ struct slabf_pipe {
 // per tile were paid n_slabs times (a third of this kernel's vector work at 160 hidden units).
 // PIPE (HFRAG only, HT >= 3: the evaluation's hooks reach into hidden tile 2): the software-pipelined chunk loop.
 // CUBIC: monotone cubic splines (2K + 2 parameters per element, the two boundary derivatives in the third tile), unpipelined.
-template <int KC, bool HFULL, bool REV, bool HFRAG, bool PIPE, bool CUBIC>
+// WIDE: 17 .. 32 bins, ONE transformed column per slab and its element in a lane pair (rqs_slab_eval_wide; slab_slot_rows_wide is the
+// slot map), unpipelined: both halves read the element's x, half 0 writes y and the slab's log-det partial -- the element's own value.
+template <int KC, bool HFULL, bool REV, bool HFRAG, bool PIPE, bool CUBIC, bool WIDE = false>
 __global__ __launch_bounds__(512, 1) void rqs_slab_fwd_kernel(const slabf_args k) {
+    static_assert(!WIDE || (KC == 0 && !PIPE && !CUBIC), "the wide form: run-time bin count, unpipelined, rational-quadratic");
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int HT = k.HT;
     int slab, range;
@@ -1045,7 +1178,8 @@ __global__ __launch_bounds__(512, 1) void rqs_slab_fwd_kernel(const slabf_args k
     __syncthreads();
     const wptr w = make_wptr(0, lane);
     const int j = lane & 31, hh = lane >> 5;
-    const int ci = 2 * slab + hh;                                       // this lane's transformed column (index into live)
+    const int ci = WIDE ? slab : 2 * slab + hh;                         // this lane's transformed column (index into live)
+    [[maybe_unused]] const int pi = WIDE ? 2 * slab + hh : ci;                     // ... and the first pass-through column it copies
     const bool col_ok = ci < k.n_live;
     const int col = col_ok ? (k.live_idx ? k.live_idx[ci] : k.l0 + ci) : 0;
     uint64_t any_bad = 0;
@@ -1122,8 +1256,8 @@ __global__ __launch_bounds__(512, 1) void rqs_slab_fwd_kernel(const slabf_args k
         const float *hb = k.h + row0 * k.ld_h;
         const uint32_t hoff = (uint32_t)jc * (uint32_t)k.ld_h + 4u * hh, xoff = (uint32_t)jc * (uint32_t)k.dim + (uint32_t)col;
         const float xl = (k.x + row0 * k.dim)[xoff];
-        const bool pdo = k.pass_idx != nullptr && j < n_here && ci < k.n_pass;      // pass-through columns: see the pipelined loop
-        const uint32_t po = pdo ? (uint32_t)j * (uint32_t)k.dim + (uint32_t)k.pass_idx[ci] : 0u;
+        const bool pdo = k.pass_idx != nullptr && j < n_here && pi < k.n_pass;      // pass-through columns: see the pipelined loop
+        const uint32_t po = pdo ? (uint32_t)j * (uint32_t)k.dim + (uint32_t)k.pass_idx[pi] : 0u;
         const float pv = pdo ? (k.x + row0 * k.dim)[po] : 0.f;
         auto load_h = [&](int m, f32x4 (&v)[4]) {
 #pragma unroll
@@ -1199,22 +1333,24 @@ __global__ __launch_bounds__(512, 1) void rqs_slab_fwd_kernel(const slabf_args k
         float out, ljd;
         slabf_nohook nh;
         if constexpr (CUBIC) cubic_slab_eval<REV>(acc[0].v[0], acc[1].v[0], acc[2].v[0], k.K, xv, k.left, k.right, k.log_span, k.ref_ldj != 0, valid, out, ljd);
+        else if constexpr (WIDE && REV) rqs_slab_eval_wide<true>(acc[1].v[0], acc[0].v[0], acc[2].v[0], k.K, hh, xv, k.bottom, k.top, k.left, k.right, out, ljd, nh);
+        else if constexpr (WIDE) rqs_slab_eval_wide<false>(acc[0].v[0], acc[1].v[0], acc[2].v[0], k.K, hh, xv, k.left, k.right, k.bottom, k.top, out, ljd, nh);
         else if constexpr (REV) rqs_slab_eval<KC, true>(acc[1].v[0], acc[0].v[0], acc[2].v[0], k.K, xv, k.bottom, k.top, k.left, k.right, out, ljd, nh);
         else rqs_slab_eval<KC, false>(acc[0].v[0], acc[1].v[0], acc[2].v[0], k.K, xv, k.left, k.right, k.bottom, k.top, out, ljd, nh);
         // (HFRAG: a row whose h left fp16's range carries NaN fragments -- flagged by the kernel that wrote them)
         const bool bad = HFRAG ? nan_h : rng_bad_sample(rg, lane);
         any_bad |= rg.bad;
-        if (valid) (k.y + row0 * k.dim)[xoff] = bad ? __builtin_nanf("") : out;
+        if (valid && (!WIDE || hh == 0)) (k.y + row0 * k.dim)[xoff] = bad ? __builtin_nanf("") : out;
         if (pdo) {
             (k.y + row0 * k.dim)[po] = pv;
-            for (int q = ci + 2 * k.n_slabs; q < k.n_pass; q += 2 * k.n_slabs) {
+            for (int q = pi + 2 * k.n_slabs; q < k.n_pass; q += 2 * k.n_slabs) {
                 const uint32_t pq = (uint32_t)j * (uint32_t)k.dim + (uint32_t)k.pass_idx[q];
                 (k.y + row0 * k.dim)[pq] = (k.x + row0 * k.dim)[pq];
             }
         }
         if (k.ldj_part != nullptr) {
             float lsum = valid ? ljd : 0.f;
-            lsum += __shfl_xor(lsum, 32, 64);
+            if constexpr (!WIDE) lsum += __shfl_xor(lsum, 32, 64);
             if (hh == 0 && j < n_here) k.ldj_part[(size_t)slab * k.n_rows + row0 + j] = bad ? __builtin_nanf("") : lsum;
         }
     }
@@ -1531,6 +1667,77 @@ extern "C" int sx_rqs_slab_fwd(const float *x, const float *h, int64_t ld_h, int
 #undef SX_SLABC
 #undef SX_SLABF
 #undef SX_SLABF2
+    SX_LAUNCH_CHECK();
+    if (ldj != nullptr) {
+        hipLaunchKernelGGL(rqs_slab_ldj_reduce_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, scratch, n_slabs,
+                           n_rows, ldj_scale, (int)(ldj_accumulate != 0), ldj);
+        SX_LAUNCH_CHECK();
+    }
+    return SX_OK;
+}
+
+// ---- the wide form: 17 .. 32 bins, one transformed column per slab (rqs_slab_fwd_kernel<..., WIDE>) ----
+extern "C" int32_t sx_rqs_slab_wide_slots(int32_t n_live) { return (n_live < 1 || n_live > (1 << 20)) ? 0 : n_live * 96; }
+
+extern "C" size_t sx_rqs_slab_wide_fwd_scratch_floats(int64_t n_rows, int32_t n_live) {
+    if (n_rows < 0 || n_rows >= ((int64_t)1 << 36) || n_live < 1 || n_live > (1 << 20)) return 0;
+    return (size_t)n_live * (size_t)n_rows;
+}
+
+extern "C" int sx_rqs_slab_wide_fwd(const float *x, const float *h, int64_t ld_h, int32_t hidden, const float *w_fwd, float *y, float *ldj,
+                                    const int32_t *live_idx, int32_t live_start, int32_t n_live, const int32_t *pass_idx, int32_t n_pass,
+                                    int32_t n_bins, float left, float right, float bottom, float top, int64_t n_rows, int32_t dim,
+                                    int32_t reverse, float ldj_scale, int32_t ldj_accumulate, int32_t h_fragments, float *scratch,
+                                    uint32_t *err_flag, void *stream) {
+    SX_REQUIRE(x && h && w_fwd && y, "sx_rqs_slab_wide_fwd: null pointer");
+    SX_REQUIRE(!h_fragments || ((uintptr_t)h & 15) == 0, "sx_rqs_slab_wide_fwd: h fragments must be 16-byte aligned");
+    SX_REQUIRE(ldj == nullptr || scratch != nullptr, "sx_rqs_slab_wide_fwd: the row log-det needs the scratch buffer");
+    SX_REQUIRE(dim > 0 && n_live > 0 && n_live <= dim && n_rows >= 0, "sx_rqs_slab_wide_fwd: bad sizes");
+    SX_REQUIRE(n_pass >= 0 && n_pass <= dim - n_live && (n_pass == 0 || pass_idx != nullptr), "sx_rqs_slab_wide_fwd: bad pass-through columns");
+    SX_REQUIRE(n_bins >= 17 && n_bins <= 32, "sx_rqs_slab_wide_fwd: n_bins must be in 17..32 (got %d)", n_bins);
+    SX_REQUIRE(hidden >= 1 && hidden <= 256, "sx_rqs_slab_wide_fwd: hidden width must be in 1..256 (got %d)", hidden);
+    SX_REQUIRE(h_fragments || ld_h >= hidden, "sx_rqs_slab_wide_fwd: ld_h < hidden");
+    SX_REQUIRE(n_rows < ((int64_t)1 << 36), "sx_rqs_slab_wide_fwd: too many rows");
+    SX_REQUIRE(right > left && top > bottom, "sx_rqs_slab_wide_fwd: empty domain");
+    SX_REQUIRE(reverse >= 0 && reverse <= 1, "sx_rqs_slab_wide_fwd: reverse must be 0 | 1");
+    SX_REQUIRE(((uintptr_t)w_fwd & 15) == 0, "sx_rqs_slab_wide_fwd: packed weights must be 16-byte aligned");
+    if (n_rows == 0) return SX_OK;
+    hipStream_t st = sx_stream(stream);
+    const int n_slabs = n_live, HT = (hidden + 31) / 32;
+    const int n_chunks = (int)((n_rows + 31) / 32);
+    // the launch shape of sx_rqs_slab_fwd: one 8-wave workgroup per CU at a time, two rounds of them, ranges in multiples of 8
+    int r = (512 + n_slabs - 1) / n_slabs;
+    const int cap = (n_chunks + 7) / 8;
+    if (r > cap) r = cap;
+    if (r >= 8) r &= ~7;
+    const int n_ranges = r < 1 ? 1 : r;
+    slabf_args k;
+    k.x = x; k.h = h; k.wf = w_fwd; k.y = y; k.ldj_part = ldj ? scratch : nullptr; k.live_idx = live_idx; k.pass_idx = n_pass > 0 ? pass_idx : nullptr; k.flags = err_flag;
+    k.n_rows = n_rows; k.ld_h = ld_h; k.l0 = live_start; k.n_live = n_live; k.n_pass = n_pass; k.K = n_bins; k.dim = dim; k.H = hidden; k.HT = HT;
+    k.n_slabs = n_slabs; k.n_chunks = n_chunks; k.n_ranges = n_ranges; k.xcd_map = (n_ranges % 8 == 0);
+    k.left = left; k.right = right; k.bottom = bottom; k.top = top;
+    k.log_span = logf(right - left); k.ref_ldj = 0;
+    const size_t lds = (size_t)(3 * HT * 1024 + 128) * sizeof(float);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const bool hfull = hidden == 32 * HT && ld_h % 4 == 0 && ((uintptr_t)h & 15) == 0;
+#define SX_SLABW(HF_, REV_, FR_, ID_)                                                                              \
+    do {                                                                                                           \
+        auto kern = rqs_slab_fwd_kernel<0, HF_, REV_, FR_, false, false, true>;                                    \
+        static int lds_allowed[6][64];                                                                             \
+        if (lds > 48 * 1024 && lds_allowed[ID_][dev & 63] < (int)lds) {                                            \
+            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            if (e != hipSuccess) { sx_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; } \
+            lds_allowed[ID_][dev & 63] = (int)lds;                                                                 \
+        }                                                                                                          \
+        hipLaunchKernelGGL(kern, dim3(n_slabs * n_ranges), dim3(512), lds, st, k);                                 \
+    } while (0)
+    if (reverse) {
+        if (h_fragments) SX_SLABW(true, true, true, 0); else if (hfull) SX_SLABW(true, true, false, 1); else SX_SLABW(false, true, false, 2);
+    } else {
+        if (h_fragments) SX_SLABW(true, false, true, 3); else if (hfull) SX_SLABW(true, false, false, 4); else SX_SLABW(false, false, false, 5);
+    }
+#undef SX_SLABW
     SX_LAUNCH_CHECK();
     if (ldj != nullptr) {
         hipLaunchKernelGGL(rqs_slab_ldj_reduce_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, scratch, n_slabs,

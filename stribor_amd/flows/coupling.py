@@ -339,7 +339,7 @@ class Coupling(Transform):
         try:
             return self._run_spline_slab(x2, lat2, reverse, want_ldj, ldj_scale)
         except NotImplementedError:
-            pass                                        # > 16 bins, > 256 hidden units, bf16 rows, 'exact' (and 'auto' after a range flag): below
+            pass                                        # > 32 bins (cubic: > 16), > 256 hidden units, bf16 rows, 'exact' (and 'auto' after a range flag): below
         progs, live_idx, live_start, n_live, width = self._spline_program(d, 0 if lat2 is None else lat2.shape[1],
                                                                           x2.device)
         params = torch.empty(n, width, dtype=torch.float32, device=x2.device)
@@ -363,20 +363,22 @@ class Coupling(Transform):
         spline.py:76-87 and net/mlp.py:48-58 take any width): everything before the last Linear leaves the last hidden activation h
         in HBM (640 B per row at H = 160 -- against 6 KB per row of spline parameters; one hidden layer: sx_rqs_slab_hidden writes
         it as MFMA fragments, deeper conditioners: MLP programs, row-major), and sx_rqs_slab_fwd evaluates  params = h W2^T + b2
-        and the spline slab by slab on the matrix pipe.
+        and the spline slab by slab on the matrix pipe.  Rational-quadratic splines of 17 .. 32 bins take the WIDE form (one
+        transformed column per slab, sx_rqs_slab_wide_fwd; cache['wide']); cubic splines stop at 16 bins.
         -> (MLP programs [(program, first column of h)], input slots of the hidden kernel | None, slot -> row of the last Linear,
             hidden slots, live_idx, live_start, n_live, H, pack cache)."""
         key = ('spline-slab', dim, latent_dim, str(device))
 
         def build():
-            from .spline import slab_slot_rows
+            from .spline import slab_slot_rows, slab_slot_rows_wide
             net, sp = self._net(), self.transform
             lin = net.linears()
             H = lin[-1][0].shape[1]
             widths = [w.shape[0] for (w, _) in lin[:-1]]
             cubic = sp.spline_type == 'cubic'
-            if sp.n_bins > 16 or H > 256:
-                raise NotImplementedError('slab tier: splines of up to 16 bins behind up to 256 hidden units')
+            wide = sp.n_bins > 16
+            if sp.n_bins > (16 if cubic else 32) or H > 256:
+                raise NotImplementedError('slab tier: splines of up to 32 bins (cubic: 16) behind up to 256 hidden units')
             one_hidden = len(lin) == 2 and lin[0][1] is not None
             if dim + latent_dim > 128 if one_hidden else (_ceil32(dim) + _ceil32(latent_dim) > 4 or max(widths) > 128):
                 raise NotImplementedError('slab tier: conditioner inputs of up to 128 columns; deep conditioners of up to 128 units')
@@ -386,7 +388,7 @@ class Coupling(Transform):
             if dim == 1:
                 cond = np.zeros(1, dtype=bool)                                       # coupling.py:62-63
             P = sp.params_per_element
-            rel = slab_slot_rows(len(live), sp.n_bins, cubic)                        # slot -> row of the compact (live) parameter block
+            rel = slab_slot_rows_wide(len(live), sp.n_bins) if wide else slab_slot_rows(len(live), sp.n_bins, cubic)      # slot -> row of the compact (live) parameter block
             rows_np = (live[:, None] * P + np.arange(P)[None, :]).reshape(-1)        # spline.py:82-86
             glob = np.where(rel >= 0, rows_np[np.clip(rel, 0, len(rows_np) - 1)], -1).astype(np.int32)
             hid = np.full(_ceil32(H) * 32, -1, dtype=np.int32)
@@ -417,6 +419,8 @@ class Coupling(Transform):
             live_idx = None if contiguous else torch.from_numpy(live.astype(np.int32)).to(device)
             passthru = np.nonzero(m > 0.5)[0].astype(np.int32)               # y = x there: copied by the slab kernel
             cache = {'pass_idx': torch.from_numpy(passthru).to(device) if len(passthru) else None, 'n_pass': len(passthru), 'cond_words': cond_words}
+            if wide:
+                cache['wide'] = True
             return (progs, in_slots, torch.from_numpy(glob).to(device), torch.from_numpy(hid).to(device), live_idx, int(live[0]), len(live), H, cache)
         return self._programs.get(key, build)
 
@@ -435,6 +439,7 @@ class Coupling(Transform):
         dev = x2.device
         ld = 0 if lat2 is None else lat2.shape[1]
         progs, in_slots, slot_rows, hid_idx, live_idx, live_start, n_live, H, cache = self._spline_slab_plan(d, ld, dev)
+        wide = cache.get('wide', False)              # 17 .. 32 bins: one column per slab, sx_rqs_slab_wide_fwd
         net = self._net()
         lin = net.linears()
         W2, b2 = lin[-1]
@@ -448,7 +453,7 @@ class Coupling(Transform):
         ps = [W2, b2] + ([lin[0][0], lin[0][1]] if in_slots is not None else [])
         stamp = tuple((p.data_ptr(), p._version) for p in ps)
         if cache.get('stamp') != stamp:
-            mt, ht = lib.sx_rqs_slab_slots(n_live) // 32, _ceil32(H)
+            mt, ht = (lib.sx_rqs_slab_wide_slots(n_live) if wide else lib.sx_rqs_slab_slots(n_live)) // 32, _ceil32(H)
             packs = torch.empty(_hip.packed_linear_floats(mt, ht), dtype=torch.float32, device=dev)
             Wc, bc = W2.detach().contiguous(), b2.detach().contiguous()
             _hip.call('sx_pack_linear', x2, Wc.data_ptr(), bc.data_ptr(), Wc.shape[0], H, slot_rows.data_ptr(), hid_idx.data_ptr(),
@@ -481,13 +486,15 @@ class Coupling(Transform):
         y = torch.empty_like(x2)
         ldj = torch.empty(n, dtype=torch.float32, device=dev) if want_ldj else None
         with _hip.device_of(x2):
-            sc = _hip.scratch(dev, lib.sx_rqs_slab_fwd_scratch_floats(n, n_live)) if want_ldj else None
+            sc = _hip.scratch(dev, (lib.sx_rqs_slab_wide_fwd_scratch_floats if wide else lib.sx_rqs_slab_fwd_scratch_floats)(n, n_live)) if want_ldj else None
         # cubic splines: a coupling's inverse log-det is MINUS the FORWARD log-det at the inverted point (flow.py:42-47): reverse = 2
         rev = (2 if (cubic and want_ldj) else 1) if reverse else 0
-        _hip.call('sx_rqs_slab_fwd', x2, x2.data_ptr(), h.data_ptr(), ld_h, H, packs.data_ptr(), y.data_ptr(), _hip.ptr(ldj),
+        # (the wide entry takes the same list without `cubic`)
+        _hip.call('sx_rqs_slab_wide_fwd' if wide else 'sx_rqs_slab_fwd', x2, x2.data_ptr(), h.data_ptr(), ld_h, H, packs.data_ptr(),
+                  y.data_ptr(), _hip.ptr(ldj),
                   _hip.ptr(live_idx), live_start, n_live, _hip.ptr(cache['pass_idx']), cache['n_pass'], sp.n_bins, float(sp.lower),
                   float(sp.upper), float(sp.lower),
-                  float(sp.upper), n, d, rev, float(ldj_scale), 0, frag, int(cubic), _hip.ptr(sc), flag)
+                  float(sp.upper), n, d, rev, float(ldj_scale), 0, frag, *(() if wide else (int(cubic),)), _hip.ptr(sc), flag)
         if mode == 'auto':                          # never hand back a NaN-poisoned result: the tier below re-runs the layer exactly
             torch.cuda.current_stream(dev).synchronize()
             with _hip.device_of(x2):

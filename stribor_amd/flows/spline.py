@@ -145,6 +145,24 @@ def slab_slot_rows(n_live: int, n_bins: int, cubic: bool = False):
     return rows
 
 
+def slab_slot_rows_wide(n_live: int, n_bins: int):
+    """sx_rqs_slab_wide_fwd's slot -> parameter-row map (rational-quadratic splines of 17 .. 32 bins): slab s holds ONE transformed
+    column, s, in the same three 32-slot tiles; slot 32 t + R carries parameter 16 half + (R&3) + 4 (R>>3) of it, half = (R>>2)&1 --
+    in C-fragment order the lane pair of a sample then holds bins 16 half .. 16 half + 15 of its element.  Rows as slab_slot_rows
+    (P = 3K-1: K widths, K heights, K-1 knot derivatives); -1 = padding."""
+    import numpy as np
+    K = n_bins
+    P = 3 * K - 1
+    rows = np.full(n_live * 96, -1, dtype=np.int32)
+    for s in range(n_live):
+        for t in range(3):
+            for R in range(32):
+                k = 16 * ((R >> 2) & 1) + (R & 3) + 4 * (R >> 3)
+                if k < (K - 1 if t == 2 else K):
+                    rows[s * 96 + 32 * t + R] = s * P + t * K + k
+    return rows
+
+
 # The slab backward's scratch grows with the rows of ONE call (dh partials: n_groups x n_chunks x HT KiB-tiles -- 10.7 GB for 2^20
 # rows at 160 hidden units, more than the parameter tensor the tier exists to avoid, ADVICE r5) and `_hip.scratch` keeps the
 # block for the life of the (device, stream).  Calls are therefore cut into row blocks whose scratch stays under a budget

@@ -1,5 +1,5 @@
 """Quantifies the fused tier's cliffs: log_prob time per 2^18 rows of 4-layer flows just inside and just beyond
-each limit of the one-launch tier -- hidden width 128 | 160, columns 128 | 160, spline bins 16 | 24 -- with the tier
+each limit of the one-launch tier -- hidden width 128 | 160, columns 128 | 160, spline bins 16 | 24, both at once -- with the tier
 that answered.  python tools/bench_cliffs.py  -> one JSON line per case."""
 import json
 import os
@@ -8,6 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import stribor_amd as st
+from stribor_amd import debug
 from stribor_amd.util import flowdesc as fd
 
 ROWS = 1 << 18
@@ -37,6 +38,8 @@ def main():
         cases.append(('rqs', 64, 64, K))
     cases.append(('rqs', 64, 160, 16))
     cases.append(('rqs', 64, 256, 16))
+    for hidden, K in ((160, 24), (160, 32), (256, 32)):      # the slab tier's wide form: 17 .. 32 bins, one column per slab
+        cases.append(('rqs', 64, hidden, K))
     cases.append(('cubic', 64, 64, 8))
     cases.append(('cubic', 64, 64, 16))
     cases.append(('cubic', 64, 160, 16))
@@ -53,7 +56,7 @@ def main():
             x = torch.randn(ROWS, dim, device=dev)
             fused = flow._fused_program(True, dim, 0, dev) is not None
             tier = 'one launch' if fused else 'layer by layer'
-            if not fused and kind in ('rqs', 'cubic'):
+            if not fused and kind in ('rqs', 'cubic') and not debug.on('STRIBOR_SPLINE_NO_SLAB_FWD'):
                 try:                            # the slab forward tier (hidden layers beyond 128 units): two launches per layer
                     flow.transforms[0]._spline_slab_plan(dim, 0, dev)
                     tier = 'slab forward'
